@@ -1,12 +1,20 @@
 """plan() calls/sec on MI355X — BASELINE.json's metric.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E] [--config c2] [--iterations 6]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch of synthetic input: E independent plans
 (synthetic SimNorm latents, random-init weights of the named architecture, in-kernel Philox noise —
 everything of TDMPC2._plan after encode()).  Inputs are resident in HBM before the timed region.
 For N > 1 launch with torch.distributed.run (one rank per GPU, RCCL); environments are sharded,
 E per GPU (weak scaling), no collective in the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times exactly K steps and prints the headline line (its roofline comes from HIP events of
+those same steps).  --full adds everything else the line used to carry: the >= 2 s second region, clocks under load,
+single-environment latencies, the parity check against tests/golden/c2.npz, the exact-fp32 companion, the c3 / c4 / c5
+legs, the eager / torch.compile / CPU baselines and the rocprofv3 traffic children (the --skip-* options apply there).
+--dump-outputs DIR writes what the last timed step returned to its caller (rank 0's action [E, A] and the updated
+prev_mean [E, H, A]) as DIR/<name>.npy in float32; the inputs are seeded, so the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -27,6 +35,7 @@ from tdmpc2_amd.config import get_discount, named_config  # noqa: E402
 FP32_MFMA_PEAK_TFLOPS = 157.3  # /opt/skills/guides/MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense
 MIN_TIMED_S = 2.0           # the timed region is extended to at least this (see main)
 F16_MFMA_PEAK_TFLOPS = 2500.0  # same guide: BF16/F16 MFMA, dense (the 2:1-sparsity figure is NOT used)
+DUMP_MAX_BYTES = 64 * 10**6  # --dump-outputs: larger outputs are written as a fixed, seeded sample of environment rows
 
 
 def per_row_macs(cfg):
@@ -116,6 +125,24 @@ def disc_pow_rows(cfg, n_envs, device):
         vals.append(float(d))
         d = d * g
     return torch.tensor(vals, dtype=torch.float32, device=device).repeat(n_envs, 1).contiguous()
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy (float32).  All arrays share their leading (environment) dimension;
+    above DUMP_MAX_BYTES in all, the same fixed, seeded, sorted sample of environment rows is kept of every array."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    rows = None
+    if total > DUMP_MAX_BYTES:
+        n = next(iter(arrays.values())).shape[0]
+        keep = max(1, int(n * DUMP_MAX_BYTES // total))
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrays = {k: np.ascontiguousarray(v[rows]) for k, v in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), v)
+    return {"dir": out_dir, "arrays": {k: list(v.shape) for k, v in arrays.items()},
+            **({"sampled_rows": int(len(rows))} if rows is not None else {})}
 
 
 def _planner_for(name, E, I, device):
@@ -576,6 +603,11 @@ def main():
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--skip-traffic", action="store_true",
                     help="do not launch the rocprofv3 --pmc children that measure roofline.traffic (use when bench.py itself runs under a profiler)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: long region, latencies, parity, exact-fp32 companion, c3 / c4 / c5 legs, "
+                         "baselines, traffic (a plain run times the --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (action, prev_mean) as DIR/<name>.npy, float32")
     ap.add_argument("--traffic-child", default=None, metavar="CONFIG", help=argparse.SUPPRESS)
     ap.add_argument("--compile-child", default=None, metavar="CONFIG", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -670,8 +702,8 @@ def main():
     for i in range(W):
         step(1 + i, warm)
     # The headline region times EXACTLY --steps steps (the driver is the authority on its own contract: its consistency check
-    # compares `steps` with what it asked for).  Short requests -- the driver's --steps 20 is half a second -- are followed by a
-    # second region of at least MIN_TIMED_S, reported as extra.long_region (value, steps, ms_per_step): long enough for an
+    # compares `steps` with what it asked for).  With --full, short requests -- the driver's --steps 20 is half a second -- are
+    # followed by a second region of at least MIN_TIMED_S, reported as extra.long_region (value, steps, ms_per_step): long enough for an
     # outside GPU-activity sampler, and a check that the short figure is not a warm-clock artefact.
     planner.set_profiling(K * I)
     fence()
@@ -692,8 +724,11 @@ def main():
         rank_ms = {"min": round(-1e3 * float(t[1].item()) / K, 3), "max": round(1e3 * float(t[0].item()) / K, 3)}
         elapsed = float(t[0].item())
     assert faults > 0 or torch.isfinite(out).all()
+    # what the last timed step handed its caller, copied before anything below reuses `out` / `prev`
+    outputs = ({"action": out.to("cpu", copy=True).numpy(), "prev_mean": prev.to("cpu", copy=True).numpy()}
+               if args.dump_outputs and rank == 0 else None)
     long_region = None
-    if elapsed < MIN_TIMED_S and not os.environ.get("TDMPC2_BENCH_EXACT_STEPS"):
+    if args.full and elapsed < MIN_TIMED_S and not os.environ.get("TDMPC2_BENCH_EXACT_STEPS"):
         K2 = int(np.ceil(1.1 * MIN_TIMED_S / max(elapsed / K, 1e-6)))
         if use_dist:
             tn = torch.tensor([K2], dtype=torch.int64, device=device)
@@ -723,10 +758,10 @@ def main():
                                  "backend": (dist.get_backend() if use_dist else None)}}
     if long_region is not None:
         extra["long_region"] = long_region
-    if rank == 0 and world == 1 and not STUB:
+    if args.full and rank == 0 and world == 1 and not STUB:
         # per-leg clocks / socket power under the leg's own load (box_under_load)
         extra["box_under_load"] = box_under_load(lambda: [step(500 + i, warm) for i in range(15)], device, with_props=True)
-    if rank == 0 and not STUB:
+    if args.full and rank == 0 and not STUB:
         # single-environment latency (the reference's E = 1 semantics), reported beside the throughput
         one = NativePlanner(cfg, I, device, max_envs=1, path=path, precision=prec)
         one.bind_state_dict(sd)
@@ -863,7 +898,8 @@ def main():
 
     c5 = None
     # (TDMPC2_BENCH_FORCE_C5=1 under torch.distributed.run exercises the leg with one rank: the builder's pool has one GPU)
-    if (world > 1 or (use_dist and os.environ.get("TDMPC2_BENCH_FORCE_C5"))) and args.config == "c2" and not args.skip_extra_configs:
+    if (args.full and (world > 1 or (use_dist and os.environ.get("TDMPC2_BENCH_FORCE_C5"))) and args.config == "c2"
+            and not args.skip_extra_configs):
         try:
             planner.close()
             c5 = c5_leg(device, rank, world, fence)
@@ -900,7 +936,7 @@ def main():
         "scaling": "weak",
         "vs_baseline": None,
         # inputs, outputs, accumulation and all non-GEMM math are fp32; what the label must not hide is how the PRODUCTS of the
-        # nn.Linear contractions are formed (extra.exact_fp32_mode carries the strict-fp32 figure of the same run)
+        # nn.Linear contractions are formed (with --full, extra.exact_fp32_mode carries the strict-fp32 figure of the same run)
         "dtype": "f32 (f16x2-split products: 22-bit operands, fp32 accumulate)" if split else "f32",
         "data": "synthetic",
         "config": {
@@ -936,7 +972,7 @@ def main():
                                           "vs_fp32_mfma_peak": round(achieved / FP32_MFMA_PEAK_TFLOPS, 3)}} if split else {}),
         "extra": extra,
     }
-    if world == 1 and not args.skip_cpu_baseline and not STUB:
+    if args.full and world == 1 and not args.skip_cpu_baseline and not STUB:
         try:
             line["extra"]["torch_rocm_eager_same_gpu"] = torch_eager_gpu_baseline(cfg, I, sd_np, device)
         except Exception as ex:
@@ -959,7 +995,7 @@ def main():
             except Exception as ex:
                 line["extra"].setdefault("configs", {})["c1_cpu"] = {"error": repr(ex)}
     # last (a counter pass that times out cannot cost the baselines above): roofline.traffic from rocprofv3 --pmc children
-    if world == 1 and not args.skip_traffic and args.path == "auto" and args.precision == "auto" and not STUB:
+    if args.full and world == 1 and not args.skip_traffic and args.path == "auto" and args.precision == "auto" and not STUB:
         log("measuring roofline.traffic (rocprofv3 --pmc children)")
         traffic, traffic_info = measured_traffic(args.config, E, I, family == "fused", E * cfg.num_samples // 64)
         for nm, leg in extra.get("configs", {}).items():
@@ -970,6 +1006,8 @@ def main():
                 leg["roofline"]["traffic_detail"] = ti
         line["roofline"]["traffic"] = None if traffic is None else round(traffic)
         line["roofline"]["traffic_detail"] = traffic_info
+    if outputs is not None:
+        extra["dumped_outputs"] = dump_outputs(args.dump_outputs, outputs)
     print(json.dumps(line), flush=True)
     if use_dist:
         dist.barrier()

@@ -1,5 +1,7 @@
 """CPU: host-side mirror of the reference interface — config derivations, checkpoint key layout,
 discount powers, the encoder."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -7,7 +9,7 @@ import torch
 from tdmpc2_amd import checkpoint, synth
 from tdmpc2_amd.config import Config, get_discount, named_config, parse_cfg, planner_iterations
 from tdmpc2_amd.world_model import WorldModel
-from tests.helpers import load_golden
+from tests.helpers import GOLDEN_DIR, load_golden
 
 
 def test_model_size_table_and_task_dim_rules():
@@ -168,30 +170,22 @@ def test_pixel_world_model_has_reference_keys_and_shapes():
 
 
 def test_pixel_modules_match_the_reference_modules():
-    """ShiftAug / PixelPreprocess / conv against the reference's own modules on the same seed (build container only)."""
-    from oracle import ref_runner
-
-    if not ref_runner.available():
-        pytest.skip("reference tree not present")
+    """ShiftAug / PixelPreprocess / conv against the outputs of the reference's own modules on the same seeded input
+    (tests/golden/pixel_modules.npz, made by oracle/make_golden_host.py)."""
+    from oracle import make_golden_host as mg
     from tdmpc2_amd import layers
 
-    ref = ref_runner._import_reference().layers
-    x = torch.randint(0, 256, (4, 9, 64, 64)).float()
-    torch.manual_seed(11)
-    want = ref.ShiftAug()(x)
-    torch.manual_seed(11)
+    g = np.load(os.path.join(GOLDEN_DIR, mg.PIXEL_FILE))
+    x = mg.pixel_input()
+    torch.manual_seed(mg.SHIFT_SEED)
     got = layers.ShiftAug()(x)
-    assert torch.equal(got, want)
-    assert torch.equal(layers.PixelPreprocess()(x), ref.PixelPreprocess()(x))
-    torch.manual_seed(0)
-    mine = layers.conv((9, 64, 64), 32, act=layers.SimNorm(8))
-    theirs = ref.conv((9, 64, 64), 32)
-    theirs.load_state_dict(mine.state_dict())  # same module indices -> same keys
-    torch.manual_seed(5)
-    a = mine(x)
-    torch.manual_seed(5)
-    b = layers.SimNorm(8)(theirs(x))
-    assert torch.allclose(a, b, atol=1e-6)
+    assert torch.equal(got, torch.from_numpy(g["shift_aug"]))
+    assert torch.equal(layers.PixelPreprocess()(x), torch.from_numpy(g["pixel_preprocess"]))
+    mine = mg.pixel_conv(mg.conv_state(g))  # the weights the reference's conv ran with, from the fixture
+    torch.manual_seed(mg.CONV_SEED)
+    with torch.no_grad():
+        a = mine(x)
+    assert torch.allclose(a, torch.from_numpy(g["conv"]), atol=1e-6)
 
 
 def test_planner_seed_differs_across_ranks(monkeypatch):
@@ -250,25 +244,21 @@ def test_every_tuning_key_of_the_header_has_a_binding():
 @pytest.mark.parametrize("cfg_name,over", [("tiny", {}), ("tiny", dict(task="mt30")), ("c1", {})])
 def test_checkpoint_conversion_agrees_with_the_references_own(cfg_name, over):
     """`checkpoint.convert_state_dict` + the WorldModel load hook against the reference's `api_model_conversion`
-    (tdmpc2/common/layers.py:167-221), imported and run as it is (needs /root/reference: build container only).  An
+    (tdmpc2/common/layers.py:167-221), as recorded from running it as it is (tests/golden/checkpoint_conversion.json, made by
+    oracle/make_golden_host.py: where every entry of its result comes from, and the keys it returns for a new-format dict).  An
     old-API checkpoint as released (flat-numbered Q keys, no log_std_* / _action_masks) goes through both; every key the
     reference produces must exist here with the same tensor, and no Q key may be left over."""
-    from oracle import ref_runner
+    import json
 
-    if not ref_runner.available():
-        pytest.skip("the reference tree is not on this machine")
-    api_model_conversion = ref_runner._import_reference().layers.api_model_conversion
-    cfg = named_config(cfg_name, **over)
-    src = WorldModel(cfg)
-    syn = {k: torch.as_tensor(v) for k, v in synth.make_state_dict(cfg, 0).items()}
-    src.load_state_dict(dict(syn))
-    old = checkpoint.to_old_format(src.state_dict())
-    for k in ("log_std_min", "log_std_dif", "_action_masks"):
-        old.pop(k, None)
+    from oracle import make_golden_host as mg
+
+    case = next(c for c, v in mg.CONVERSION_CASES.items() if v == (cfg_name, over))
+    with open(os.path.join(GOLDEN_DIR, mg.CONVERSION_FILE)) as f:
+        rec = json.load(f)[case]
+    cfg, old, target, new = mg.conversion_inputs(case)
     assert checkpoint.is_old_format(old)
     # reference: target_state_dict = the freshly built model's state dict (tdmpc2.py:92-94)
-    fresh = WorldModel(cfg)
-    want = api_model_conversion(fresh.state_dict(), dict(old))
+    want = {k: (old if where == "source" else target)[key] for k, (where, key) in rec["origin"].items()}
     # here: strict load of the same old dict (the pre-hook converts), then read the model back
     mine = WorldModel(cfg)
     mine.load_state_dict(dict(old))
@@ -285,8 +275,7 @@ def test_checkpoint_conversion_agrees_with_the_references_own(cfg_name, over):
         if "Qs" in k and torch.is_tensor(v) and not checkpoint.is_meta_key(k):
             assert torch.equal(conv[k], v), k
     # a new-format dict passes through both unchanged (layers.py:171-173)
-    new = src.state_dict()
-    assert api_model_conversion(fresh.state_dict(), dict(new)).keys() == new.keys()
+    assert rec["new_format_keys"] == list(new.keys())
     again = WorldModel(cfg)
     again.load_state_dict(dict(new))
     assert all(torch.equal(v, again.state_dict()[k]) for k, v in new.items() if torch.is_tensor(v))

@@ -22,7 +22,7 @@ if [ "${1:-build}" = "build" ]; then
 else
   for v in "${VARIANTS[@]}"; do
     name="${v%%:*}"
-    TDMPC2_TIMING=1 TDMPC2_PLAN_LIB="$R/build/ablate/lib_${name}.so" timeout 120 python "$R/bench.py" --steps 5 --warmup 2 --skip-cpu-baseline ${ABLATE_BENCH_ARGS:-} 2> >(grep "tdmpc2_plan timing" >&2) \
+    TDMPC2_TIMING=1 TDMPC2_PLAN_LIB="$R/build/ablate/lib_${name}.so" timeout 120 python "$R/bench.py" --full --steps 5 --warmup 2 --skip-cpu-baseline ${ABLATE_BENCH_ARGS:-} 2> >(grep "tdmpc2_plan timing" >&2) \
       | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$name', 'plans/s', d['value'], 'rollout_ms', d['roofline']['avg_launch_ms'], 'lat1_ms', d['extra'].get('latency_ms_single_env'))"
   done
 fi

@@ -8,18 +8,19 @@
 cd "$(dirname "$0")/.."
 R=$PWD
 TAG="${1:-r3z}"; PARTS="${2:-tests bench stats pmc_layered pmc torchrun}"
-mkdir -p gpurun_out
+export REC="${REC:-$R/records}"  # where this run's records go (REC=<dir> to choose)
+mkdir -p "$REC"
 has() { [[ " $PARTS " == *" $1 "* ]]; }
 if has tests; then
-  (time timeout 2700 python -m pytest tests -m gpu -q --tb=short -p no:cacheprovider) > gpurun_out/${TAG}_pytest_gpu.log 2>&1
-  tail -8 gpurun_out/${TAG}_pytest_gpu.log
+  (time timeout 2700 python -m pytest tests -m gpu -q --tb=short -p no:cacheprovider) > $REC/${TAG}_pytest_gpu.log 2>&1
+  tail -8 $REC/${TAG}_pytest_gpu.log
 fi
 if has bench; then
-  timeout 900 python bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
-  tail -5 gpurun_out/${TAG}_bench.err
+  timeout 900 python bench.py --full > $REC/${TAG}_bench.json 2> $REC/${TAG}_bench.err
+  tail -5 $REC/${TAG}_bench.err
   python - <<PY
 import json
-d=json.loads(open("gpurun_out/${TAG}_bench.json").read().strip().splitlines()[-1])
+d=json.loads(open("$REC/${TAG}_bench.json").read().strip().splitlines()[-1])
 print("bench", d["value"], d["roofline"]["frac"], d["roofline"]["avg_launch_ms"], d["roofline"].get("traffic"), d["extra"].get("latency_ms_single_env"),
       {k:(v.get("value"), v.get("roofline",{}).get("frac"), v.get("roofline",{}).get("traffic")) for k,v in d["extra"].get("configs",{}).items()}, d.get("cpu_baseline",{}).get("value"))
 PY
@@ -27,42 +28,42 @@ fi
 if has stats; then
   export TMPDIR=/tmp
   cd /tmp
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_${TAG} -o ${TAG} -- python $R/bench.py --steps 5 --warmup 2 --skip-cpu-baseline --skip-traffic > $R/gpurun_out/prof_${TAG}.stdout 2> $R/gpurun_out/prof_${TAG}.stderr
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $REC/prof_${TAG} -o ${TAG} -- python $R/bench.py --full --steps 5 --warmup 2 --skip-cpu-baseline --skip-traffic > $REC/prof_${TAG}.stdout 2> $REC/prof_${TAG}.stderr
   cd $R
-  KT=$(find gpurun_out/prof_${TAG} -name "*kernel_trace.csv" | head -1)
-  python tools/rocprof_summary.py $KT > gpurun_out/${TAG}_kernel_stats_by_grid.txt
-  cp $(find gpurun_out/prof_${TAG} -name "*kernel_stats.csv" | head -1) gpurun_out/${TAG}_rocprofv3_kernel_stats.csv
-  head -14 gpurun_out/${TAG}_kernel_stats_by_grid.txt | cut -c1-160
-  rm -rf gpurun_out/prof_${TAG}
+  KT=$(find $REC/prof_${TAG} -name "*kernel_trace.csv" | head -1)
+  python tools/rocprof_summary.py $KT > $REC/${TAG}_kernel_stats_by_grid.txt
+  cp $(find $REC/prof_${TAG} -name "*kernel_stats.csv" | head -1) $REC/${TAG}_rocprofv3_kernel_stats.csv
+  head -14 $REC/${TAG}_kernel_stats_by_grid.txt | cut -c1-160
+  rm -rf $REC/prof_${TAG}
 fi
 if has pmc_layered; then  # the layered family's GEMMs at the c3 / c4 geometry of the bench legs
-  PMC_PASSES="${PMC_PASSES_LAYERED:-sq1 grbm fetch}" bash tools/gpu_pmc.sh ${TAG}_c3 --config c3 --envs 30 --steps 2 --warmup 1 --skip-cpu-baseline --skip-extra-configs --skip-traffic
-  python tools/pmc_summary.py gpurun_out/pmc_${TAG}_c3 g_gemm > gpurun_out/${TAG}_c3_pmc.txt 2>&1
-  PMC_PASSES="${PMC_PASSES_LAYERED:-sq1 grbm fetch}" bash tools/gpu_pmc.sh ${TAG}_c4 --config c4 --envs 8 --steps 1 --warmup 1 --skip-cpu-baseline --skip-extra-configs --skip-traffic
-  python tools/pmc_summary.py gpurun_out/pmc_${TAG}_c4 g_gemm > gpurun_out/${TAG}_c4_pmc.txt 2>&1
-  grep -A16 "g_gemm_w<1, 0>  workgroups=448\|g_gemm_w<1, 0>  workgroups=512" gpurun_out/${TAG}_c3_pmc.txt gpurun_out/${TAG}_c4_pmc.txt | grep -E "g_gemm_w|pipe|clock|HBM" | head -20
-  rm -rf gpurun_out/pmc_${TAG}_c3/*/ gpurun_out/pmc_${TAG}_c4/*/ 2>/dev/null
+  PMC_PASSES="${PMC_PASSES_LAYERED:-sq1 grbm fetch}" bash tools/gpu_pmc.sh ${TAG}_c3 --full --config c3 --envs 30 --steps 2 --warmup 1 --skip-cpu-baseline --skip-extra-configs --skip-traffic
+  python tools/pmc_summary.py $REC/pmc_${TAG}_c3 g_gemm > $REC/${TAG}_c3_pmc.txt 2>&1
+  PMC_PASSES="${PMC_PASSES_LAYERED:-sq1 grbm fetch}" bash tools/gpu_pmc.sh ${TAG}_c4 --full --config c4 --envs 8 --steps 1 --warmup 1 --skip-cpu-baseline --skip-extra-configs --skip-traffic
+  python tools/pmc_summary.py $REC/pmc_${TAG}_c4 g_gemm > $REC/${TAG}_c4_pmc.txt 2>&1
+  grep -A16 "g_gemm_w<1, 0>  workgroups=448\|g_gemm_w<1, 0>  workgroups=512" $REC/${TAG}_c3_pmc.txt $REC/${TAG}_c4_pmc.txt | grep -E "g_gemm_w|pipe|clock|HBM" | head -20
+  rm -rf $REC/pmc_${TAG}_c3/*/ $REC/pmc_${TAG}_c4/*/ 2>/dev/null
 fi
 if has ab; then  # environment-switch A/B of the in-tree library (interleaved twice), e.g. AB_SPEC="c3 30 8" AB_ENVS="A=0|TDMPC2_X_GEMM_XCD_ROWS=0"
   IFS='|' read -r -a ABE <<< "${AB_ENVS:-A=0}"
   bash tools/gpu_env_ab.sh ${TAG} "${AB_SPEC:-c3 30 8}" "${ABE[@]}" > /dev/null
-  cat gpurun_out/${TAG}_ab.txt
+  cat $REC/${TAG}_ab.txt
   if [ -n "${AB_SPEC2:-}" ]; then  # a second, single-repetition A/B (the slow configuration)
     AB_REPS=1 bash tools/gpu_env_ab.sh ${TAG}b "${AB_SPEC2}" "${ABE[@]}" > /dev/null
-    cat gpurun_out/${TAG}b_ab.txt
+    cat $REC/${TAG}b_ab.txt
   fi
 fi
 if has pmc; then
   bash tools/gpu_pmc.sh ${TAG}
-  python tools/pmc_summary.py gpurun_out/pmc_${TAG} ks_rollout > gpurun_out/${TAG}_pmc.txt 2>&1
-  python tools/pmc_summary.py gpurun_out/pmc_${TAG} --json gpurun_out/${TAG}_pmc.json 'ks_rollout<\d+, \d, 8, 0, 0>'
-  head -40 gpurun_out/${TAG}_pmc.txt
-  rm -rf gpurun_out/pmc_${TAG}/*/ 2>/dev/null
+  python tools/pmc_summary.py $REC/pmc_${TAG} ks_rollout > $REC/${TAG}_pmc.txt 2>&1
+  python tools/pmc_summary.py $REC/pmc_${TAG} --json $REC/${TAG}_pmc.json 'ks_rollout<\d+, \d, 8, 0, 0>'
+  head -40 $REC/${TAG}_pmc.txt
+  rm -rf $REC/pmc_${TAG}/*/ 2>/dev/null
 fi
 if has torchrun; then
-  HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 5 --warmup 2 --skip-cpu-baseline --skip-extra-configs --skip-traffic > gpurun_out/${TAG}_torchrun_n1.log 2>&1
-  tail -c 600 gpurun_out/${TAG}_torchrun_n1.log; echo
-  TDMPC2_BENCH_FORCE_C5=1 HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 1 --steps 2 --warmup 1 --skip-cpu-baseline --skip-traffic > gpurun_out/${TAG}_torchrun_c5_leg.log 2>&1
-  tail -c 400 gpurun_out/${TAG}_torchrun_c5_leg.log; echo
+  HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --full --steps 5 --warmup 2 --skip-cpu-baseline --skip-extra-configs --skip-traffic > $REC/${TAG}_torchrun_n1.log 2>&1
+  tail -c 600 $REC/${TAG}_torchrun_n1.log; echo
+  TDMPC2_BENCH_FORCE_C5=1 HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 1 --steps 2 --warmup 1 --full --skip-cpu-baseline --skip-traffic > $REC/${TAG}_torchrun_c5_leg.log 2>&1
+  tail -c 400 $REC/${TAG}_torchrun_c5_leg.log; echo
 fi
-du -sh gpurun_out | tail -1
+du -sh "$REC" | tail -1

@@ -5,11 +5,12 @@
 set -u
 TAG="${1:-r01}"; shift || true
 R="${GRAFT_REPO_ROOT:-$PWD}"
-OUT="$R/gpurun_out/pmc_${TAG}"
+export REC="${REC:-$R/records}"  # where this run's records go (REC=<dir> to choose)
+OUT="$REC/pmc_${TAG}"
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-ARGS="${*:---steps 2 --warmup 1 --skip-cpu-baseline --skip-extra-configs}"
+ARGS="${*:---full --steps 2 --warmup 1 --skip-cpu-baseline --skip-extra-configs}"
 pass() {
   local name="$1"; shift
   timeout 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$OUT/$name" -o "$name" -- \

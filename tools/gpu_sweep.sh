@@ -2,15 +2,16 @@
 # SURVEY.md section 8(d)'s list of configurations, one bench.py line each (run on the GPU box through gpurun):
 #   c1 at E = 1, 16, 64, 512 | c2 at I = 6 (metric text) and I = 8 (reference behaviour, A >= 20) | c3: 30 concurrent plans |
 #   c4 at the reference dims (L = 1376) and at BASELINE.json's L = 1024 | c5's per-GPU share: c4 with 64 environments
-# usage: tools/gpu_sweep.sh <tag>   ->  gpurun_out/sweep_<tag>.jsonl
+# usage: tools/gpu_sweep.sh <tag>   ->  $REC/sweep_<tag>.jsonl
 set -u
 TAG="${1:-r01}"
 R="${GRAFT_REPO_ROOT:-$PWD}"
-OUT="$R/gpurun_out/sweep_${TAG}.jsonl"
-mkdir -p "$R/gpurun_out"; : > "$OUT"
+export REC="${REC:-$R/records}"  # where this run's records go (REC=<dir> to choose)
+OUT="$REC/sweep_${TAG}.jsonl"
+mkdir -p "$REC"; : > "$OUT"
 run() {
   echo "== bench.py $*" >&2
-  timeout 600 python "$R/bench.py" --skip-cpu-baseline --skip-traffic --skip-extra-configs "$@" 2>/dev/null | tail -1 >> "$OUT" || echo "{\"error\": \"$*\"}" >> "$OUT"
+  timeout 600 python "$R/bench.py" --full --skip-cpu-baseline --skip-traffic --skip-extra-configs "$@" 2>/dev/null | tail -1 >> "$OUT" || echo "{\"error\": \"$*\"}" >> "$OUT"
 }
 run --config c1 --envs 1 --steps 20 --warmup 3
 run --config c1 --envs 16 --steps 20 --warmup 3

@@ -4,15 +4,16 @@
 # usage: gpurun -- bash tools/gpu_tree_ab.sh <tag> "<name>=<dir> <name>=<dir> ..." "<config envs steps>;..." [reps]
 cd "$(dirname "$0")/.."
 R=$PWD; TAG=$1; TREES=$2; SPECS=$3; REPS=${4:-2}
-mkdir -p gpurun_out
-out=$R/gpurun_out/${TAG}_tree_ab.txt; : > $out
+export REC="${REC:-$R/records}"  # where this run's records go (REC=<dir> to choose)
+mkdir -p "$REC"
+out=$REC/${TAG}_tree_ab.txt; : > $out
 IFS=';' read -r -a SP <<< "$SPECS"
 for rep in $(seq 1 $REPS); do
   for spec in "${SP[@]}"; do
     set -- $spec
     for t in $TREES; do
       name=${t%%=*}; dir=${t#*=}
-      (cd $R/$dir && TDMPC2_BENCH_EXACT_STEPS=1 timeout 400 python bench.py --config $1 --envs $2 --steps $3 --warmup 3 --skip-cpu-baseline --skip-extra-configs --skip-traffic 2>/dev/null \
+      (cd $R/$dir && TDMPC2_BENCH_EXACT_STEPS=1 timeout 400 python bench.py $(grep -q '"--full"' bench.py && echo --full) --config $1 --envs $2 --steps $3 --warmup 3 --skip-cpu-baseline --skip-extra-configs --skip-traffic 2>/dev/null \
         | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); b=d['extra'].get('box_under_load',{})
