@@ -367,7 +367,7 @@ int tdmpc2_plan_shard_refit(tdmpc2_plan_t *h, int n_envs, int iter, float *value
 enum tdmpc2_tuning { TDMPC2_TUNE_ROWS_PER_WORKGROUP = 0, TDMPC2_TUNE_FOLD_REFIT = 1, TDMPC2_TUNE_CLUSTER = 2, TDMPC2_TUNE_FUSE_LN = 3,
                      TDMPC2_TUNE_REARM_AFTER = 4, TDMPC2_TUNE_SAFE_ONCE = 5, TDMPC2_TUNE_KSPLIT = 6, TDMPC2_TUNE_FEWROW = 7,
                      TDMPC2_TUNE_WAIT_US = 8, TDMPC2_TUNE_EXPERT = 100 };
-/* (what each knob decides: tdmpc2_amd/csrc/layered_host.cuh; defaults in tdmpc2_amd/csrc/handle.h) */
+/* (what each knob decides, its default and the values it accepts -- anything else: TDMPC2_ERR_INVALID: tdmpc2_amd/csrc/layer_route.h) */
 enum tdmpc2_expert_knob { TDMPC2_X_GEMM_W256_MIN = 0, TDMPC2_X_GEMM_W_SPLIT_MIN, TDMPC2_X_GEMM_W_SPLIT_MAX, TDMPC2_X_GEMM_W_SPLIT_OVH,
                           TDMPC2_X_KSPLIT_AUTO_LO, TDMPC2_X_KSPLIT_AUTO_MIN, TDMPC2_X_GEMM_W_XCD_ROWS, TDMPC2_X_GEMM_NCT1,
                           TDMPC2_X_GEMM_WIDE_MIN, TDMPC2_X_GEMM_RT4, TDMPC2_X_GEMM_FILL_PERMILLE, TDMPC2_X_GEMM_FILL_HEAD_PERMILLE,

@@ -13,6 +13,7 @@
 #include <cstring>
 
 #include "../../include/tdmpc2_plan.h"
+#include "layer_route.h"  // GBM and the other tile constants the layered family's routes share with its kernels
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -28,8 +29,7 @@ constexpr int MAXQ = 8;
 constexpr int MAXH = 8;
 constexpr float LN_EPS = 1e-5f;
 
-// layered family (layered_kernels.cuh / layered_split.cuh): GEMM tile constants the host sizes buffers with
-constexpr int GBM = 128;          // rows per GEMM workgroup (the narrow tiles; the wide tile takes 256)
+// layered family (layered_kernels.cuh / layered_split.cuh): GEMM tile constants the host sizes buffers with (GBM: layer_route.h)
 constexpr int GBN = 128;          // output columns per GEMM workgroup (4 column tiles of 32)
 constexpr int GBK = 32;           // k-chunk staged through LDS
 constexpr int GLD = GBK + 4;      // LDS row stride in floats (stride/4 = 9, odd -> conflict-free ds_read_b128)

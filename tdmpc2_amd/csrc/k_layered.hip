@@ -5,7 +5,6 @@
 
 namespace {
 #include "fused_kernels.cuh"  // device helpers shared with the fused family: ldw, SPLIT_MFMA, mish_fast, split4
-#include "tile_order.h"
 #include "layered_kernels.cuh"
 #include "layered_split.cuh"
 #include "layered_wide.cuh"

@@ -1,5 +1,7 @@
-// Host orchestration of the layer-at-a-time planner path (kernels: layered_kernels.cuh, layered_split.cuh).
-// Included by k_layered.hip inside namespace tdk (the functions declared in launch.h are the family's interface).
+// Host orchestration of the layer-at-a-time planner path (kernels: layered_kernels.cuh, layered_split.cuh, layered_wide.cuh,
+// layered_mid.cuh).  Which kernel, tile, order and epilogue each split-arithmetic GEMM launch takes is decided in layer_route.h
+// (lay_route, mid_route, mid_ok); the functions here fill the kernels' parameters around that route, keep the arrival counters
+// it reports, and launch.  Included by k_layered.hip inside namespace tdk (the functions declared in launch.h are the family's interface).
 #pragma once
 
 
@@ -43,20 +45,6 @@ int lay_arrive_reset(tdmpc2_plan *h, hipStream_t st) {
     return 0;
 }
 
-#define GEMM_S_LAUNCH_PF(NCTV, RTV, SDV, PFV)                                                                  \
-    do {                                                                                                      \
-        if (epi == 0) hipLaunchKernelGGL((g_gemm_s<NCTV, RTV, SDV, 0, PFV>), dim3(nblk), dim3(GTHREADS), 0, st, q); \
-        else if (epi == 1) hipLaunchKernelGGL((g_gemm_s<NCTV, RTV, SDV, 1, PFV>), dim3(nblk), dim3(GTHREADS), 0, st, q); \
-        else hipLaunchKernelGGL((g_gemm_s<NCTV, RTV, SDV, 2, PFV>), dim3(nblk), dim3(GTHREADS), 0, st, q);     \
-    } while (0)
-#define GEMM_S_LAUNCH(NCTV, RTV, SDV) GEMM_S_LAUNCH_PF(NCTV, RTV, SDV, 0)
-// the narrow tiles that can run the two-hot epilogue (epi == 3)
-#define GEMM_S_LAUNCH_TH(RTV, SDV)                                                                              \
-    do {                                                                                                      \
-        if (epi == 3) hipLaunchKernelGGL((g_gemm_s<1, RTV, SDV, 3, 0>), dim3(nblk), dim3(GTHREADS), 0, st, q);  \
-        else GEMM_S_LAUNCH(1, RTV, SDV);                                                                      \
-    } while (0)
-
 // A k-range of a layer with a per-environment bias of the caller's: the action columns of a first layer at t = 0, where the
 // z columns' product is one vector per plan (lay_cvec).
 struct GemmRange {
@@ -69,11 +57,84 @@ struct GemmRange {
 int lay_ln(tdmpc2_plan *h, hipStream_t st, int act, float *x, int ld, int width, size_t rows, int rows_per_env,
            const HostLayer &ly, long gb_sel_stride, const int *sel, float *out_packed = nullptr, int ld_out = 0);
 
+// What the handle offers a launch on the chain whose statistics exchange / K-split workspace are `stats` / `ksws` (layer_route.h)
+inline LayCtx lay_ctx(const tdmpc2_plan *h, const float *stats, const float *ksws) {
+    const Layered &L = h->lay;
+    return LayCtx{h->num_cus > 0 ? h->num_cus : 256, L.ksplit, L.fuse_ln, L.row_env != nullptr, L.arrive != nullptr, L.arrive_off, L.arrive_cap,
+                  stats != nullptr, L.stats_cap, ksws != nullptr, L.ksws_slots, L.knob.v};
+}
+
+// The bias of a layer's rows (g_gemm_s / g_gemm / m_rows): the net's slot of the effective first-layer biases (multitask first
+// layers), else the layer's own -- in both cases overridden by a k-range's per-environment bias (t = 0: lay_cvec)
+template <class P>
+inline void lay_bias(P &p, const tdmpc2_plan *h, const HostLayer &ly, int slot, bool sel, long bias_sel_stride, const GemmRange *range) {
+    const Layered &L = h->lay;
+    if (slot >= 0 && h->cfg.multitask) {
+        p.bias = L.bias_tab + (size_t)slot * L.Mp;
+        p.bias_env_stride = (long)h->nnets * L.Mp;
+        p.bias_sel_stride = sel ? L.Mp : 0;
+    } else {
+        p.bias = ly.bias;
+        p.bias_env_stride = 0;
+        p.bias_sel_stride = sel ? bias_sel_stride : 0;
+    }
+    if (range && range->bias_env) {
+        p.bias = range->bias_env; p.bias_env_stride = range->bias_env_stride; p.bias_sel_stride = 0;
+    }
+}
+
+// The NormedLinear epilogue inside a GEMM (g_gemm_s, g_gemm_w, g_gemm_m): LayerNorm parameters, the statistics exchange, `n_arrive`
+// of the stage's arrival counters, the packed output operand of `ldo` columns
+template <class P>
+inline void lay_ln_epi(P &p, tdmpc2_plan *h, const HostLayer &ly, long gb_sel_stride, bool sel, int width, float *stats, size_t n_arrive,
+                       float *out, int ldo) {
+    Layered &L = h->lay;
+    p.ln_g = ly.g; p.ln_b = ly.b; p.gb_sel_stride = gb_sel_stride;
+    p.ascale = ly.ascale; p.asc_sel_stride = sel ? (long)(3 * sizeof(LayerScal) / sizeof(float)) : 0;
+    p.width = width; p.stats = stats; p.arrive = L.arrive + L.arrive_off; p.err = h->cl_err_dev; p.fault = h->cl_fault;
+    L.arrive_off += n_arrive;
+    p.out = out; p.KBo = ldo / 16;
+}
+
+// g_gemm_s<NCT, RT, SD, epi, 0>; the two-hot epilogue (epi 3) exists for the narrow tiles of 32 / 64 rows only
+template <int NCT, int RT, int SD>
+inline int gemm_s_launch(int epi, unsigned grid, hipStream_t st, const GemmSParams &q) {
+    constexpr bool twohot = NCT == 1 && RT <= 2;
+    if (epi == 0) hipLaunchKernelGGL((g_gemm_s<NCT, RT, SD, 0, 0>), dim3(grid), dim3(GTHREADS), 0, st, q);
+    else if (epi == 1) hipLaunchKernelGGL((g_gemm_s<NCT, RT, SD, 1, 0>), dim3(grid), dim3(GTHREADS), 0, st, q);
+    else if (epi == 2) hipLaunchKernelGGL((g_gemm_s<NCT, RT, SD, 2, 0>), dim3(grid), dim3(GTHREADS), 0, st, q);
+    else if (epi == 3 && twohot) {
+        if constexpr (twohot) hipLaunchKernelGGL((g_gemm_s<1, RT, SD, 3, 0>), dim3(grid), dim3(GTHREADS), 0, st, q);
+    } else return fail(TDMPC2_ERR_STATE, "no instance g_gemm_s<%d, %d, %d, %d, 0> (layer_route.h returned a route the library does not build)",
+                       NCT, RT, SD, epi);
+    return 0;
+}
+
+// The kernel instance a route names (every instance lay_route can return, and no other)
+inline int lay_gemm_launch(const LayRoute &r, hipStream_t st, const GemmSParams &q) {
+    if (r.w) {
+        if (r.wo.parts > 1) {
+            if (r.epi == 1) hipLaunchKernelGGL((g_gemm_w<1, 1>), dim3(r.grid), dim3(512), 0, st, q);
+            else hipLaunchKernelGGL((g_gemm_w<2, 1>), dim3(r.grid), dim3(512), 0, st, q);
+        } else if (r.epi == 1) hipLaunchKernelGGL((g_gemm_w<1>), dim3(r.grid), dim3(512), 0, st, q);
+        else hipLaunchKernelGGL((g_gemm_w<2>), dim3(r.grid), dim3(512), 0, st, q);
+        return 0;
+    }
+    if (r.nct == 2) return gemm_s_launch<2, 4, 2>(r.epi, r.grid, st, q);
+    if (r.sd == 4 && r.rt == 4) return gemm_s_launch<1, 4, 4>(r.epi, r.grid, st, q);
+    if (r.sd == 4 && r.rt == 2) return gemm_s_launch<1, 2, 4>(r.epi, r.grid, st, q);
+    if (r.sd == 4) return gemm_s_launch<1, 1, 4>(r.epi, r.grid, st, q);
+    if (r.rt == 4) return gemm_s_launch<1, 4, 1>(r.epi, r.grid, st, q);
+    if (r.rt == 2) return gemm_s_launch<1, 2, 1>(r.epi, r.grid, st, q);
+    return gemm_s_launch<1, 1, 1>(r.epi, r.grid, st, q);
+}
+
 // One nn.Linear over `rows_p` (padded) rows.  `slot` = index of the net in beff (multitask first layers), -1 otherwise.
 // A / out: split arithmetic -- fragment-packed operand buffers of lda / ldo columns (out: only with `ln`; head logits and
 // pre-activations are fp32 [rows, ldo]); exact fp32 -- fp32 [rows, ld].
 // `ln` != null: the whole NormedLinear (layers.py:94-118) -- out <- ACT(LayerNorm(A W^T + b)) -- inside the GEMM's epilogue when the
-// handle's fused path is on and fits, else by the LayerNorm row kernel behind the GEMM (split: through bufs->PRE).
+// handle's fused path is on and fits, else by the LayerNorm row kernel behind the GEMM (split: through bufs->PRE).  Split arithmetic:
+// lay_route (layer_route.h) picks the kernel, tile, order and epilogue; this fills the parameters around it and launches.
 int lay_gemm(tdmpc2_plan *h, hipStream_t st, const float *A, int lda, size_t rows_p, int rows_per_env,
              const HostLayer &ly, long w_sel_stride, long bias_sel_stride, int slot, const int *sel, float *out, int ldo,
              const LnFuse *ln = nullptr, const LayBufs *bufs = nullptr, const GemmRange *range = nullptr, size_t rows = 0,
@@ -91,150 +152,30 @@ int lay_gemm(tdmpc2_plan *h, hipStream_t st, const float *A, int lda, size_t row
         q.w_sel_stride = sel ? w_sel_stride : 0; q.oscale = ly.oscale;
         q.osc_sel_stride = sel ? (long)(3 * sizeof(LayerScal) / sizeof(float)) : 0;  // the net's [heads][3] scalar table
         q.row_env = L.row_env;
-        if (slot >= 0 && h->cfg.multitask) {
-            q.bias = L.bias_tab + (size_t)slot * L.Mp;
-            q.bias_env_stride = (long)h->nnets * L.Mp;
-            q.bias_sel_stride = sel ? L.Mp : 0;
-        } else {
-            q.bias = ly.bias;
-            q.bias_env_stride = 0;
-            q.bias_sel_stride = sel ? bias_sel_stride : 0;
-        }
-        if (range && range->bias_env) {
-            q.bias = range->bias_env; q.bias_env_stride = range->bias_env_stride; q.bias_sel_stride = 0;
-        }
+        lay_bias(q, h, ly, slot, sel != nullptr, bias_sel_stride, range);
         q.sel = sel; q.sel_stride = 2; q.rows_per_env = rows_per_env; q.CT = ly.CT;
-        const long cus = h->num_cus > 0 ? h->num_cus : 256;
-        // Can the NormedLinear epilogue run inside the GEMM?  (always decided the same way whatever the tile: the statistics'
-        // combination order is tile-independent, so a plan's bits do not depend on the size of the call it is part of)
-        const bool can_fuse = ln && L.fuse_ln && L.arrive && bufs->stats && rows_p * ((ly.CT + 3) / 4) * 2 <= L.stats_cap;
-        // ---- the 256 x 256 tile (g_gemm_w): fused NormedLinear layers of calls that fill the chip with one workgroup per CU
-        const long w256_min = L.knob[LK_W256_MIN];
-        // (Measured and rejected, profiles/README.md r4f: 256 x 224 / 192 tiles -- 8 x 1 wave layout, one W fragment set -- for widths
-        // like the 48M model's 1792 = 8 x 224, which would fill 1.875 rounds of the chip instead of 1.64: the layout reads every W
-        // fragment eight times from LDS (128 KiB per slab) and lost 4.5 % in spite of the better fill.)
-        constexpr int NT = 8;
-        const int ncb256 = (ly.CT + NT - 1) / NT;
-        const size_t stats_need = rows_p * ((ly.CT + 3) / 4) * 2;
-        // K-split tail (tile_order.h: gemm_w_order): tiles of the launch's last, partly filled round are computed by `parts`
-        // workgroups each.  That makes the wide tile worth taking from fewer tiles on (a 180-tile SimNorm layer: 720 workgroups)
-        const int nrowblk_w = (int)(rows_p / 256);
-        const long cus_x = cus >= 8 ? cus / 8 : 1;
-        const long ks_min = L.knob[LK_W_SPLIT_MIN];
-        const int ks_maxp = L.knob[LK_W_SPLIT_MAX];
-        const int ks_ovh = L.knob[LK_W_SPLIT_OVH];
-        GemmWOrder wo{};
-        wo.parts = 1;
-        const bool w_shape = can_fuse && ly.CT >= 8 && rows_p % 256 == 0 && rows_per_env % 256 == 0 && ncb256 <= 32 && !L.row_env &&
-                             stats_need <= L.stats_cap && w256_min >= 0;
-        // L.ksplit (TDMPC2_TUNE_KSPLIT): 0 never; 1 whenever the round arithmetic says so; 2 (default) only for launches that leave
-        // most of the chip idle -- 16 .. 128 tiles, i.e. one or two plans of the 317M model (64 tiles -> 256 workgroups of a quarter
-        // of K: single-plan latency 17.85 -> 16.2 ms, +9.7 % plans/s at E = 1; the 48M model at E = 4: +6 %; profiles/r5j_*).  On launches that fill the chip the partial sums' traffic (256 KiB per part
-        // through the fabric, +210 MB per hidden GEMM of the 48M model at E = 30) costs more than the better fill buys: c3 -10 ... -13 %,
-        // c4 -2.7 % (profiles/README.md r5d).
-        const long tiles_w = (long)nrowblk_w * ncb256;
-        const long ks_auto_lo = L.knob[LK_KSPLIT_AUTO_LO];
-        const long ks_auto_min = L.knob[LK_KSPLIT_AUTO_MIN] >= 0 ? L.knob[LK_KSPLIT_AUTO_MIN] : cus / 4;
-        const bool ks_want = L.ksplit == 1 || (L.ksplit == 2 && tiles_w >= ks_auto_lo && tiles_w <= cus / 2);
-        if (w_shape && ks_want && bufs->ksws && ks_maxp > 1) {
-            const int nk = q.K / 16;
-            wo = gemm_w_order(nrowblk_w, ncb256, (int)cus_x, nk, ks_maxp, ks_ovh / (nk + 25));
-            if (wo.parts > 1 && ((size_t)8 * wo.max_tail * wo.parts > L.ksws_slots || (long)wo.nblk < (L.ksplit == 2 ? ks_auto_min : ks_min))) wo.parts = 1;
-        }
-        const size_t n_arrive = (size_t)nrowblk_w + (wo.parts > 1 ? (size_t)8 * wo.max_tail : 0);
-        if (w_shape && ((long)nrowblk_w * ncb256 >= w256_min || wo.parts > 1) &&
-            L.arrive_off + n_arrive <= L.arrive_cap /* out of arrival counters: the narrow tiles below degrade to the unfused LayerNorm */) {
-            const int nrowblk = nrowblk_w;
-            q.ncolblk = ncb256;
-            q.ln_g = ly.g; q.ln_b = ly.b; q.gb_sel_stride = sel ? ln->gb_sel_stride : 0;
-            q.ascale = ly.ascale; q.asc_sel_stride = sel ? (long)(3 * sizeof(LayerScal) / sizeof(float)) : 0;
-            q.width = ln->width; q.stats = bufs->stats; q.arrive = L.arrive + L.arrive_off; q.err = h->cl_err_dev; q.fault = h->cl_fault;
-            L.arrive_off += n_arrive;
-            q.out = out; q.KBo = ldo / 16;
-            q.ks_parts = wo.parts; q.ks_full = wo.full; q.ks_max_tail = wo.max_tail; q.ks_ws = bufs->ksws; q.ks_cnt = q.arrive + nrowblk;
-            // tile order: XCD-local row blocks keep the column blocks of a row block -- which wait for each other -- on consecutive
-            // slots of ONE XCD (with one workgroup per CU and <= 16 column blocks two launches in flight cannot starve each other:
-            // 2 x 15 waiting workgroups < 32 CUs), and read every A row through one L2
-            const int xr_env = L.knob[LK_W_XCD_ROWS];
-            // TDMPC2_GEMM_W_XCD_ROWS=2: XCD rectangles, a row block on 2 XCDs -- per XCD and launch A/4 + W/2 instead of A/8 + W
-            // through the L2.  At 16 column blocks (317M model): c4 +1 %, fabric-side reads of the launch 881 -> 654 MB, of a stage
-            // 27.3 -> 20.6 GB (profiles/README.md r4s, r4t) -- but NOT the default: with a row block on two XCDs two launches in
-            // flight can wait for each other in a circle (A's XCD full of launch 1 waiting for B's, B's full of launch 2 waiting
-            // for A's); the stress test lost 3 waits in 6 300 stages that way, the XCD-local order none (r4za).
-            const int xr_auto = nrowblk >= 16 ? 1 : 0;
-            const GemmSOrder ord = gemm_s_order(nrowblk, q.ncolblk, xr_env >= 0 ? xr_env : xr_auto, 1);
-            q.xcd_rows = ord.xcd_rows; q.ncol_grid = ord.ncol_grid; q.nrowblk = nrowblk;
-            q.timing = L.gw_timing ? L.gw_timing + (q.K >= 1024 ? 8 : 0) + (ln->act ? 16 : 0) : nullptr;  // [Mish K < 1024 | Mish K >= 1024 | SimNorm ...]
-            const int epi = 1 + ln->act;
-#define GEMM_W_LAUNCH(K) hipLaunchKernelGGL(K, dim3(wo.parts > 1 ? wo.nblk : ord.nblk), dim3(512), 0, st, q)
-            if (wo.parts > 1) {
-                if (epi == 1) GEMM_W_LAUNCH((g_gemm_w<1, 1>));
-                else GEMM_W_LAUNCH((g_gemm_w<2, 1>));
-            } else if (epi == 1) GEMM_W_LAUNCH((g_gemm_w<1>));
-            else GEMM_W_LAUNCH((g_gemm_w<2>));
-#undef GEMM_W_LAUNCH
-            LAUNCH_CHECK();
-            return 0;
-        }
-        // wide outputs (>= 256 columns) take the 128 x 256 tile from 128 such workgroups on: with a second chain in flight
-        // (lay_estimate_value) a partly filled round is not idle (A/B r3n: threshold 512 -> 256: c3 +2.0 %, c4 +2.3 %; 128: single
-        // plans of the 317M model 20.8 -> 18.7 ms; below that single plans of the 48M model lose)
-        const size_t wide_min = L.knob[LK_NCT1] ? (size_t)1 << 30 : (size_t)L.knob[LK_WIDE_MIN];
-        const bool wide = ly.CT >= 8 && (rows_p / GBM) * ((ly.CT + 7) / 8) >= wide_min;
-        q.ncolblk = wide ? (ly.CT + 7) / 8 : (ly.CT + 3) / 4;
-        // rows per workgroup tile: 128 when that fills the chip (two workgroups per CU), else 64 or 32 -- few rows mean
-        // single-plan latency, where occupancy beats operand reuse (TDMPC2_GEMM_RT=4 forces the 128-row tile)
-        const long slots = 2L * cus;
-        int rt = 4;
-        if (!wide && !L.knob[LK_RT4]) {
-            const double fill = L.knob[LK_FILL_PERMILLE] / 1000.0;
-            const double fill_head = L.knob[LK_FILL_HEAD_PERMILLE] / 1000.0;
-            const double f = ly.CT <= 4 ? fill_head : fill;  // narrow outputs (two-hot / policy heads): one column block
-            while (rt > 1 && (double)((long)(rows_p / (32 * rt)) * q.ncolblk) < (double)slots * f) rt >>= 1;
-        }
-        const int nrowblk = (int)(rows_p / (32 * rt));
-        int nblk = nrowblk * q.ncolblk;
-        // few workgroups per CU: row operand staged four chunks deep, weight ring of 8 / 16 blocks (g_gemm_s<.., .., 4>)
-        const bool deep = !wide && (long)nblk < 2 * slots && !L.knob[LK_SD1];
-        int epi = 0;
-        const bool fuse = can_fuse && L.arrive_off + (size_t)nrowblk <= L.arrive_cap;
-        if (fuse) {
-            epi = 1 + ln->act;
-            q.ln_g = ly.g; q.ln_b = ly.b; q.gb_sel_stride = sel ? ln->gb_sel_stride : 0;
-            q.ascale = ly.ascale; q.asc_sel_stride = sel ? (long)(3 * sizeof(LayerScal) / sizeof(float)) : 0;
-            q.width = ln->width; q.stats = bufs->stats; q.arrive = L.arrive + L.arrive_off; q.err = h->cl_err_dev; q.fault = h->cl_fault;
-            L.arrive_off += (size_t)nrowblk;
-            q.out = out; q.KBo = ldo / 16;
-            // tile order (tile_order.h); TDMPC2_GEMM_XCD_ROWS = 0 / 1: never / always XCD-local row blocks, TDMPC2_GEMM_COL_PAD = 0:
-            // no padding of the row-major order
-            const int xcd_rows_env = L.knob[LK_XCD_ROWS];
-            const int col_pad_env = L.knob[LK_COL_PAD];
-            const GemmSOrder ord = gemm_s_order(nrowblk, q.ncolblk, xcd_rows_env, col_pad_env);
-            q.xcd_rows = ord.xcd_rows; q.ncol_grid = ord.ncol_grid; q.nrowblk = nrowblk;
-            nblk = ord.nblk;
-        } else if (ln) {  // pre-activations -> PRE, the LayerNorm kernel writes the packed operand
+        const LayRoute r = lay_route(LayIn{rows_p, rows_per_env, ly.CT, q.K / 16, ln ? 1 + ln->act : th ? LR_TWOHOT : LR_PLAIN},
+                                     lay_ctx(h, bufs->stats, bufs->ksws));
+        q.ncolblk = r.ncolblk;
+        if (r.epi == LR_MISH || r.epi == LR_SIMNORM) {  // the NormedLinear inside the GEMM (the column blocks of a row block wait)
+            lay_ln_epi(q, h, ly, sel ? ln->gb_sel_stride : 0, sel != nullptr, ln->width, bufs->stats, r.arrive, out, ldo);
+            q.xcd_rows = r.ord.xcd_rows; q.ncol_grid = r.ord.ncol_grid; q.nrowblk = r.nrowblk;
+            if (r.w) {
+                q.ks_parts = r.wo.parts; q.ks_full = r.wo.full; q.ks_max_tail = r.wo.max_tail; q.ks_ws = bufs->ksws; q.ks_cnt = q.arrive + r.nrowblk;
+                q.timing = L.gw_timing ? L.gw_timing + (q.K >= 1024 ? 8 : 0) + (ln->act ? 16 : 0) : nullptr;  // [Mish K < 1024 | Mish K >= 1024 | SimNorm ...]
+            }
+        } else if (r.ln_after) {  // pre-activations -> PRE, the LayerNorm kernel writes the packed operand
             if (!bufs->PRE) return fail(TDMPC2_ERR_STATE, "no pre-activation buffer on this handle");
             q.out = bufs->PRE; q.ldo = L.ldpre;
-        } else if (th && !wide && rt <= 2 && ly.CT <= 4 && (long)nblk >= cus && !L.knob[LK_TWOHOT_UNFUSED]) {
-            // two-hot head: the row routine in the epilogue -- from one workgroup per CU on (c3 E = 30: +1.4 %; a single plan's 16-32
-            // workgroups are better served by l_twohot's one wavefront per row across the chip: 3.33 vs 3.44 ms, profiles r4i)
-            epi = 3;
+        } else if (r.epi == LR_TWOHOT) {
             q.th = *th;
             if (th_done) *th_done = true;
         } else {
             q.out = out; q.ldo = ldo;
         }
-        // The throughput tile stages its row operand TWO chunks ahead (g_gemm_s<2, 4, 2, ..>: same sums; c3 +0.4 ... 0.7 %,
-        // c4 +0.5 % over one chunk ahead in three same-call A/Bs, profiles/README.md r3z / r3y / r3x).
-        if (wide) GEMM_S_LAUNCH(2, 4, 2);
-        else if (deep && rt == 4) GEMM_S_LAUNCH(1, 4, 4);
-        else if (deep && rt == 2) GEMM_S_LAUNCH_TH(2, 4);
-        else if (deep) GEMM_S_LAUNCH_TH(1, 4);
-        else if (rt == 4) GEMM_S_LAUNCH(1, 4, 1);
-        else if (rt == 2) GEMM_S_LAUNCH_TH(2, 1);
-        else GEMM_S_LAUNCH_TH(1, 1);
+        if (int rc = lay_gemm_launch(r, st, q)) return rc;
         LAUNCH_CHECK();
-        if (ln && !fuse)
+        if (r.ln_after)
             return lay_ln(h, st, ln->act, bufs->PRE, L.ldpre, ln->width, rows ? rows : rows_p, rows_per_env, ly, ln->gb_sel_stride, sel, out, ldo);
         return 0;
     }
@@ -242,15 +183,7 @@ int lay_gemm(tdmpc2_plan *h, hipStream_t st, const float *A, int lda, size_t row
     p.A = A; p.lda = lda; p.K = ly.KB * 8; p.wp = ly.wp; p.w_sel_stride = sel ? w_sel_stride : 0;
     p.CT = ly.CT; p.ncolblk = (ly.CT + 3) / 4;
     p.row_env = h->lay.row_env;
-    if (slot >= 0 && h->cfg.multitask) {
-        p.bias = h->lay.bias_tab + (size_t)slot * h->lay.Mp;
-        p.bias_env_stride = (long)h->nnets * h->lay.Mp;
-        p.bias_sel_stride = sel ? h->lay.Mp : 0;
-    } else {
-        p.bias = ly.bias;
-        p.bias_env_stride = 0;
-        p.bias_sel_stride = sel ? bias_sel_stride : 0;
-    }
+    lay_bias(p, h, ly, slot, sel != nullptr, bias_sel_stride, nullptr);
     p.sel = sel; p.sel_stride = 2; p.rows_per_env = rows_per_env; p.out = out; p.ldo = ldo;
     const int nblocks = (int)(rows_p / GBM) * p.ncolblk;
     hipLaunchKernelGGL(g_gemm, dim3(nblocks), dim3(GTHREADS), 0, st, p);
@@ -454,62 +387,58 @@ struct MidOp {
     PiHeadParams pi;
 };
 
-inline bool mid_ok(const tdmpc2_plan *h, size_t rows_p) {
+// What the few-row path needs of the handle to take a call (layer_route.h: mid_ok)
+inline MidCtx mid_ctx(const tdmpc2_plan *h) {
     const Layered &L = h->lay;
-    if (!h->split || !L.mid || L.ksplit == 0 || !L.mws[0] || !L.HA2 || L.row_env) return false;
-    const long cus = h->num_cus > 0 ? h->num_cus : 256;
-    const long maxct = (std::max(h->cfg.mlp_dim, h->cfg.latent_dim) + 31) / 32;
-    return 2 * (long)(rows_p / GM_TM) * ((maxct + 7) / 8) <= cus;  // a launch's two widest problems fill at most one round of the chip
+    return MidCtx{h->split, L.mid, L.ksplit, L.mws[0] != nullptr, L.HA2 != nullptr, L.row_env != nullptr, h->num_cus > 0 ? h->num_cus : 256,
+                  (std::max(h->cfg.mlp_dim, h->cfg.latent_dim) + 31) / 32};
 }
 
-// one launch of g_gemm_m + one of m_rows for n (1 or 2) layers over the same `rows` sample rows
+// one launch of g_gemm_m + one of m_rows for n (1 or 2) layers over the same `rows` sample rows; mid_route (layer_route.h) sizes both
+// launches and picks the problems whose NormedLinear epilogue runs inside g_gemm_m; this fills the parameters and launches
 int mid_stage(tdmpc2_plan *h, hipStream_t st, size_t rows, size_t rows_p, int rpe, const MidOp *ops, int n, bool rows_one_by_one = false) {
     Layered &L = h->lay;
-    const long cus = h->num_cus > 0 ? h->num_cus : 256;
+    float *stats[2] = {L.stats, L.stats2};
+    MidIn in{rows, rows_p, rpe, n, {}, rows_one_by_one, L.arrive_pending, L.mws_cap};
+    for (int i = 0; i < n; ++i) {
+        const MidOp &o = ops[i];
+        in.pr[i] = MidProbIn{o.ly->CT, o.range ? o.range->kblocks : o.ly->KB, o.kind == MR_LN_MISH || o.kind == MR_LN_SIMNORM,
+                             o.actions != nullptr, stats[i] != nullptr};
+    }
+    const MidRoute m = mid_route(in, lay_ctx(h, L.stats, L.ksws));
+    if (!m.ws_ok) return fail(TDMPC2_ERR_STATE, "few-row path: partial-sum workspace too small");
     GemmMParams G{};
     MRowParams R{};
-    G.nprob = R.nprob = n;
-    long tiles = 0;
-    for (int i = 0; i < n; ++i) tiles += (long)(rows_p / GM_TM) * ((ops[i].ly->CT + 7) / 8);
-    const int pmax = L.knob[LK_MID_PARTS_MAX];
-    const int pall = (int)std::max<long>(1, std::min<long>(pmax, cus / std::max<long>(tiles, 1)));
-    unsigned gblk = 0, rblk = 0;
+    G.nprob = n;
+    G.split_xcd = m.split_xcd;
+    R.nprob = m.nrow;
+    R.serial = m.serial;
     int nrow = 0;
     for (int i = 0; i < n; ++i) {
         const MidOp &o = ops[i];
         const HostLayer &ly = *o.ly;
         const bool sel = o.sel != nullptr;
+        const MidRoute::Prob &mp = m.pr[i];
         GemmMProb &g = G.pr[i];
         g.A = reinterpret_cast<const _Float16 *>(o.A); g.KBa = o.lda / 16;
         g.a_kb0 = o.range ? o.range->col_off / 16 : 0;
-        g.nk = (o.range ? o.range->kblocks : ly.KB) / 2;  // k32-slabs
+        g.nk = mp.nk;
         g.kb0 = o.range ? o.range->kb0 : 0; g.kbs = ly.KB;
         g.wp = ly.wps; g.w_sel_stride = sel && o.is_q ? q_wstride(h, o.layer) : 0;
-        g.CT = ly.CT; g.ncolblk = (ly.CT + 7) / 8; g.nrowblk = (int)(rows_p / GM_TM);
-        g.parts = std::max(1, std::min(pall, g.nk / 2));
+        g.CT = ly.CT; g.ncolblk = mp.ncolblk; g.nrowblk = mp.nrowblk; g.parts = mp.parts;
         g.sel = o.sel; g.sel_stride = 2; g.rows_per_env = rpe;
-        g.ldw = g.ncolblk * 256; g.part_stride = (long)rows_p * g.ldw;
-        if ((size_t)g.parts * g.part_stride > L.mws_cap) return fail(TDMPC2_ERR_STATE, "few-row path: partial-sum workspace too small");
+        g.ldw = mp.ldw; g.part_stride = mp.part_stride;
         g.ws = L.mws[i];
-        g.nblk = 8 * ((g.ncolblk * g.parts + 7) / 8) * g.nrowblk;
+        g.nblk = mp.nblk;
         g.rows = (int)rows;
-        gblk += (unsigned)g.nblk;
         // the row-side description of the layer (m_rows, or the GEMM's own epilogue when the tile is whole: parts == 1)
         MRowProb r{};
-        r.kind = o.kind; r.rows = (int)rows; r.rows_per_env = rpe;
-        if ((int)rows < MR_WIDE_MIN) r.nwg = (o.kind == MR_LN_MISH || o.kind == MR_LN_SIMNORM) ? (int)rows : (int)((rows + 3) / 4);  // m_rows<256>
-        else r.nwg = (int)((rows + MR_R - 1) / MR_R);                                                                            // m_rows<512>
+        r.kind = o.kind; r.rows = (int)rows; r.rows_per_env = rpe; r.nwg = mp.nwg;
         r.ws = g.ws; r.part_stride = g.part_stride; r.ldw = g.ldw; r.parts = g.parts;
         r.oscale = ly.oscale; r.osc_sel_stride = sel ? (long)(3 * sizeof(LayerScal) / sizeof(float)) : 0;
-        if (o.slot >= 0 && h->cfg.multitask) {
-            r.bias = L.bias_tab + (size_t)o.slot * L.Mp; r.bias_env_stride = (long)h->nnets * L.Mp; r.bias_sel_stride = sel ? L.Mp : 0;
-        } else {
-            r.bias = ly.bias; r.bias_env_stride = 0; r.bias_sel_stride = sel && o.is_q ? q_bstride(h, o.layer) : 0;
-        }
-        if (o.range && o.range->bias_env) { r.bias = o.range->bias_env; r.bias_env_stride = o.range->bias_env_stride; r.bias_sel_stride = 0; }
+        lay_bias(r, h, ly, o.slot, sel, o.is_q ? q_bstride(h, o.layer) : 0, o.range);
         r.sel = o.sel; r.sel_stride = 2; r.row_env = nullptr;
-        const bool ln = o.kind == MR_LN_MISH || o.kind == MR_LN_SIMNORM;
-        if (ln) {
+        if (o.kind == MR_LN_MISH || o.kind == MR_LN_SIMNORM) {
             r.width = o.width; r.g = ly.g; r.b = ly.b; r.gb_sel_stride = sel && o.is_q ? q_gstride(h, o.layer) : 0;
             r.ascale = ly.ascale; r.asc_sel_stride = sel ? (long)(3 * sizeof(LayerScal) / sizeof(float)) : 0;
             r.out = reinterpret_cast<char *>(o.out); r.KBo = o.ldo / 16;
@@ -518,14 +447,8 @@ int mid_stage(tdmpc2_plan *h, hipStream_t st, size_t rows, size_t rows_p, int rp
         }
         r.term = L.TERM;
         r.th = o.th; r.pi = o.pi;
-        // whole-K tiles of a NormedLinear: LayerNorm + activation + split in the GEMM's own epilogue (no partial sums, no m_rows) -- the
-        // 317M model's hidden layers (2 x 128 tiles = the chip), the 48M model from four plans on.  Needs the exchange buffers and the
-        // handle's consent (L.fuse_ln: off after a reported wait, apply_modes).  Rows that also carry the next step's actions stay with m_rows.
-        float *stats = i == 0 ? L.stats : L.stats2;
-        const size_t stats_need = rows_p * ((ly.CT + 3) / 4) * 2;
-        if (ln && g.parts == 1 && L.fuse_ln && L.knob[LK_MID_FUSE_LN] && !o.actions && stats && L.arrive && stats_need <= L.stats_cap &&
-            (L.arrive_pending ? 0 : L.arrive_off) + (size_t)g.nrowblk <= L.arrive_cap && rpe % GM_TM == 0) {
-            if (L.arrive_pending) {
+        if (mp.epi) {  // the NormedLinear inside g_gemm_m: the counters of the stage are zeroed in front of the first launch that waits
+            if (mp.reset) {
                 L.arrive_pending = false;
                 int rc0 = lay_arrive_reset(h, st);
                 if (rc0) return rc0;
@@ -533,33 +456,16 @@ int mid_stage(tdmpc2_plan *h, hipStream_t st, size_t rows, size_t rows_p, int rp
             g.epi = o.kind == MR_LN_MISH ? 1 : 2;
             g.oscale = r.oscale; g.osc_sel_stride = r.osc_sel_stride;
             g.bias = r.bias; g.bias_env_stride = r.bias_env_stride; g.bias_sel_stride = r.bias_sel_stride;
-            g.ln_g = r.g; g.ln_b = r.b; g.gb_sel_stride = r.gb_sel_stride; g.ascale = r.ascale; g.asc_sel_stride = r.asc_sel_stride;
-            g.width = o.width; g.stats = stats; g.arrive = L.arrive + L.arrive_off; g.err = h->cl_err_dev; g.fault = h->cl_fault;
-            g.out = o.out; g.KBo = o.ldo / 16;
-            L.arrive_off += (size_t)g.nrowblk;
+            lay_ln_epi(g, h, ly, r.gb_sel_stride, sel, o.width, stats[i], mp.arrive, o.out, o.ldo);
         } else {
             R.pr[nrow++] = r;
-            rblk += (unsigned)r.nwg;
         }
     }
-    R.nprob = nrow;
-    // two problems of one shape: one per half of the XCDs (g_gemm_m); each problem's share of the grid is 4 x ceil(jobs / 4) x row blocks
-    if (n == 2 && L.knob[LK_MID_SPLIT_XCD] && G.pr[0].ncolblk * G.pr[0].parts == G.pr[1].ncolblk * G.pr[1].parts && G.pr[0].nrowblk == G.pr[1].nrowblk) {
-        const int jobs = G.pr[0].ncolblk * G.pr[0].parts;
-        G.split_xcd = 1;
-        gblk = 8u * (unsigned)((jobs + 3) / 4) * (unsigned)G.pr[0].nrowblk;
-        G.pr[0].nblk = G.pr[1].nblk = (int)gblk / 2;
-    }
-    hipLaunchKernelGGL(g_gemm_m, dim3(gblk), dim3(512), 0, st, G);
+    hipLaunchKernelGGL(g_gemm_m, dim3(m.gblk), dim3(512), 0, st, G);
     LAUNCH_CHECK();
-    const bool small = (int)rows < MR_WIDE_MIN;
-    if (nrow == 0) return 0;  // both layers' epilogues ran inside the GEMM
-    if (rows_one_by_one && nrow == 2) {  // the second problem's rows read what the first one's wrote (the two Q heads' two-hots, qtmp):
-        R.serial = 1;                    // one grid over problem 0's rows, every wavefront does its row of both problems in order
-        rblk = (unsigned)R.pr[0].nwg;
-    }
-    if (small) hipLaunchKernelGGL(m_rows<256>, dim3(rblk), dim3(256), 0, st, R);
-    else hipLaunchKernelGGL(m_rows<512>, dim3(rblk), dim3(512), 0, st, R);
+    if (m.nrow == 0) return 0;  // both layers' epilogues ran inside the GEMM
+    if (m.mr_threads == 256) hipLaunchKernelGGL(m_rows<256>, dim3(m.rblk), dim3(256), 0, st, R);
+    else hipLaunchKernelGGL(m_rows<512>, dim3(m.rblk), dim3(512), 0, st, R);
     LAUNCH_CHECK();
     return 0;
 }
@@ -697,7 +603,7 @@ int lay_estimate_value(tdmpc2_plan *h, hipStream_t st, int E, const float *z0, c
     const bool ranged = N != NF;
     const size_t rows = (size_t)E * N, rows_p = round_up(rows, GBM);
     int rc;
-    if (mid_ok(h, rows_p))  // few rows (single plans): K-part tiles + row kernels on one stream (layered_mid.cuh)
+    if (mid_ok(mid_ctx(h), rows_p))  // few rows (single plans): K-part tiles + row kernels on one stream (layered_mid.cuh)
         return lay_estimate_value_m(h, st, E, z0, act_mask, disc_pow, actions, pi_eps, pi_eps_estride, qidx, seed, call, iter, value, trace, n_off, n_sub);
     if (L.pifold)  // lay_run decided with the same predicate that this call computes the policy-prior rows' actions: never reached
         return fail(TDMPC2_ERR_STATE, "policy-prior rows were left to a stage that does not compute them");
@@ -817,7 +723,7 @@ int lay_pitraj(tdmpc2_plan *h, hipStream_t st, int E, const float *z0, const flo
     const int P = c.num_pi_trajs, H = c.horizon, A = c.action_dim, rpe = L.Ppad;
     const size_t rows = (size_t)E * rpe, rows_p = round_up(rows, GBM);
     int rc;
-    if (mid_ok(h, rows_p)) return lay_pitraj_m(h, st, E, z0, act_mask, tape_eps, seed, call);
+    if (mid_ok(mid_ctx(h), rows_p)) return lay_pitraj_m(h, st, E, z0, act_mask, tape_eps, seed, call);
     if ((rc = lay_arrive_reset(h, st))) return rc;
     if (h->split)
         hipLaunchKernelGGL(l_init_x_s, init_x_grid(rows, L.Kin), dim3(256), 0, st, L.X, L.Kin, c.latent_dim, rpe, z0, (float *)nullptr,
@@ -885,7 +791,7 @@ int lay_run(tdmpc2_plan *h, hipStream_t st, int E, const float *z0, const float 
     if ((rc = lay_cvec(h, st, E, z0))) return rc;
     // one plan on the few-row path: the policy-prior trajectories ride along in iteration 0's stage (lay_estimate_value_m) -- their own
     // pass would repeat the dynamics of rows the stage rolls out anyway (12 of its 27 layer launches on the 317M model)
-    const bool pifold = P > 0 && E == 1 && h->lay.knob[LK_MID_PIFOLD] && mid_ok(h, round_up((size_t)E * N, GBM));
+    const bool pifold = P > 0 && E == 1 && h->lay.knob[LK_MID_PIFOLD] && mid_ok(mid_ctx(h), round_up((size_t)E * N, GBM));
     if (P > 0 && !pifold && (rc = lay_pitraj(h, st, E, z0, act_mask, tape ? tape->pi_traj_eps : nullptr, seed, call))) return rc;
     int refit_stage = 0;
     const size_t refit_lds = refit_lds_bytes(N, K, H, A, &refit_stage);

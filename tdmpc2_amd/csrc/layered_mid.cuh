@@ -34,7 +34,7 @@
 // Included by k_layered.hip after layered_wide.cuh.
 #pragma once
 
-constexpr int GM_TM = 128;        // rows of a tile
+// (GM_TM = 128 rows of a tile, MR_R, MR_WIDE_MIN: layer_route.h, with the routes that size the launches)
 constexpr int GM_SLOT = 49152;    // bytes of a k32-slab in the ring: [A: 4 row tiles x (kb, plane)][W: 8 column tiles x (kb, plane)] x 1 KiB
 constexpr int GM_NS = 3;          // ring slots (144 KiB): two slabs = 96 KiB in flight per CU, two phases (~1.7 us) for a slab to arrive.
                                   // History of this loop (profiles/README.md r6c, r6d, r6v): 64-row tiles with k32-slabs ran at the L2-miss
@@ -597,7 +597,7 @@ struct MRowParams {
 // workgroups on whatever XCDs they ran on -- 14 us per launch on 2 x 512 rows of the 48M model, 35 us on 2 x 1 024 rows of the 317M
 // model, 1.4 TB/s; the same with four rows per workgroup and a quarter of the parameter loads: 15 / 32 us.)
 // SimNorm's groups of 8 columns are thread-local.  Head kinds: one wavefront per row, all K-parts of its <= 128 columns in flight.
-constexpr int MR_R = 8, MR_THREADS = 512;
+constexpr int MR_THREADS = 512;  // (MR_R = 8 rows per workgroup: layer_route.h)
 template <int NQ>
 __device__ __forceinline__ void m_rows_ln(const MRowProb &p, int wg, float (*red)[MR_R][MR_THREADS / 64]) {
     constexpr int PCH = NQ <= 4 ? 4 : 2;  // K-parts loaded together
@@ -780,10 +780,6 @@ __device__ __forceinline__ void m_rows_ln(const MRowProb &p, int wg, float (*red
 // row, thread t holds columns 4 (t + T q) .. + 3 -- more workgroups in flight than eight rows per workgroup would give (128 workgroups for a
 // 48M plan's two chains: 3.84 ms per plan against 3.29, r6h); the 8-byte stores of this mapping assemble every output line from
 // eight rows' writes, which is what the eight-row mapping above avoids where there are rows enough.
-#ifndef MR_WIDE_MIN_ROWS
-#define MR_WIDE_MIN_ROWS 1024
-#endif
-constexpr int MR_WIDE_MIN = MR_WIDE_MIN_ROWS;
 template <int QN, int T>
 __device__ __forceinline__ void m_rows_ln1(const MRowProb &p, int row, float (*red)[MR_R][MR_THREADS / 64]) {
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;

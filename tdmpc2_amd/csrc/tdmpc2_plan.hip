@@ -295,25 +295,6 @@ int dev_alloc(tdmpc2_plan *h, void **p, size_t bytes) {
     return 0;
 }
 
-// g_gemm_w's K-split workspaces (256 KiB per split tile and part, one workspace per chain), sized for what the handle's mode can
-// use (ADVICE r5: every layered handle used to pay for 1 024 slots per chain -- 0.5 GiB -- whatever its mode): mode 0 none; mode 2
-// (the default) only splits launches of at most cus / 2 tiles = at most cus / 16 tail tiles per XCD; mode 1 the last round of any
-// launch = 32 tail tiles per XCD.  Called at create and when tdmpc2_plan_set_tuning raises the mode (grows, never shrinks; the
-// smaller buffers stay with the handle until destroy).
-int ksws_ensure(tdmpc2_plan *h) {
-    Layered &L = h->lay;
-    if (!L.ks_tiles || L.ksplit == 0) return 0;
-    const size_t cus = (size_t)(h->num_cus > 0 ? h->num_cus : 256);
-    const size_t cap_slots = L.ksplit == 2 ? 8 * ((cus / 16 + 3) / 4 * 4) * 4 : 8 * 32 * 4;
-    const size_t want = std::min<size_t>(cap_slots, L.ks_tiles * 4);
-    if (want <= L.ksws_slots) return 0;
-    float *a = nullptr, *b = nullptr;
-    int rc;
-    if ((rc = dev_alloc(h, (void **)&a, want * 65536 * 4)) || (L.side && (rc = dev_alloc(h, (void **)&b, want * 65536 * 4)))) return rc;
-    L.ksws = a; L.ksws2 = b; L.ksws_slots = want;
-    return 0;
-}
-
 void dev_release(tdmpc2_plan *h, void *p) {  // free one allocation made with dev_alloc (tables that are re-grown)
     if (!p) return;
     for (size_t i = 0; i < h->allocs.size(); ++i)
@@ -322,6 +303,31 @@ void dev_release(tdmpc2_plan *h, void *p) {  // free one allocation made with de
             break;
         }
     (void)hipFree(p);
+}
+
+// g_gemm_w's K-split workspaces (256 KiB per split tile and part, one workspace per chain), sized for what the handle's mode can
+// use (ADVICE r5: every layered handle used to pay for 1 024 slots per chain -- 0.5 GiB -- whatever its mode): mode 0 none; mode 2
+// (the default) only splits launches of at most cus / 2 tiles = at most cus / 16 tail tiles per XCD; mode 1 the last round of any
+// launch = 32 tail tiles per XCD.  Called at create and when tdmpc2_plan_set_tuning raises the mode (grows, never shrinks; the
+// smaller buffers stay with the handle until destroy).  `mode`: the K-split mode the workspaces are for -- the caller stores it
+// only once they are there; a failed second allocation releases the first.
+int ksws_ensure(tdmpc2_plan *h, int mode) {
+    Layered &L = h->lay;
+    if (!L.ks_tiles || mode == 0) return 0;
+    const size_t cus = (size_t)(h->num_cus > 0 ? h->num_cus : 256);
+    const size_t cap_slots = mode == 2 ? 8 * ((cus / 16 + 3) / 4 * 4) * 4 : 8 * 32 * 4;
+    const size_t want = std::min<size_t>(cap_slots, L.ks_tiles * 4);
+    if (want <= L.ksws_slots) return 0;
+    float *a = nullptr, *b = nullptr;
+    int rc;
+    if ((rc = dev_alloc(h, (void **)&a, want * 65536 * 4))) return rc;
+    if (L.side && (rc = dev_alloc(h, (void **)&b, want * 65536 * 4))) {
+        dev_release(h, a);
+        h->bytes -= want * 65536 * 4;
+        return rc;
+    }
+    L.ksws = a; L.ksws2 = b; L.ksws_slots = want;
+    return 0;
 }
 
 template <class NET> NET to_dev(const HostNet &n);
@@ -906,7 +912,7 @@ int tdmpc2_plan_create(const tdmpc2_plan_cfg *cfg, tdmpc2_plan_t **out) {
             // of the handle's largest call (one workspace per chain)
             if (const char *ks = getenv("TDMPC2_KSPLIT")) L.ksplit = std::min(2, std::max(0, atoi(ks)));
             L.ks_tiles = (Rp % 256 == 0 && maxct >= 8) ? (Rp / 256) * ((maxct + 7) / 8) : 0;
-            if ((rc = ksws_ensure(h))) {
+            if ((rc = ksws_ensure(h, L.ksplit))) {
                 tdmpc2_plan_destroy(h);
                 return rc;
             }
@@ -1872,16 +1878,21 @@ int tdmpc2_plan_set_tuning(tdmpc2_plan_t *h, int key, int value) {
     }
     if (key == TDMPC2_TUNE_KSPLIT) {
         if (value < 0 || value > 2) return fail(TDMPC2_ERR_INVALID, "ksplit must be 0 (never), 1 (always) or 2 (few-tile launches)");
-        h->lay.ksplit = value;
         {
             DevGuard dev_(h->cfg.device);
-            return ksws_ensure(h);  // (a bigger workspace when the mode needs one)
+            const int rc = ksws_ensure(h, value);  // (a bigger workspace when the mode needs one)
+            if (rc) return rc;
         }
+        h->lay.ksplit = value;
+        return TDMPC2_OK;
     }
     if (key >= TDMPC2_TUNE_EXPERT && key < TDMPC2_TUNE_EXPERT + LK_COUNT) {
-        // measurement knobs of the layered family's tile choice (handle.h: LayKnob; include/tdmpc2_plan.h: tdmpc2_expert_knob).
+        // measurement knobs of the layered family's tile choice (layer_route.h: LayKnob, LAY_KNOBS; include/tdmpc2_plan.h: tdmpc2_expert_knob).
         // INT32_MIN restores the default.  They move work between kernels that compute the same values to fp32 round-off.
-        h->lay.knob[key - TDMPC2_TUNE_EXPERT] = value == INT32_MIN ? LAY_KNOB_DEFAULTS[key - TDMPC2_TUNE_EXPERT] : value;
+        const LayKnobSpec &k = LAY_KNOBS[key - TDMPC2_TUNE_EXPERT];
+        if (value != INT32_MIN && (value < k.lo || value > k.hi))
+            return fail(TDMPC2_ERR_INVALID, "expert knob %d: %d is outside %d .. %d", key - TDMPC2_TUNE_EXPERT, value, k.lo, k.hi);
+        h->lay.knob[key - TDMPC2_TUNE_EXPERT] = value == INT32_MIN ? k.def : value;
         return TDMPC2_OK;
     }
     if (key == TDMPC2_TUNE_WAIT_US) {

@@ -780,3 +780,22 @@ def test_safe_once_covers_one_plan_and_the_verdict_word_is_readable_on_the_devic
     torch.cuda.synchronize()
     assert torch.isnan(bad3).all() and int(word.item()) != 0 and planner.take_fault() == 1
     planner.close()
+
+
+def test_expert_knobs_outside_their_range_are_refused():
+    """tdmpc2_plan_set_tuning(TDMPC2_TUNE_EXPERT + knob): a value outside the knob's range (tdmpc2_amd/csrc/layer_route.h: LAY_KNOBS)
+    is TDMPC2_ERR_INVALID; the values with a meaning -- -1 = automatic, a negative GEMM_W256_MIN = no wide tile -- are taken, and
+    None (INT32_MIN) restores the default."""
+    from tdmpc2_amd.config import named_config
+    from tdmpc2_amd.native import NativeError, NativePlanner
+
+    planner = NativePlanner(named_config("small"), 3, torch.device("cuda", 0), max_envs=2, path=PATH_LAYERED)
+    for name, bad in (("GEMM_W_SPLIT_MAX", 5), ("GEMM_W_SPLIT_MAX", 0), ("GEMM_XCD_ROWS", 9), ("GEMM_W_XCD_ROWS", -2),
+                      ("MID_PIFOLD", 2), ("GEMM_RT4", -1), ("MID_PARTS_MAX", 0), ("GEMM_WIDE_MIN", -1)):
+        with pytest.raises(NativeError):
+            planner.set_expert(name, bad)
+    for name, good in (("GEMM_W256_MIN", -1), ("GEMM_W256_MIN", 128), ("GEMM_W_SPLIT_MAX", 4), ("KSPLIT_AUTO_MIN", -1),
+                       ("GEMM_XCD_ROWS", 2), ("GEMM_COL_PAD", 0), ("MID_PARTS_MAX", 32), ("MID_PIFOLD", 0)):
+        planner.set_expert(name, good)
+        planner.set_expert(name, None)
+    planner.close()

@@ -13,12 +13,11 @@ what the measured locality gains rest on -- are properties of the block -> tile 
 * the rule picks the order the measurements chose (profiles/README.md r3v, r3u, r3s).
 """
 import ctypes
-import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tdmpc2_amd.config import named_config
+from tests import layer_route_model as lrm
 SHIM = r"""
 #include "tile_order.h"
 extern "C" void order(int nrowblk, int ncolblk, int force_xcd_rows, int col_pad, int *out) {
@@ -40,13 +39,7 @@ extern "C" int w_tile(int b, int nrowblk, int ncolblk, int full, int parts, int 
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    d = tmp_path_factory.mktemp("tile_order")
-    src = d / "shim.cpp"
-    src.write_text(SHIM)
-    so = d / "libtile_order.so"
-    subprocess.run(["g++", "-O1", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(ROOT, "tdmpc2_amd", "csrc"), str(src), "-o", str(so)],
-                   check=True)
-    return ctypes.CDLL(str(so))
+    return lrm.build(tmp_path_factory.mktemp("tile_order"), SHIM)  # (with the route shim of layer_route.h)
 
 
 def order(lib, nrowblk, ncolblk, force=-1, col_pad=1):
@@ -269,29 +262,37 @@ def _deadlock_pair(HA, HB, cap):
     return False
 
 
-def _launch_model(lib, nrowblk, ncolblk, nk, ksplit, tile_fn=None):
-    """Per-XCD held bounds of one fused-epilogue launch of the wide tile (one workgroup per CU) as the host would order it:
-    K-split tail when `ksplit` and the rule says so, else XCD-local row blocks (>= 16 row blocks) or row-major."""
-    entries, nblk, spans = {}, 0, False
-    o = w_order(lib, nrowblk, ncolblk, nk=nk, ovh=12000 // (nk + 25)) if ksplit else {"parts": 1}
-    if o["parts"] > 1:
+def _launch_model(lib, r, tile_fn=None):
+    """Per-XCD held bounds of one fused-epilogue launch of the wide tile (one workgroup per CU) as layer_route.h routes it (`r`):
+    its K-split tail when it has one, else its tile order (XCD-local row blocks or row-major)."""
+    nrowblk, ncolblk = r["nrowblk"], r["ncolblk"]
+    entries, spans = {}, False
+    if r["parts"] > 1:
+        o = {"parts": r["parts"], "full": r["full"], "max_tail": r["max_tail"], "nblk": r["wo_nblk"]}
         nblk = o["nblk"]
-        rb, cb, part, slot = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         for b in range(nblk):
             got = (tile_fn or _w_tile)(lib, b, nrowblk, ncolblk, o)
             if got:
-                r, c, _, sl = got
-                entries[b] = (r, (r, c, o["parts"] if sl >= 0 else 1), o["parts"] if sl >= 0 else 1)
+                rb, cb, _, sl = got
+                entries[b] = (rb, (rb, cb, o["parts"] if sl >= 0 else 1), o["parts"] if sl >= 0 else 1)
     else:
-        so = order(lib, nrowblk, ncolblk, 1 if nrowblk >= 16 else 0, 1)
+        so = {"xcd_rows": r["xcd_rows"], "ncol_grid": r["ncol_grid"], "nblk": r["ord_nblk"]}
         nblk, spans = so["nblk"], so["xcd_rows"] == 0
-        for b, r, c in tiles(lib, nrowblk, ncolblk, so):
-            entries[b] = (r, (r, c, 1), 1)
+        for b, rb, cb in tiles(lib, nrowblk, ncolblk, so):
+            entries[b] = (rb, (rb, cb, 1), 1)
+    assert nblk == r["grid"]
     rb_sizes = {}
-    for r, tile, parts in entries.values():
-        rb_sizes[r] = rb_sizes.get(r, 0) + 1
+    for rb, tile, parts in entries.values():
+        rb_sizes[rb] = rb_sizes.get(rb, 0) + 1
     lists = _xcd_lists(entries, nblk)
     return [(_held_bound(l, rb_sizes), sum(s is not None for s in l)) for l in lists], spans
+
+
+def _wide_launch(lib, model, E, layer, ksplit):
+    """The route of a g_gemm_w launch of the plan (`layer`: its label in layer_route_model.plan_launches)."""
+    r = next(r for label, kind, r in lrm.plan_launches(lib, named_config(model), E, ksplit) if label == layer)
+    assert r["w"]
+    return r
 
 
 def _w_tile(lib, b, nrowblk, ncolblk, o):
@@ -314,36 +315,97 @@ def _w_tile_tile_major(lib, b, nrowblk, ncolblk, o):
     return None if got is None else (got[0], got[1], part, got[3])
 
 
-# the GEMM shapes of a stage: (column blocks of 256, k16-slabs) of the hidden layers / the SimNorm output layer
-C3 = [(7, 112), (7, 50), (3, 112)]
-C4 = [(16, 256), (16, 88), (6, 256)]
+_GEOM = ("nrowblk", "ncolblk", "parts", "full", "max_tail", "xcd_rows", "ncol_grid", "ord_nblk", "wo_nblk")
 
 
-@pytest.mark.parametrize("model,shapes,rows_per_plan", [("c3", C3, 512), ("c4", C4, 1024)])
-def test_no_order_the_library_picks_can_deadlock_in_the_dispatcher_model(lib, model, shapes, rows_per_plan):
+def _mid_tiles(r):
+    """g_gemm_m's block -> (problem, row block, column job) map (layered_mid.cuh: g_gemm_m) over a few-row route `r`: per workgroup that
+    has a tile (padding blocks -- job >= ncolblk x parts -- leave at once) its XCD (b % 8), its slot in that XCD's in-order share of
+    the grid (b / 8), its row block and whether it waits (the problem's NormedLinear epilogue is inside the GEMM)."""
+    pr, res = r["pr"], []
+    for b0 in range(r["gblk"]):
+        b = b0
+        if r["split_xcd"]:
+            pi, x, lanes = (b & 7) >> 2, b & 3, 4
+        else:
+            pi = 1 if len(pr) > 1 and b >= pr[0]["nblk"] else 0
+            b -= pr[0]["nblk"] if pi else 0
+            x, lanes = b & 7, 8
+        p, t = pr[pi], b >> 3
+        jj = t // p["nrowblk"]
+        rb, job = t - jj * p["nrowblk"], jj * lanes + x
+        if job < p["ncolblk"] * p["parts"]:
+            res.append((b0 % 8, b0 >> 3, (pi, rb), bool(p["epi"])))
+    return res
+
+
+# Few-row launches whose workgroups with a tile do NOT fit their XCDs (32 CUs each, one workgroup per CU): the 1M model's pairs of
+# hidden layers at 9 .. 16 plans -- two column jobs per row block, problem 0's on XCDs 0 and 1, problem 1's on 4 and 5, every row
+# block on each: 36 .. 64 waiting workgroups on each of those XCDs.  Their waits are not for resident peers; they resolve through
+# the in-order dispatch of each XCD (a row block's peers hold the same slot of their XCDs' shares, asserted below) and are bounded
+# like every other wait (DESIGN 8).
+MID_OVER_ONE_ROUND = {("m1_mt30", E, label) for E in range(9, 17)
+                      for label in ("dyn|rew.l0@t0", "dyn|rew.l0", "dyn|rew.l1", "q0|q1.l0", "q0|q1.l1")}
+
+
+@pytest.mark.parametrize("model", ["c3", "c4", "m19_mt80", "m19_mt30", "m1_mt30"])
+def test_no_order_the_library_picks_can_deadlock_in_the_dispatcher_model(lib, model):
+    """Every launch whose workgroups wait for each other that layer_route.h returns for a plan of `model` (E = 1 .. 64, K-split modes
+    0 / 1 / 2, default knobs, the policy-prior pass included -- layer_route_model.plan_launches): each g_gemm_w launch alone and
+    paired with every wide launch of the same plan (the two chains of a stage) in the per-XCD model; for each g_gemm_m launch with
+    the NormedLinear epilogue inside, the workgroups with a tile on every XCD fit its CUs (the few-row path's waits are for
+    resident peers) -- except the launches of MID_OVER_ONE_ROUND, exactly those.  Waiting g_gemm_s launches are counted, not modelled."""
     cap = CUS_PER_SE  # the wide tile: one workgroup per CU
-    proven, coresident = 0, 0
+    cfg = named_config(model)
+    models, pairs = {}, {}
+    w_launches = coresident = s_waits = m_waits = 0
+    over = set()
     for E in range(1, 65):
-        if (E * rows_per_plan) % 256:
-            continue  # the wide tile takes whole 256-row blocks
-        nrowblk = E * rows_per_plan // 256
-        for ksplit in (False, True):
-            launches = [_launch_model(lib, nrowblk, nc, nk, ksplit) for nc, nk in shapes]
-            for i, (la, spans_a) in enumerate(launches):
-                for x in range(8):
-                    assert not _deadlock_alone(la[x][0], cap), (model, E, ksplit, shapes[i], x)
-                for j, (lb, spans_b) in enumerate(launches):
-                    if spans_a or spans_b:
-                        # row blocks on several XCDs (row-major orders of launches with < 16 row blocks): the per-XCD argument does
-                        # not apply; such a pair is only claimed safe when both launches fit the chip together
-                        if all(la[x][1] + lb[x][1] <= SE * cap for x in range(8)):
-                            coresident += 1
-                        continue
+        for ksplit in (0, 1, 2):
+            wide = {}
+            for label, kind, r in lrm.plan_launches(lib, cfg, E, ksplit):
+                if kind == "mid":
+                    if any(p["epi"] for p in r["pr"]):
+                        m_waits += 1
+                        tiles_m = _mid_tiles(r)
+                        per_xcd = [sum(x == xcd for x, _, _, _ in tiles_m) for xcd in range(8)]
+                        if max(per_xcd) > lrm.CUS // 8:
+                            over.add((model, E, label))
+                            slots = {}  # a row block's waiting peers: one slot of the XCDs' in-order shares
+                            for x, t, rb, waits in tiles_m:
+                                if waits:
+                                    slots.setdefault(rb, set()).add(t)
+                            assert all(len(v) == 1 for v in slots.values()), (model, E, ksplit, label)
+                elif r["w"]:
+                    w_launches += 1
+                    wide.setdefault(tuple(r[k] for k in _GEOM), []).append(r)
+                elif r["epi"] in (1, 2):
+                    s_waits += 1
+            for ka, ra in wide.items():
+                if ka not in models:
+                    models[ka] = _launch_model(lib, ra[0])
                     for x in range(8):
-                        assert not _deadlock_pair(la[x][0], lb[x][0], cap), (model, E, ksplit, shapes[i], shapes[j], x)
-                    proven += 1
-    assert proven > 100
-    print(f"[{model}] dispatcher model: {proven} launch pairs proven per XCD, {coresident} row-major pairs co-resident")
+                        assert not _deadlock_alone(models[ka][0][x][0], cap), (model, E, ksplit, ka, x)
+            for ka in wide:
+                la, spans_a = models[ka]
+                for kb in wide:
+                    lb, spans_b = models[kb]
+                    if (ka, kb) not in pairs:
+                        if spans_a or spans_b:
+                            # row blocks on several XCDs (row-major orders of launches with < 16 row blocks): the per-XCD argument does
+                            # not apply; such a pair is only claimed safe when both launches fit the chip together
+                            pairs[ka, kb] = all(la[x][1] + lb[x][1] <= SE * cap for x in range(8))
+                        else:
+                            for x in range(8):
+                                assert not _deadlock_pair(la[x][0], lb[x][0], cap), (model, E, ksplit, ka, kb, x)
+                            pairs[ka, kb] = False
+                    coresident += pairs[ka, kb]
+    assert over == {k for k in MID_OVER_ONE_ROUND if k[0] == model}
+    # the route still returns what the model is about: hundreds of waiting wide-tile launches of dozens of geometries, few-row waits
+    assert w_launches > 1000 and len(models) > 50 and len(pairs) >= len(models) and m_waits > 0, (w_launches, len(models), m_waits)
+    print(f"[{model}] dispatcher model: {w_launches} waiting g_gemm_w launches checked ({len(models)} geometries, {len(pairs)} pairs, "
+          f"{coresident} row-major pairs co-resident); {m_waits} waiting g_gemm_m launches, {len(over)} of them above one round of an "
+          f"XCD; {s_waits} waiting g_gemm_s launches not modelled")
 
 
 def test_the_dispatcher_model_reports_the_orders_that_deadlocked_on_the_gpu(lib):
@@ -353,8 +415,10 @@ def test_the_dispatcher_model_reports_the_orders_that_deadlocked_on_the_gpu(lib)
     on one engine (four row blocks of an XCD slot-interleaved) -- the 48M model's two chains deadlocked on every stage."""
     cap = CUS_PER_SE
     # (i)
-    good, _ = _launch_model(lib, 12, 16, 256, True)  # three plans: 24 tiles x 4 parts on every XCD
-    bad, _ = _launch_model(lib, 12, 16, 256, True, tile_fn=_w_tile_tile_major)
+    r = _wide_launch(lib, "c4", 3, "dyn.l1", 1)  # three plans, K-split mode 1: 24 tiles x 4 parts on every XCD
+    assert (r["nrowblk"], r["ncolblk"], r["parts"]) == (12, 16, 4)
+    good, _ = _launch_model(lib, r)
+    bad, _ = _launch_model(lib, r, tile_fn=_w_tile_tile_major)
     assert good[0][1] == 96
     assert not any(_deadlock_alone(good[x][0], cap) for x in range(8))
     assert any(_deadlock_alone(bad[x][0], cap) for x in range(8))
@@ -370,6 +434,8 @@ def test_the_dispatcher_model_reports_the_orders_that_deadlocked_on_the_gpu(lib)
     rb_sizes = {r: ncolblk for r in range(nrowblk)}
     nblk = 8 * (max(entries) // 8 + 1)
     se_local = [_held_bound(l, rb_sizes) for l in _xcd_lists(entries, nblk)]
-    shipped, _ = _launch_model(lib, nrowblk, ncolblk, 112, False)
+    r = _wide_launch(lib, "c3", 30, "dyn.l1", 0)
+    assert (r["nrowblk"], r["ncolblk"], r["parts"], r["xcd_rows"]) == (nrowblk, ncolblk, 1, 1)
+    shipped, _ = _launch_model(lib, r)
     assert not any(_deadlock_pair(shipped[x][0], shipped[x][0], cap) for x in range(8))
     assert any(_deadlock_pair(se_local[x], se_local[x], cap) for x in range(8))
