@@ -17,6 +17,9 @@
  *   tdmpc2_plan_bind_encoder  <- the state encoder's parameters         tdmpc2/common/layers.py:153-164
  *   tdmpc2_plan_encode        <- WorldModel.encode (state observations) tdmpc2/common/world_model.py:103-112
  *   tdmpc2_plan_run_obs       <- TDMPC2._plan including encode()        tdmpc2/tdmpc2.py:152-206
+ *   tdmpc2_plan_bind_pixel_encoder <- the pixel encoder's parameters    tdmpc2/common/layers.py:136-150
+ *   tdmpc2_plan_encode_pix    <- WorldModel.encode (rgb observations)   tdmpc2/common/layers.py:36-71,136-150
+ *   tdmpc2_plan_run_pix       <- TDMPC2._plan including encode(), rgb   tdmpc2/tdmpc2.py:152-206
  *   tdmpc2_plan_td_target[_mt]    <- TDMPC2._td_target                  tdmpc2/tdmpc2.py:239-254
  *   tdmpc2_plan_policy_value[_mt] <- forward half of TDMPC2.update_pi   tdmpc2/tdmpc2.py:208-225
  *   tdmpc2_plan_export_packed / import_packed <- TDMPC2.save / load of the planner's weights  tdmpc2/tdmpc2.py:72-95
@@ -55,7 +58,7 @@
 extern "C" {
 #endif
 
-#define TDMPC2_PLAN_ABI_VERSION 9
+#define TDMPC2_PLAN_ABI_VERSION 10
 
 typedef struct tdmpc2_plan tdmpc2_plan_t;
 
@@ -207,8 +210,8 @@ int tdmpc2_plan_set_call_counter(tdmpc2_plan_t *h, uint32_t next_call);
 
 /* State-observation encoder: WorldModel.encode for cfg.obs == 'state'
  * (tdmpc2/common/world_model.py:103-112) with the network of layers.enc (tdmpc2/common/layers.py:153-164):
- * n_layers NormedLinear blocks, Mish after all but the last, SimNorm after the last.  Pixel observations are encoded
- * by the host framework's conv module (tdmpc2_amd/layers.py: conv) and enter through tdmpc2_plan_run as latents.  bind_encoder takes one nn.Linear (`W` [out, in] row-major, `b` [out]) and its LayerNorm (`ln_g`,
+ * n_layers NormedLinear blocks, Mish after all but the last, SimNorm after the last.  Pixel observations have an encoder
+ * of their own (tdmpc2_plan_bind_pixel_encoder / encode_pix / run_pix below).  bind_encoder takes one nn.Linear (`W` [out, in] row-major, `b` [out]) and its LayerNorm (`ln_g`,
  * `ln_b` [out]) per call, DEVICE pointers, copied (weights transposed) into library memory; layer 0 takes
  * obs_dim + task_dim inputs, the last layer has latent_dim outputs; widths up to 4096. */
 int tdmpc2_plan_bind_encoder(tdmpc2_plan_t *h, int layer, int n_layers, const float *W, const float *b,
@@ -224,6 +227,29 @@ int tdmpc2_plan_encode(tdmpc2_plan_t *h, int n_envs, const float *obs, int obs_d
 int tdmpc2_plan_run_obs(tdmpc2_plan_t *h, int n_envs, const float *obs, int obs_dim, const float *task_emb,
                         const float *act_mask, const float *disc_pow, float *prev_mean, const uint8_t *t0,
                         int eval_mode, const tdmpc2_noise *tape, uint64_t seed, float *action, void *stream);
+
+/* Pixel-observation encoder (ABI 10): WorldModel.encode for cfg.obs == 'rgb' with the network of layers.conv
+ * (tdmpc2/common/layers.py:36-71, 136-150): ShiftAug (replicate pad 3 + bilinear resampling by an integer shift), x / 255 - 0.5,
+ * Conv2d 7x7/2, 5x5/2, 3x3/2, 3x3/1 with bias and ReLU between, Flatten, SimNorm; fp32 throughout.  Frames are 64 x 64;
+ * C = out_channels = cfg.num_channels, a multiple of 8 in [8, 64] with 16 C == latent_dim; Cin = in_channels in [1, 16] (9 for
+ * three stacked RGB frames).  Single-task handles only (a multitask handle: TDMPC2_ERR_UNSUPPORTED -- the reference cannot
+ * concatenate task_emb onto an image either, world_model.py:88-112).  Not part of the packed blob: re-bind after import_packed.
+ * bind_pixel_encoder takes one Conv2d per call, checkpoint keys _encoder.rgb.{2,4,6,8}.{weight,bias} for layers 0..3:
+ * W [C, Cin (layer 0) | C, k, k], b [C], kernel = 7, 5, 3, 3; DEVICE pointers, copied (re-packed).  The first call allocates
+ * every buffer the encoder uses (a workspace for max_envs images): encode_pix / run_pix allocate nothing. */
+int tdmpc2_plan_bind_pixel_encoder(tdmpc2_plan_t *h, int layer, const float *W, const float *b, int out_channels,
+                                   int in_channels, int kernel, void *stream);
+/*   obs [E, Cin, 64, 64] as uint8 (obs_dtype 0: what the reference's Pixels wrapper returns) or float32 (obs_dtype 1), raw
+ *   pixel levels; shift int32 [E, 2] = (dx, dy) of ShiftAug (dx moves the columns), DEVICE memory: the reference draws it with
+ *   torch.randint(0, 7, (E, 1, 1, 2)) in train and eval mode alike, so a caller that draws it the same way keeps its RNG stream
+ *   identical to the reference's.  Values outside [0, 6] are clamped.  -> z_out [E, 16 C].  1 <= n_envs <= max_envs.  No host
+ *   synchronisation: the call can be captured in a hipGraph. */
+int tdmpc2_plan_encode_pix(tdmpc2_plan_t *h, int n_envs, const void *obs, int obs_dtype, int in_channels,
+                           const int32_t *shift, float *z_out, void *stream);
+/* TDMPC2._plan from the frame stack on: encode_pix into library memory, then exactly tdmpc2_plan_run (no task_emb / act_mask). */
+int tdmpc2_plan_run_pix(tdmpc2_plan_t *h, int n_envs, const void *obs, int obs_dtype, int in_channels, const int32_t *shift,
+                        const float *disc_pow, float *prev_mean, const uint8_t *t0, int eval_mode, const tdmpc2_noise *tape,
+                        uint64_t seed, float *action, void *stream);
 
 /* Training-side consumers of the planner's layer code, forward only, no gradients.  Both kernel
  * families, single-task and multitask models.  The fused family takes any number of rows; the layered family at most

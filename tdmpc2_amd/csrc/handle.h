@@ -161,6 +161,15 @@ struct tdmpc2_plan {
     float *zenc = nullptr;  // [max_envs, L]: latents of tdmpc2_plan_run_obs
     float *enc_y = nullptr, *enc_x = nullptr;  // wide encoders: [max_envs, widest layer] pre-activations / activations
     int enc_ws_width = 0;
+    // pixel-observation encoder (optional: bound with tdmpc2_plan_bind_pixel_encoder; pixel_kernels.cuh)
+    struct Pix {
+        float *wp[4] = {nullptr, nullptr, nullptr, nullptr};    // [cin][k][k][C] re-packed weights (layer 0 sized for 16 inputs)
+        float *bias[4] = {nullptr, nullptr, nullptr, nullptr};
+        bool bound[4] = {false, false, false, false};
+        int C = 0, cin = 0;
+        void *tab = nullptr;  // PixTap [7][64]: ShiftAug's resampling table (pixel_route.h)
+        float *ws = nullptr;  // [max_envs][pix_ws_floats(C)] layer outputs of the spread route
+    } pix;
     unsigned int call = 0;
     unsigned long long *timing = nullptr;  // TDMPC2_TIMING=1 with a -DSPLIT_TIMING build: in-kernel phase cycle counters
     // profiling

@@ -81,6 +81,7 @@ __global__ void k_copy_pad(const float *src, int n, int npad, float *dst) {
 
 #include "bind_kernels.cuh"
 #include "encoder_kernels.cuh"
+#include "pixel_kernels.cuh"
 
 // ================================================================ the in-kernel generator as a noise tape (tdmpc2_plan_export_noise)
 // Every draw of a tape = NULL plan, written with the index formulas and device functions of the kernels that consume them
@@ -1333,6 +1334,109 @@ int tdmpc2_plan_run_obs(tdmpc2_plan_t *h, int n_envs, const float *obs, int obs_
     if (rc) return rc;
     return run_impl(h, n_envs, h->zenc, task_emb, act_mask, discount_pow, prev_mean, t0, eval_mode, tape, seed, action, nullptr,
                     stream);
+}
+
+// ================================================================ pixel-observation encoder (pixel_kernels.cuh, pixel_route.h)
+int tdmpc2_plan_bind_pixel_encoder(tdmpc2_plan_t *h, int layer, const float *W, const float *b, int out_channels, int in_channels,
+                                   int kernel, void *stream) {
+    if (!h || !W || !b) return fail(TDMPC2_ERR_INVALID, "null argument");
+    const tdmpc2_plan_cfg &c = h->cfg;
+    if (c.multitask)  // the reference cannot concatenate task_emb onto an image either (world_model.py:88-112)
+        return fail(TDMPC2_ERR_UNSUPPORTED, "the pixel encoder is single-task only (multitask handle)");
+    if (layer < 0 || layer >= PIX_LAYERS) return fail(TDMPC2_ERR_INVALID, "pixel encoder layer %d outside [0, %d)", layer, PIX_LAYERS);
+    if (kernel != pix_kernel(layer))
+        return fail(TDMPC2_ERR_INVALID, "pixel encoder layer %d has a %dx%d kernel, not %dx%d", layer, pix_kernel(layer), pix_kernel(layer),
+                    kernel, kernel);
+    if (out_channels < PIX_MIN_C || out_channels > PIX_MAX_C || out_channels % 8)
+        return fail(TDMPC2_ERR_UNSUPPORTED, "pixel encoder: %d channels (a multiple of 8 in [%d, %d])", out_channels, PIX_MIN_C, PIX_MAX_C);
+    if (16 * out_channels != c.latent_dim)
+        return fail(TDMPC2_ERR_INVALID, "pixel encoder: 16 x %d channels is not latent_dim %d", out_channels, c.latent_dim);
+    if (c.simnorm_dim != 8) return fail(TDMPC2_ERR_UNSUPPORTED, "pixel encoder: SimNorm groups of %d (8 only)", c.simnorm_dim);
+    if (layer == 0 && (in_channels < 1 || in_channels > PIX_MAX_CIN))
+        return fail(TDMPC2_ERR_INVALID, "pixel encoder: %d input channels outside [1, %d]", in_channels, PIX_MAX_CIN);
+    if (layer > 0 && in_channels != out_channels)
+        return fail(TDMPC2_ERR_INVALID, "pixel encoder layer %d takes %d channels, not %d", layer, out_channels, in_channels);
+    ENTER_ON(h, stream);
+    tdmpc2_plan::Pix &P = h->pix;
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if (!P.tab) {  // every buffer of the encoder, once: encode / run never allocate
+        static PixTap host_tab[PIX_SHIFTS * PIX_IN];
+        static std::once_flag once;
+        std::call_once(once, [] { pix_shift_table(host_tab); });
+        for (int l = 0; l < PIX_LAYERS; ++l) {
+            const int cin = l == 0 ? PIX_MAX_CIN : out_channels;
+            if ((rc = dev_alloc(h, (void **)&P.wp[l], (size_t)cin * pix_kernel(l) * pix_kernel(l) * out_channels * 4))) return rc;
+            if ((rc = dev_alloc(h, (void **)&P.bias[l], (size_t)out_channels * 4))) return rc;
+        }
+        if ((rc = dev_alloc(h, &P.tab, sizeof(host_tab)))) return rc;
+        if ((rc = dev_alloc(h, (void **)&P.ws, pix_ws_bytes(c.max_envs, out_channels)))) return rc;
+        if (!h->zenc && (rc = dev_alloc(h, (void **)&h->zenc, (size_t)c.max_envs * c.latent_dim * 4))) return rc;
+        HIP_TRY(hipMemcpyAsync(P.tab, host_tab, sizeof(host_tab), hipMemcpyHostToDevice, st));
+        P.C = out_channels;
+    }
+    const int kk = kernel * kernel;
+    const int n = out_channels * in_channels * kk;
+    hipLaunchKernelGGL(k_pix_pack, dim3((n + 255) / 256), dim3(256), 0, st, W, P.wp[layer], out_channels, in_channels, kk);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(P.bias[layer], b, (size_t)out_channels * 4, hipMemcpyDeviceToDevice, st));
+    if (layer == 0) P.cin = in_channels;
+    P.bound[layer] = true;
+    return TDMPC2_OK;
+}
+
+namespace {
+int check_pix_call(tdmpc2_plan *h, int n_envs, int obs_dtype, int in_channels) {
+    const tdmpc2_plan::Pix &P = h->pix;
+    if (n_envs < 1 || n_envs > h->cfg.max_envs) return fail(TDMPC2_ERR_INVALID, "n_envs %d outside [1, %d]", n_envs, h->cfg.max_envs);
+    if (obs_dtype != 0 && obs_dtype != 1) return fail(TDMPC2_ERR_INVALID, "obs_dtype %d (0 = uint8, 1 = float32)", obs_dtype);
+    for (int l = 0; l < PIX_LAYERS; ++l)
+        if (!P.bound[l]) return fail(TDMPC2_ERR_STATE, "no pixel encoder bound (layer %d; tdmpc2_plan_bind_pixel_encoder)", l);
+    if (in_channels < 1 || in_channels > PIX_MAX_CIN)
+        return fail(TDMPC2_ERR_INVALID, "pixel encoder: %d input channels outside [1, %d]", in_channels, PIX_MAX_CIN);
+    if (in_channels != P.cin)
+        return fail(TDMPC2_ERR_INVALID, "pixel encoder: the observation has %d channels, layer 0 was bound with %d", in_channels, P.cin);
+    return 0;
+}
+
+int launch_encode_pix(tdmpc2_plan *h, int E, const void *obs, int obs_dtype, const int32_t *shift, float *z, hipStream_t st) {
+    const tdmpc2_plan::Pix &P = h->pix;
+    PixParams p{};
+    for (int l = 0; l < PIX_LAYERS; ++l) { p.wp[l] = P.wp[l]; p.bias[l] = P.bias[l]; }
+    p.obs = obs; p.obs_u8 = obs_dtype == 0; p.cin = P.cin; p.C = P.C;
+    p.shift = shift; p.tab = static_cast<const PixTap *>(P.tab); p.ws = P.ws; p.z = z;
+    const PixRoute r = pix_route(E, P.C, h->num_cus);
+    if (r.kind == PIX_PER_IMAGE) {
+        hipLaunchKernelGGL(k_pix_image, dim3(r.g[0].x), dim3(r.g[0].threads), r.g[0].lds, st, p);
+    } else {
+        hipLaunchKernelGGL(k_pix_spread<0>, dim3(r.g[0].x, r.g[0].y, r.g[0].z), dim3(r.g[0].threads), 0, st, p);
+        hipLaunchKernelGGL(k_pix_spread<1>, dim3(r.g[1].x, r.g[1].y, r.g[1].z), dim3(r.g[1].threads), 0, st, p);
+        hipLaunchKernelGGL(k_pix_spread<2>, dim3(r.g[2].x, r.g[2].y, r.g[2].z), dim3(r.g[2].threads), 0, st, p);
+        hipLaunchKernelGGL(k_pix_spread<3>, dim3(r.g[3].x, r.g[3].y, r.g[3].z), dim3(r.g[3].threads), 0, st, p);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+}  // namespace
+
+int tdmpc2_plan_encode_pix(tdmpc2_plan_t *h, int n_envs, const void *obs, int obs_dtype, int in_channels, const int32_t *shift,
+                           float *z_out, void *stream) {
+    if (!h || !obs || !shift || !z_out) return fail(TDMPC2_ERR_INVALID, "null argument");
+    int rc = check_pix_call(h, n_envs, obs_dtype, in_channels);
+    if (rc) return rc;
+    ENTER_ON(h, stream);
+    return launch_encode_pix(h, n_envs, obs, obs_dtype, shift, z_out, (hipStream_t)stream);
+}
+
+int tdmpc2_plan_run_pix(tdmpc2_plan_t *h, int n_envs, const void *obs, int obs_dtype, int in_channels, const int32_t *shift,
+                        const float *disc_pow, float *prev_mean, const uint8_t *t0, int eval_mode, const tdmpc2_noise *tape, uint64_t seed,
+                        float *action, void *stream) {
+    if (!h || !obs || !shift || !disc_pow || !prev_mean || !t0 || !action) return fail(TDMPC2_ERR_INVALID, "null argument");
+    int rc = check_pix_call(h, n_envs, obs_dtype, in_channels);
+    if (rc) return rc;
+    ENTER_ON(h, stream);
+    if ((rc = launch_encode_pix(h, n_envs, obs, obs_dtype, shift, h->zenc, (hipStream_t)stream))) return rc;
+    return run_impl(h, n_envs, h->zenc, nullptr, nullptr, disc_pow, prev_mean, t0, eval_mode, tape, seed, action, nullptr, stream);
 }
 
 namespace {

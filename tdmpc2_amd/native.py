@@ -17,7 +17,7 @@ import torch
 _LIB_PATH = os.environ.get("TDMPC2_PLAN_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtdmpc2_plan.so")
 _lib = None
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 # every symbol include/tdmpc2_plan.h declares (tests check the .so exports all of them)
 ABI_SYMBOLS = [
@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "tdmpc2_plan_shard_begin", "tdmpc2_plan_shard_values", "tdmpc2_plan_shard_refit",
     "tdmpc2_plan_export_noise", "tdmpc2_plan_call_counter", "tdmpc2_plan_set_call_counter", "tdmpc2_plan_take_fault",
     "tdmpc2_plan_fault_info", "tdmpc2_plan_fault_word",
+    "tdmpc2_plan_bind_pixel_encoder", "tdmpc2_plan_encode_pix", "tdmpc2_plan_run_pix",
 ]
 
 NET_DYNAMICS, NET_REWARD, NET_PI, NET_Q, NET_TERMINATION, NET_TARGET_Q = range(6)
@@ -128,6 +129,12 @@ def _open(path):
     lib.tdmpc2_plan_encode.restype = i32
     lib.tdmpc2_plan_run_obs.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, C.POINTER(Noise), u64, vp, vp]
     lib.tdmpc2_plan_run_obs.restype = i32
+    lib.tdmpc2_plan_bind_pixel_encoder.argtypes = [vp, i32, vp, vp, i32, i32, i32, vp]
+    lib.tdmpc2_plan_bind_pixel_encoder.restype = i32
+    lib.tdmpc2_plan_encode_pix.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
+    lib.tdmpc2_plan_encode_pix.restype = i32
+    lib.tdmpc2_plan_run_pix.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, C.POINTER(Noise), u64, vp, vp]
+    lib.tdmpc2_plan_run_pix.restype = i32
     lib.tdmpc2_plan_policy_value.argtypes = [vp, i32, vp, i32, i32, vp, vp, u64, vp, vp, vp]
     lib.tdmpc2_plan_policy_value.restype = i32
     lib.tdmpc2_plan_td_target.argtypes = [vp, i32, vp, vp, vp, C.c_float, vp, vp, u64, vp, vp]
@@ -370,6 +377,73 @@ class NativePlanner:
         with torch.cuda.device(dev):
             self._check(self.lib.tdmpc2_plan_run_obs(self._h, E, _ptr(obs), self.obs_dim, _ptr(task_emb), _ptr(act_mask),
                                                      _ptr(disc_pow), _ptr(prev_mean), _ptr(t0), int(bool(eval_mode)), noise_p,
+                                                     C.c_uint64(int(seed) & (2**64 - 1)), _ptr(action), self._stream()))
+        return action
+
+    # ------------------------------------------------------------------ pixel observations (ABI 10)
+    @staticmethod
+    def draw_shift(E: int, device) -> torch.Tensor:
+        """ShiftAug's draw (tdmpc2/common/layers.py:52, tdmpc2_amd.layers.ShiftAug): the same torch.randint call, so the
+        generator advances exactly as the reference's encoder advances it; returned as int32 [E, 2] = (dx, dy)."""
+        s = torch.randint(0, 7, size=(int(E), 1, 1, 2), device=device, dtype=torch.float32)
+        return s.view(int(E), 2).to(torch.int32)
+
+    def bind_pixel_encoder(self, sd: Dict[str, torch.Tensor], prefix: str = "_encoder.rgb"):
+        """Bind the pixel encoder (tdmpc2/common/layers.py:136-150) from checkpoint keys `_encoder.rgb.{2,4,6,8}.{weight,bias}`;
+        afterwards `encode_pix` / `plan_pix` run it in HIP.  Not part of the packed blob: bind again after `import_packed`."""
+        with torch.cuda.device(self.device):
+            keep = []
+            for layer, idx in enumerate((2, 4, 6, 8)):
+                W = sd[f"{prefix}.{idx}.weight"].detach().to(self.device, torch.float32).contiguous()
+                b = sd[f"{prefix}.{idx}.bias"].detach().to(self.device, torch.float32).contiguous()
+                keep += [W, b]
+                if W.dim() != 4 or W.shape[2] != W.shape[3]:
+                    raise ValueError(f"{prefix}.{idx}.weight: expected a square Conv2d kernel, got {tuple(W.shape)}")
+                self._check(self.lib.tdmpc2_plan_bind_pixel_encoder(self._h, layer, _ptr(W), _ptr(b), int(W.shape[0]),
+                                                                    int(W.shape[1]), int(W.shape[2]), self._stream()))
+            torch.cuda.current_stream(self.device).synchronize()  # sources may now be freed
+        self.pix_channels = int(sd[f"{prefix}.2.weight"].shape[1])
+
+    def _pix_inputs(self, obs, shift):
+        dev = self.device
+        if getattr(self, "pix_channels", None) is None:
+            raise NativeError("no pixel encoder bound (bind_pixel_encoder)")
+        E = int(obs.shape[0])
+        if obs.dtype not in (torch.uint8, torch.float32):
+            raise ValueError(f"obs: expected dtype torch.uint8 or torch.float32, got {obs.dtype}")
+        _chk_tensor("obs", obs, obs.dtype, (E, self.pix_channels, 64, 64), dev)
+        _chk_tensor("shift", shift, torch.int32, (E, 2), dev)
+        return E, 0 if obs.dtype == torch.uint8 else 1
+
+    def encode_pix(self, obs, shift, out: Optional[torch.Tensor] = None):
+        """WorldModel.encode for rgb observations: obs [E, Cin, 64, 64] (uint8 or fp32 pixel levels), shift int32 [E, 2]
+        (`draw_shift`) -> z [E, L]."""
+        E, dt = self._pix_inputs(obs, shift)
+        z = out if out is not None else torch.empty(E, self.cfg.latent_dim, device=self.device, dtype=torch.float32)
+        _chk_tensor("z", z, torch.float32, (E, self.cfg.latent_dim), self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.tdmpc2_plan_encode_pix(self._h, E, _ptr(obs), dt, self.pix_channels, _ptr(shift), _ptr(z),
+                                                        self._stream()))
+        return z
+
+    def plan_pix(self, obs, shift, disc_pow, prev_mean, t0, eval_mode=False, tape: Optional[Dict[str, torch.Tensor]] = None,
+                 seed: int = 0, out: Optional[torch.Tensor] = None):
+        """TDMPC2._plan from the frame stack on: encode_pix + plan in one library call (single-task models)."""
+        cfg, dev = self.cfg, self.device
+        E, dt = self._pix_inputs(obs, shift)
+        H, A = cfg.horizon, cfg.action_dim
+        _chk_tensor("disc_pow", disc_pow, torch.float32, (E, H + 1), dev)
+        _chk_tensor("prev_mean", prev_mean, torch.float32, (E, H, A), dev)
+        _chk_tensor("t0", t0, torch.uint8, (E,), dev)
+        action = out if out is not None else torch.empty(E, A, device=dev, dtype=torch.float32)
+        _chk_tensor("action", action, torch.float32, (E, A), dev)
+        noise_p = None
+        if tape is not None:
+            noise = self._noise(tape, E)
+            noise_p = C.byref(noise)
+        with torch.cuda.device(dev):
+            self._check(self.lib.tdmpc2_plan_run_pix(self._h, E, _ptr(obs), dt, self.pix_channels, _ptr(shift), _ptr(disc_pow),
+                                                     _ptr(prev_mean), _ptr(t0), int(bool(eval_mode)), noise_p,
                                                      C.c_uint64(int(seed) & (2**64 - 1)), _ptr(action), self._stream()))
         return action
 

@@ -48,6 +48,11 @@ class TDMPC2(torch.nn.Module):
         self._prev_mean = torch.nn.Buffer(torch.zeros(cfg.horizon, cfg.action_dim, device=self.device))
         self.max_envs = int(max_envs)
         self.native_encoder = True  # False: encode with the PyTorch-ROCm module (the parity tests compare both)
+        # True: rgb observations are encoded inside the library too (tdmpc2_plan_run_pix); off by default -- the PyTorch-ROCm
+        # conv module encodes them and the planner is handed the latent
+        self.native_pixel_encoder = False
+        self._pix_shift = None      # ShiftAug's shifts of the last native pixel plan (a re-planned step reuses them)
+        self._reuse_shift = False
         self._planner: Optional[NativePlanner] = None
         self._planner_log_std = None
         self._prev_mean_batch = None
@@ -95,10 +100,16 @@ class TDMPC2(torch.nn.Module):
     def _bind_encoder(self):
         # state observations: WorldModel.encode runs inside the library as well (include/tdmpc2_plan.h,
         # tdmpc2_plan_run_obs); pixel observations are encoded by the PyTorch-ROCm conv module (layers.conv) and enter
-        # the library as latents (tdmpc2_plan_run)
+        # the library as latents (tdmpc2_plan_run), or -- native_pixel_encoder -- inside the library (tdmpc2_plan_run_pix)
         if self.native_encoder and self.cfg.obs == "state":
             sd = {k: v for k, v in self.model.state_dict().items() if torch.is_tensor(v) and k.startswith("_encoder.state.")}
             self._planner.bind_encoder(sd)
+        if self.native_pixel_encoder and self.cfg.obs == "rgb":
+            self._bind_pixel_encoder()
+
+    def _bind_pixel_encoder(self):
+        sd = {k: v for k, v in self.model.state_dict().items() if torch.is_tensor(v) and k.startswith("_encoder.rgb.")}
+        self._planner.bind_pixel_encoder(sd)
 
     def sync_planner_weights(self):
         """Re-pack the model's current weights into the planner (after load / a training step)."""
@@ -142,7 +153,12 @@ class TDMPC2(torch.nn.Module):
             if self._planner is not None and self._planner.take_fault():
                 # a cluster hand-over of THIS plan gave up (another process / kernel held the compute units): the library
                 # returned NaN and left _prev_mean alone; it has switched to the path without hand-overs -- plan again
-                a = self.plan(obs, t0=t0, eval_mode=eval_mode, task=task).cpu()
+                # (the native pixel route with the same ShiftAug shifts: the step is re-planned, not re-drawn)
+                self._reuse_shift = True
+                try:
+                    a = self.plan(obs, t0=t0, eval_mode=eval_mode, task=task).cpu()
+                finally:
+                    self._reuse_shift = False
             return a
         z = self.model.encode(obs, task)
         action, info = self.model.pi(z, task)
@@ -157,6 +173,8 @@ class TDMPC2(torch.nn.Module):
         prev = self._prev_mean.view(1, *self._prev_mean.shape)
         if self.native_encoder and self.cfg.obs == "state":
             return self._plan_obs(obs.to(torch.float32).contiguous(), t0, eval_mode, task, prev)[0]
+        if self._native_pix():
+            return self._plan_pix(obs, t0, eval_mode, prev)[0]
         z = self.model.encode(obs, task)  # PyTorch-ROCm encoder (pixels, or native_encoder = False)
         return self._plan_latent(z.contiguous(), t0, eval_mode, task, prev)[0]
 
@@ -175,6 +193,8 @@ class TDMPC2(torch.nn.Module):
             t0 = torch.as_tensor(t0, device=self.device).to(torch.uint8)
         if self.native_encoder and self.cfg.obs == "state":
             return self._plan_obs(obs.to(torch.float32).contiguous(), t0, eval_mode, tasks, self._prev_mean_batch)
+        if self._native_pix():
+            return self._plan_pix(obs, t0, eval_mode, self._prev_mean_batch)
         if self.cfg.multitask:
             emb = self.model._task_emb(tasks)  # max_norm renorm happens inside the lookup
             z = self.model._encoder[self.cfg.obs](torch.cat([obs, emb], dim=-1))
@@ -186,7 +206,11 @@ class TDMPC2(torch.nn.Module):
     def act_batch(self, obs, t0, eval_mode=False, tasks=None):
         a = self.plan_batch(obs, t0, eval_mode, tasks).cpu()
         if self._planner is not None and self._planner.take_fault():  # see act()
-            a = self.plan_batch(obs, t0, eval_mode, tasks).cpu()
+            self._reuse_shift = True
+            try:
+                a = self.plan_batch(obs, t0, eval_mode, tasks).cpu()
+            finally:
+                self._reuse_shift = False
         return a
 
     def _plan_inputs(self, E, tasks):
@@ -208,6 +232,24 @@ class TDMPC2(torch.nn.Module):
         planner, emb, mask, disc = self._plan_inputs(obs.shape[0], tasks)
         return planner.plan_obs(obs, disc, prev_mean, t0, eval_mode=eval_mode, task_emb=emb, act_mask=mask,
                                 tape=self.noise_tape, seed=self._seed)
+
+    def _native_pix(self) -> bool:
+        return self.native_pixel_encoder and self.cfg.obs == "rgb"
+
+    def _plan_pix(self, obs, t0, eval_mode, prev_mean):
+        """ShiftAug's draw on the host framework's generator (as the conv module would draw it), then encode + plan inside the
+        library (tdmpc2_plan_run_pix).  A re-planned step (act after a reported fault) reuses the step's shifts."""
+        E = obs.shape[0]
+        if obs.dtype not in (torch.uint8, torch.float32):
+            obs = obs.to(torch.float32)
+        obs = obs.contiguous()
+        planner, _, _, disc = self._plan_inputs(E, None)
+        if planner.__dict__.get("pix_channels") is None:  # flag set after the handle was made
+            self._bind_pixel_encoder()
+        if not (self._reuse_shift and self._pix_shift is not None and self._pix_shift.shape[0] == E):
+            self._pix_shift = planner.draw_shift(E, self.device)
+        return planner.plan_pix(obs, self._pix_shift, disc, prev_mean, t0, eval_mode=eval_mode, tape=self.noise_tape,
+                                seed=self._seed)
 
     def _plan_latent(self, z, t0, eval_mode, tasks, prev_mean):
         planner, emb, mask, disc = self._plan_inputs(z.shape[0], tasks)
