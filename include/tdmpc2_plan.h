@@ -20,6 +20,9 @@
  *   tdmpc2_plan_bind_pixel_encoder <- the pixel encoder's parameters    tdmpc2/common/layers.py:136-150
  *   tdmpc2_plan_encode_pix    <- WorldModel.encode (rgb observations)   tdmpc2/common/layers.py:36-71,136-150
  *   tdmpc2_plan_run_pix       <- TDMPC2._plan including encode(), rgb   tdmpc2/tdmpc2.py:152-206
+ *   tdmpc2_plan_bind_policy   <- the policy prior's parameters (_pi)    tdmpc2/common/world_model.py:32
+ *   tdmpc2_plan_pi            <- WorldModel.pi                          tdmpc2/common/world_model.py:144-184
+ *   tdmpc2_plan_act_pi[_pix]  <- TDMPC2.act with cfg.mpc == False       tdmpc2/tdmpc2.py:114-120
  *   tdmpc2_plan_td_target[_mt]    <- TDMPC2._td_target                  tdmpc2/tdmpc2.py:239-254
  *   tdmpc2_plan_policy_value[_mt] <- forward half of TDMPC2.update_pi   tdmpc2/tdmpc2.py:208-225
  *   tdmpc2_plan_export_packed / import_packed <- TDMPC2.save / load of the planner's weights  tdmpc2/tdmpc2.py:72-95
@@ -58,7 +61,7 @@
 extern "C" {
 #endif
 
-#define TDMPC2_PLAN_ABI_VERSION 10
+#define TDMPC2_PLAN_ABI_VERSION 11
 
 typedef struct tdmpc2_plan tdmpc2_plan_t;
 
@@ -251,6 +254,40 @@ int tdmpc2_plan_run_pix(tdmpc2_plan_t *h, int n_envs, const void *obs, int obs_d
                         const float *disc_pow, float *prev_mean, const uint8_t *t0, int eval_mode, const tdmpc2_noise *tape,
                         uint64_t seed, float *action, void *stream);
 
+/* Policy prior (ABI 11): WorldModel.pi (tdmpc2/common/world_model.py:144-184, common/math.py:12-29) and TDMPC2.act's branch
+ * without planning (tdmpc2/tdmpc2.py:114-120), plain fp32.  bind_policy takes _pi.{layer}: layer 0 [M, L + T] and 1 [M, M]
+ * with their LayerNorm (ln_g / ln_b), layer 2 [2A, M] without (ln_g / ln_b ignored); DEVICE pointers, copied transposed into an
+ * fp32 [in][out] copy of its own -- separate from tdmpc2_plan_bind_weights(TDMPC2_NET_PI), whose MFMA layouts a GEMV cannot read,
+ * so that only handles which use the policy prior pay for it (2 MB on the 5M model, 90 MB on the 317M model).  The first call
+ * allocates every buffer the policy prior uses; pi / act_pi / act_pi_pix allocate nothing and never synchronise the host (they
+ * can be captured in a hipGraph).  Not part of the packed blob: re-bind after import_packed.
+ *   z [n, L]; task_emb [n, T] and act_mask [n, A] (multitask handles: both required; per row, action_dims = act_mask.sum(-1) per
+ *   row); eps [n, A] the normal draws of torch.randn_like, or NULL: drawn in the kernel from Philox(seed, call counter, row,
+ *   action index) -- every call advances the call counter by exactly one.  eval_mode: out->action = info["mean"].
+ * Routes (TDMPC2_TUNE_POLICY_ROUTE, tdmpc2_amd/csrc/policy_route.h): the row route runs one workgroup per row and the whole chain
+ * in one launch -- acting with an encoder no wider than 1024, the encoder too; the spread route one launch per layer (GEMVs that
+ * read each weight once per 8 rows, a LayerNorm + Mish row kernel, the head), chunks of at most max_envs rows.  Refusals: nothing
+ * bound -- TDMPC2_ERR_STATE; a layer shape other than (L + T) -> M -> 2A, n_envs outside [1, max_envs] when acting, a null
+ * `out` or `out->action` -- TDMPC2_ERR_INVALID; act_pi_pix on a multitask handle -- TDMPC2_ERR_UNSUPPORTED. */
+typedef struct tdmpc2_policy_out {   /* device pointers; all but action may be NULL */
+    float *action;          /* [n, A]  tanh(mean + eps*exp(log_std)); eval_mode: info["mean"] */
+    float *mean;            /* [n, A]  info["mean"] (after tanh, masked) */
+    float *log_std;         /* [n, A]  info["log_std"] (masked) */
+    float *entropy;         /* [n]     info["entropy"] */
+    float *scaled_entropy;  /* [n]     info["scaled_entropy"] */
+    float *eps_out;         /* [n, A]  the normal draws used (before masking): passed back as eps they replay the call */
+} tdmpc2_policy_out;
+int tdmpc2_plan_bind_policy(tdmpc2_plan_t *h, int layer, const float *W, const float *b, const float *ln_g, const float *ln_b,
+                            int out_features, int in_features, void *stream);
+int tdmpc2_plan_pi(tdmpc2_plan_t *h, int n_rows, const float *z, const float *task_emb, const float *act_mask, const float *eps,
+                   uint64_t seed, const tdmpc2_policy_out *out, void *stream);
+/* act(): encode (tdmpc2_plan_bind_encoder) then pi, 1 <= n_envs <= max_envs; obs [n_envs, obs_dim]. */
+int tdmpc2_plan_act_pi(tdmpc2_plan_t *h, int n_envs, const float *obs, int obs_dim, const float *task_emb, const float *act_mask,
+                       const float *eps, int eval_mode, uint64_t seed, const tdmpc2_policy_out *out, void *stream);
+/* the same for rgb observations: encode_pix (its obs / obs_dtype / in_channels / shift) then pi; single-task handles only. */
+int tdmpc2_plan_act_pi_pix(tdmpc2_plan_t *h, int n_envs, const void *obs, int obs_dtype, int in_channels, const int32_t *shift,
+                           const float *eps, int eval_mode, uint64_t seed, const tdmpc2_policy_out *out, void *stream);
+
 /* Training-side consumers of the planner's layer code, forward only, no gradients.  Both kernel
  * families, single-task and multitask models.  The fused family takes any number of rows; the layered family at most
  * max_envs * num_samples rows per call (its activation workspace).  Multitask tables are (re)built inside the call and
@@ -389,10 +426,14 @@ int tdmpc2_plan_shard_refit(tdmpc2_plan_t *h, int n_envs, int iter, float *value
  * clock is only consulted from the 256th poll of a wait on).
  * keys TDMPC2_TUNE_EXPERT + tdmpc2_expert_knob (ABI 9): the measurement knobs of the layered family's tile choice -- thresholds between
  * kernels that compute the same values to fp32 round-off.  They were environment variables of the library until ABI 8; the library
- * now reads exactly the environment variables listed in INTEGRATION.md section C and nothing else.  value INT32_MIN = the default. */
+ * now reads exactly the environment variables listed in INTEGRATION.md section C and nothing else.  value INT32_MIN = the default.
+ * key TDMPC2_TUNE_POLICY_ROUTE (ABI 11): the route of tdmpc2_plan_pi / act_pi / act_pi_pix -- 0 (default) = auto (policy_route.h),
+ * 1 = the row route (where its LDS holds the widest layer), 2 = the spread route. */
 enum tdmpc2_tuning { TDMPC2_TUNE_ROWS_PER_WORKGROUP = 0, TDMPC2_TUNE_FOLD_REFIT = 1, TDMPC2_TUNE_CLUSTER = 2, TDMPC2_TUNE_FUSE_LN = 3,
                      TDMPC2_TUNE_REARM_AFTER = 4, TDMPC2_TUNE_SAFE_ONCE = 5, TDMPC2_TUNE_KSPLIT = 6, TDMPC2_TUNE_FEWROW = 7,
-                     TDMPC2_TUNE_WAIT_US = 8, TDMPC2_TUNE_EXPERT = 100 };
+                     TDMPC2_TUNE_WAIT_US = 8,
+                     TDMPC2_TUNE_POLICY_ROUTE = TDMPC2_TUNE_WAIT_US + 1, /* = 9 (tests/test_host_logic.py pins ABI 10's literal keys) */
+                     TDMPC2_TUNE_EXPERT = 100 };
 /* (what each knob decides, its default and the values it accepts -- anything else: TDMPC2_ERR_INVALID: tdmpc2_amd/csrc/layer_route.h) */
 enum tdmpc2_expert_knob { TDMPC2_X_GEMM_W256_MIN = 0, TDMPC2_X_GEMM_W_SPLIT_MIN, TDMPC2_X_GEMM_W_SPLIT_MAX, TDMPC2_X_GEMM_W_SPLIT_OVH,
                           TDMPC2_X_KSPLIT_AUTO_LO, TDMPC2_X_KSPLIT_AUTO_MIN, TDMPC2_X_GEMM_W_XCD_ROWS, TDMPC2_X_GEMM_NCT1,

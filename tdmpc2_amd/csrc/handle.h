@@ -170,6 +170,14 @@ struct tdmpc2_plan {
         void *tab = nullptr;  // PixTap [7][64]: ShiftAug's resampling table (pixel_route.h)
         float *ws = nullptr;  // [max_envs][pix_ws_floats(C)] layer outputs of the spread route
     } pix;
+    // policy prior (optional: bound with tdmpc2_plan_bind_policy; policy_kernels.cuh, policy_route.h)
+    struct Pol {
+        float *wt[3] = {nullptr, nullptr, nullptr}, *bias[3] = {nullptr, nullptr, nullptr};  // _pi.{0,1,2}: [in][out], [out]
+        float *g[2] = {nullptr, nullptr}, *b[2] = {nullptr, nullptr};                        // LayerNorm of layers 0, 1
+        bool bound[3] = {false, false, false};
+        float *x = nullptr, *y = nullptr;  // spread-route workspace: [max_envs][M] activations, [max_envs][max(M, 2A)] pre-activations
+        int mode = 0;                      // TDMPC2_TUNE_POLICY_ROUTE: 0 auto, 1 row route, 2 spread route
+    } pol;
     unsigned int call = 0;
     unsigned long long *timing = nullptr;  // TDMPC2_TIMING=1 with a -DSPLIT_TIMING build: in-kernel phase cycle counters
     // profiling

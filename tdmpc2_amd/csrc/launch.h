@@ -2,6 +2,42 @@
 // in exactly one translation unit; everything else reaches it through these functions / tables.
 #pragma once
 #include "handle.h"
+#include "policy_route.h"
+
+// ---- policy prior (k_policy.hip: policy_kernels.cuh, routes in policy_route.h)
+struct PolLayerDev {
+    const float *wt, *bias, *g, *b;  // [in][out] weights, bias, LayerNorm affine (g / b unused by the output layer)
+    int in, out;
+};
+struct PolHeadArgs {
+    int A, row0, eval_mode;   // row0: row index of this launch's first row in the call (Philox key)
+    float lmin, ldif;         // log_std_min, log_std_dif
+    const float *mask, *eps;  // [n, A] each, or null (single-task / in-kernel draws)
+    unsigned long long seed;
+    unsigned call;
+    float *action, *mean, *log_std, *entropy, *scaled_entropy, *eps_out;  // all but action may be null
+};
+struct PolRowParams {
+    PolLayerDev enc[6];  // acting: the encoder's layers (enc_nl > 0), else z is the input
+    int enc_nl, obs_dim;
+    const float *obs;    // [n, obs_dim]
+    const float *z;      // [n, L] (enc_nl == 0)
+    const float *task_emb;  // [n, T] or null
+    int L, T, maxw, simnorm_dim;
+    PolLayerDev pi[3];
+    PolHeadArgs head;
+};
+struct PolGemvParams {
+    const float *wt, *bias;  // [in][out], [out]
+    const float *x;          // [n, ldx] activations, or null: layer 0 reads z [n, L] | emb [n, T]
+    const float *z, *emb;
+    int ldx, L, T, in, out, n;
+    float *y;                // [n, out]
+};
+struct PolHeadParams {
+    const float *y;  // [n, 2A] output-layer pre-activations
+    PolHeadArgs head;
+};
 
 namespace tdk {
 
@@ -56,5 +92,11 @@ int lay_sample_iteration(tdmpc2_plan *h, hipStream_t st, int E, int iter, const 
 // the two Q heads of a single evaluation (td_target / estimate_value entry points): copied from `qidx` ([E, 2], row stride
 // `stride`) or drawn (Philox) when it is null
 int lay_set_qidx(tdmpc2_plan *h, hipStream_t st, int E, const int *qidx, long stride, int nq, int iter, uint64_t seed, unsigned call, int *dst);
+
+// ---- policy prior (k_policy.hip)
+int pol_set_lds();  // the GEMV instantiations' dynamic LDS limit (once per handle, at bind)
+int pol_launch_row(const PolRowParams &p, const PolGrid &g, hipStream_t st);
+int pol_launch_gemv(const PolGemvParams &p, const PolGrid &g, hipStream_t st);
+int pol_launch_head(const PolHeadParams &p, const PolGrid &g, hipStream_t st);
 
 }  // namespace tdk

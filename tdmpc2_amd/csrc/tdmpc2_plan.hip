@@ -18,6 +18,7 @@
 //   layered_kernels.cuh, layered_split.cuh, layered_host.cuh
 //                        layer-at-a-time family for every other model size and for episodic planning
 //   encoder_kernels.cuh  WorldModel.encode for state observations (world_model.py:103-112)
+// The policy prior's kernels (WorldModel.pi, act() with mpc = False) are in k_policy.hip; its host side is here.
 // Weights are re-packed once (bind) into MFMA fragment order so that a wave's global_load_dwordx4 reads 1 KiB
 // contiguous; one small workgroup per plan does nan_to_num + top-k + score + mean/std refit (+ the final Gumbel pick)
 // between rollout launches (k_refit below).  DESIGN.md has the full account.
@@ -1439,6 +1440,175 @@ int tdmpc2_plan_run_pix(tdmpc2_plan_t *h, int n_envs, const void *obs, int obs_d
     return run_impl(h, n_envs, h->zenc, nullptr, nullptr, disc_pow, prev_mean, t0, eval_mode, tape, seed, action, nullptr, stream);
 }
 
+// ================================================================ policy prior (k_policy.hip: policy_kernels.cuh, policy_route.h)
+int tdmpc2_plan_bind_policy(tdmpc2_plan_t *h, int layer, const float *W, const float *b, const float *ln_g, const float *ln_b,
+                            int out_features, int in_features, void *stream) {
+    if (!h || !W || !b) return fail(TDMPC2_ERR_INVALID, "null argument");
+    if (layer < 0 || layer > 2) return fail(TDMPC2_ERR_INVALID, "policy layer %d outside [0, 2]", layer);
+    const tdmpc2_plan_cfg &c = h->cfg;
+    const int in0 = c.latent_dim + c.task_dim, M = c.mlp_dim, A = c.action_dim;
+    const int want_in = layer == 0 ? in0 : M, want_out = layer == 2 ? 2 * A : M;
+    if (in_features != want_in || out_features != want_out)
+        return fail(TDMPC2_ERR_INVALID, "policy layer %d: got [%d, %d], expected [%d, %d] (latent_dim + task_dim -> mlp_dim -> 2 action_dim)",
+                    layer, out_features, in_features, want_out, want_in);
+    if (layer < 2 && (!ln_g || !ln_b)) return fail(TDMPC2_ERR_INVALID, "policy layer %d needs its LayerNorm parameters", layer);
+    if (M > POL_MAX_WIDTH || in0 > POL_MAX_WIDTH)
+        return fail(TDMPC2_ERR_UNSUPPORTED, "policy prior: widths %d / %d beyond %d", in0, M, POL_MAX_WIDTH);
+    ENTER_ON(h, stream);
+    tdmpc2_plan::Pol &P = h->pol;
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if (!P.x) {  // every buffer of the policy prior, once: pi / act_pi never allocate
+        for (int l = 0; l < 3; ++l) {
+            const int li = l == 0 ? in0 : M, lo = l == 2 ? 2 * A : M;
+            if ((rc = dev_alloc(h, (void **)&P.wt[l], (size_t)li * lo * 4))) return rc;
+            if ((rc = dev_alloc(h, (void **)&P.bias[l], (size_t)lo * 4))) return rc;
+            if (l < 2 && (rc = dev_alloc(h, (void **)&P.g[l], (size_t)lo * 4))) return rc;
+            if (l < 2 && (rc = dev_alloc(h, (void **)&P.b[l], (size_t)lo * 4))) return rc;
+        }
+        if ((rc = dev_alloc(h, (void **)&P.y, pol_ws_y_floats(c.max_envs, M, A) * 4))) return rc;
+        if (!h->zenc && (rc = dev_alloc(h, (void **)&h->zenc, (size_t)c.max_envs * c.latent_dim * 4))) return rc;
+        if ((rc = tdk::pol_set_lds())) return rc;
+        if ((rc = dev_alloc(h, (void **)&P.x, pol_ws_x_floats(c.max_envs, M) * 4))) return rc;  // last: marks the set complete
+    }
+    const size_t n = (size_t)in_features * out_features;
+    hipLaunchKernelGGL(k_transpose, dim3((unsigned)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, st, W, P.wt[layer], out_features, in_features);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(P.bias[layer], b, (size_t)out_features * 4, hipMemcpyDeviceToDevice, st));
+    if (layer < 2) {
+        HIP_TRY(hipMemcpyAsync(P.g[layer], ln_g, (size_t)out_features * 4, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(P.b[layer], ln_b, (size_t)out_features * 4, hipMemcpyDeviceToDevice, st));
+    }
+    P.bound[layer] = true;
+    return TDMPC2_OK;
+}
+
+namespace {
+int check_pol_call(tdmpc2_plan *h, const float *task_emb, const float *act_mask, const tdmpc2_policy_out *out) {
+    if (!out || !out->action) return fail(TDMPC2_ERR_INVALID, "null policy output (out / out->action)");
+    for (int l = 0; l < 3; ++l)
+        if (!h->pol.bound[l]) return fail(TDMPC2_ERR_STATE, "policy layer %d is not bound (tdmpc2_plan_bind_policy)", l);
+    if (h->cfg.multitask && (!task_emb || !act_mask)) return fail(TDMPC2_ERR_INVALID, "a multitask policy prior needs task_emb and act_mask");
+    return 0;
+}
+
+// the state encoder as row-route layers (acting), with launch_encode's checks; maxw = its widest layer
+int pol_enc_chain(tdmpc2_plan *h, int obs_dim, PolRowParams &p, int &maxw) {
+    if (!h->enc_layers) return fail(TDMPC2_ERR_STATE, "no encoder bound (tdmpc2_plan_bind_encoder)");
+    maxw = 0;
+    for (int l = 0; l < h->enc_layers; ++l) {
+        const tdmpc2_plan::Enc &L = h->enc[l];
+        if (!L.bound) return fail(TDMPC2_ERR_STATE, "encoder layer %d of %d is not bound", l, h->enc_layers);
+        const int exp_in = l == 0 ? obs_dim + h->cfg.task_dim : h->enc[l - 1].out;
+        if (L.in != exp_in) return fail(TDMPC2_ERR_INVALID, "encoder layer %d takes %d inputs, the data brings %d", l, L.in, exp_in);
+        p.enc[l] = PolLayerDev{L.wt, L.bias, L.g, L.b, L.in, L.out};
+        maxw = std::max(maxw, std::max(L.in, L.out));
+    }
+    p.enc_nl = h->enc_layers;
+    p.obs_dim = obs_dim;
+    return 0;
+}
+
+// WorldModel.pi of n rows.  obs != null: the rows are observations and the encoder runs first -- inside the row-route launch when
+// it is narrow enough for k_encode's own one-launch route, else through launch_encode into h->zenc.
+int launch_pi(tdmpc2_plan *h, int n, const float *z, const float *obs, int obs_dim, const float *emb, const float *mask,
+              const float *eps, uint64_t seed, int eval_mode, const tdmpc2_policy_out *out, hipStream_t st) {
+    const tdmpc2_plan_cfg &c = h->cfg;
+    const tdmpc2_plan::Pol &P = h->pol;
+    const int L = c.latent_dim, T = c.task_dim, M = c.mlp_dim, A = c.action_dim, in0 = L + T;
+    PolRowParams rp{};
+    int maxw = std::max(in0, std::max(M, 2 * A)), rc;
+    if (obs) {
+        int enc_w = 0;
+        if ((rc = pol_enc_chain(h, obs_dim, rp, enc_w))) return rc;
+        const PolRoute r = pol_route(n, in0, M, A, std::max(maxw, enc_w), P.mode);
+        if (enc_w <= ENC_WIDE && r.kind == POL_ROW) {
+            maxw = std::max(maxw, enc_w);
+            rp.obs = obs;
+        } else {  // the encoder's own route, unchanged, then the policy from its latents
+            if ((rc = launch_encode(h, n, obs, obs_dim, emb, h->zenc, st))) return rc;
+            rp.enc_nl = 0;
+            z = h->zenc;
+        }
+    }
+    PolHeadArgs hd{};
+    hd.A = A; hd.eval_mode = eval_mode; hd.lmin = c.log_std_min; hd.ldif = c.log_std_dif;
+    hd.seed = seed; hd.call = h->call++;  // exactly one per call
+    auto at = [](float *p, size_t off) { return p ? p + off : nullptr; };
+    auto cat = [](const float *p, size_t off) { return p ? p + off : nullptr; };
+    const PolRoute r = pol_route(n, in0, M, A, maxw, P.mode);
+    if (r.kind == POL_ROW) {
+        rp.z = z; rp.task_emb = emb;
+        rp.L = L; rp.T = T; rp.maxw = maxw; rp.simnorm_dim = c.simnorm_dim;
+        for (int l = 0; l < 3; ++l) rp.pi[l] = PolLayerDev{P.wt[l], P.bias[l], l < 2 ? P.g[l] : nullptr, l < 2 ? P.b[l] : nullptr,
+                                                            l == 0 ? in0 : M, l == 2 ? 2 * A : M};
+        hd.row0 = 0; hd.mask = mask; hd.eps = eps;
+        hd.action = out->action; hd.mean = out->mean; hd.log_std = out->log_std; hd.entropy = out->entropy;
+        hd.scaled_entropy = out->scaled_entropy; hd.eps_out = out->eps_out;
+        rp.head = hd;
+        return tdk::pol_launch_row(rp, r.g[0], st);
+    }
+    for (int r0 = 0; r0 < n; r0 += c.max_envs) {  // the spread route: chunks of at most max_envs rows (the workspace)
+        const int m = std::min(c.max_envs, n - r0);
+        const PolRoute rc_ = pol_route(m, in0, M, A, maxw, POL_FORCE_SPREAD);
+        const size_t ra = (size_t)r0 * A;
+        for (int l = 0; l < 3; ++l) {
+            PolGemvParams g{};
+            g.wt = P.wt[l]; g.bias = P.bias[l]; g.in = l == 0 ? in0 : M; g.out = l == 2 ? 2 * A : M; g.n = m; g.y = P.y;
+            if (l == 0) { g.z = z + (size_t)r0 * L; g.emb = cat(emb, (size_t)r0 * T); g.L = L; g.T = T; }
+            else { g.x = P.x; g.ldx = M; }
+            if ((rc = tdk::pol_launch_gemv(g, rc_.g[2 * l], st))) return rc;
+            if (l == 2) break;
+            EncNormParams nm{};
+            nm.y = P.y; nm.g = P.g[l]; nm.b = P.b[l]; nm.out = P.x; nm.width = M; nm.last = 0; nm.simnorm_dim = c.simnorm_dim;
+            const PolGrid &ng = rc_.g[2 * l + 1];
+            hipLaunchKernelGGL(k_enc_norm, dim3(ng.x), dim3(ng.threads), 0, st, nm);
+            HIP_TRY(hipGetLastError());
+        }
+        PolHeadParams hp{};
+        hp.y = P.y;
+        hp.head = hd;
+        hp.head.row0 = r0; hp.head.mask = cat(mask, ra); hp.head.eps = cat(eps, ra);
+        hp.head.action = at(out->action, ra); hp.head.mean = at(out->mean, ra); hp.head.log_std = at(out->log_std, ra);
+        hp.head.entropy = at(out->entropy, r0); hp.head.scaled_entropy = at(out->scaled_entropy, r0); hp.head.eps_out = at(out->eps_out, ra);
+        if ((rc = tdk::pol_launch_head(hp, rc_.g[5], st))) return rc;
+    }
+    return 0;
+}
+}  // namespace
+
+int tdmpc2_plan_pi(tdmpc2_plan_t *h, int n_rows, const float *z, const float *task_emb, const float *act_mask, const float *eps,
+                   uint64_t seed, const tdmpc2_policy_out *out, void *stream) {
+    if (!h || !z) return fail(TDMPC2_ERR_INVALID, "null argument");
+    if (n_rows < 1) return fail(TDMPC2_ERR_INVALID, "n_rows %d < 1", n_rows);
+    int rc = check_pol_call(h, task_emb, act_mask, out);
+    if (rc) return rc;
+    ENTER_ON(h, stream);
+    return launch_pi(h, n_rows, z, nullptr, 0, task_emb, act_mask, eps, seed, 0, out, (hipStream_t)stream);
+}
+
+int tdmpc2_plan_act_pi(tdmpc2_plan_t *h, int n_envs, const float *obs, int obs_dim, const float *task_emb, const float *act_mask,
+                       const float *eps, int eval_mode, uint64_t seed, const tdmpc2_policy_out *out, void *stream) {
+    if (!h || !obs) return fail(TDMPC2_ERR_INVALID, "null argument");
+    if (n_envs < 1 || n_envs > h->cfg.max_envs) return fail(TDMPC2_ERR_INVALID, "n_envs %d outside [1, %d]", n_envs, h->cfg.max_envs);
+    int rc = check_pol_call(h, task_emb, act_mask, out);
+    if (rc) return rc;
+    ENTER_ON(h, stream);
+    return launch_pi(h, n_envs, nullptr, obs, obs_dim, task_emb, act_mask, eps, seed, eval_mode, out, (hipStream_t)stream);
+}
+
+int tdmpc2_plan_act_pi_pix(tdmpc2_plan_t *h, int n_envs, const void *obs, int obs_dtype, int in_channels, const int32_t *shift,
+                           const float *eps, int eval_mode, uint64_t seed, const tdmpc2_policy_out *out, void *stream) {
+    if (!h || !obs || !shift) return fail(TDMPC2_ERR_INVALID, "null argument");
+    if (h->cfg.multitask) return fail(TDMPC2_ERR_UNSUPPORTED, "the pixel encoder is single-task only (multitask handle)");
+    int rc = check_pix_call(h, n_envs, obs_dtype, in_channels);
+    if (rc) return rc;
+    if ((rc = check_pol_call(h, nullptr, nullptr, out))) return rc;
+    ENTER_ON(h, stream);
+    if ((rc = launch_encode_pix(h, n_envs, obs, obs_dtype, shift, h->zenc, (hipStream_t)stream))) return rc;
+    return launch_pi(h, n_envs, h->zenc, nullptr, 0, nullptr, nullptr, eps, seed, eval_mode, out, (hipStream_t)stream);
+}
+
 namespace {
 // per-task tables of a multitask value call: effective first-layer biases of pi and of the chosen Q ensemble, action
 // masks, discounts; (re)built on every call (the weights may have been re-bound), storage grown on demand
@@ -2009,6 +2179,12 @@ int tdmpc2_plan_set_tuning(tdmpc2_plan_t *h, int key, int value) {
     if (key == TDMPC2_TUNE_FEWROW) {
         if (value < 0 || value > 1) return fail(TDMPC2_ERR_INVALID, "fewrow must be 0 or 1");
         h->lay.mid = value != 0;
+        return TDMPC2_OK;
+    }
+    if (key == TDMPC2_TUNE_POLICY_ROUTE) {
+        if (value == INT32_MIN) value = POL_AUTO;
+        if (value < POL_AUTO || value > POL_FORCE_SPREAD) return fail(TDMPC2_ERR_INVALID, "policy route must be 0 (auto), 1 (row) or 2 (spread)");
+        h->pol.mode = value;
         return TDMPC2_OK;
     }
     if (key == TDMPC2_TUNE_FOLD_REFIT) {

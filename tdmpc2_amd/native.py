@@ -17,7 +17,7 @@ import torch
 _LIB_PATH = os.environ.get("TDMPC2_PLAN_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtdmpc2_plan.so")
 _lib = None
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 # every symbol include/tdmpc2_plan.h declares (tests check the .so exports all of them)
 ABI_SYMBOLS = [
@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "tdmpc2_plan_export_noise", "tdmpc2_plan_call_counter", "tdmpc2_plan_set_call_counter", "tdmpc2_plan_take_fault",
     "tdmpc2_plan_fault_info", "tdmpc2_plan_fault_word",
     "tdmpc2_plan_bind_pixel_encoder", "tdmpc2_plan_encode_pix", "tdmpc2_plan_run_pix",
+    "tdmpc2_plan_bind_policy", "tdmpc2_plan_pi", "tdmpc2_plan_act_pi", "tdmpc2_plan_act_pi_pix",
 ]
 
 NET_DYNAMICS, NET_REWARD, NET_PI, NET_Q, NET_TERMINATION, NET_TARGET_Q = range(6)
@@ -61,6 +62,16 @@ class TaskTables(C.Structure):
     """struct tdmpc2_task_tables: one task per row of a training batch + the per-task tables."""
     _fields_ = [("task_ids", C.c_void_p), ("task_emb", C.c_void_p), ("act_mask", C.c_void_p), ("discount", C.c_void_p),
                 ("n_tasks", C.c_int32)]
+
+
+class PolicyOut(C.Structure):
+    """struct tdmpc2_policy_out: device pointers, all but `action` optional."""
+    _fields_ = [("action", C.c_void_p), ("mean", C.c_void_p), ("log_std", C.c_void_p), ("entropy", C.c_void_p),
+                ("scaled_entropy", C.c_void_p), ("eps_out", C.c_void_p)]
+
+
+POLICY_ROUTE_AUTO, POLICY_ROUTE_ROW, POLICY_ROUTE_SPREAD = range(3)  # TDMPC2_TUNE_POLICY_ROUTE values
+TUNE_POLICY_ROUTE = 9
 
 
 class Debug(C.Structure):
@@ -135,6 +146,14 @@ def _open(path):
     lib.tdmpc2_plan_encode_pix.restype = i32
     lib.tdmpc2_plan_run_pix.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, C.POINTER(Noise), u64, vp, vp]
     lib.tdmpc2_plan_run_pix.restype = i32
+    lib.tdmpc2_plan_bind_policy.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, vp]
+    lib.tdmpc2_plan_bind_policy.restype = i32
+    lib.tdmpc2_plan_pi.argtypes = [vp, i32, vp, vp, vp, vp, u64, C.POINTER(PolicyOut), vp]
+    lib.tdmpc2_plan_pi.restype = i32
+    lib.tdmpc2_plan_act_pi.argtypes = [vp, i32, vp, i32, vp, vp, vp, i32, u64, C.POINTER(PolicyOut), vp]
+    lib.tdmpc2_plan_act_pi.restype = i32
+    lib.tdmpc2_plan_act_pi_pix.argtypes = [vp, i32, vp, i32, i32, vp, vp, i32, u64, C.POINTER(PolicyOut), vp]
+    lib.tdmpc2_plan_act_pi_pix.restype = i32
     lib.tdmpc2_plan_policy_value.argtypes = [vp, i32, vp, i32, i32, vp, vp, u64, vp, vp, vp]
     lib.tdmpc2_plan_policy_value.restype = i32
     lib.tdmpc2_plan_td_target.argtypes = [vp, i32, vp, vp, vp, C.c_float, vp, vp, u64, vp, vp]
@@ -259,6 +278,7 @@ class NativePlanner:
         self._shard_noise = None  # struct tdmpc2_noise of the sharded plan in progress (shard_begin .. shard_refit)
         self.encoder_layers = 0
         self.obs_dim = None
+        self.policy_bound = False
 
     # ------------------------------------------------------------------ plumbing
     def _check(self, rc: int):
@@ -446,6 +466,87 @@ class NativePlanner:
                                                      _ptr(prev_mean), _ptr(t0), int(bool(eval_mode)), noise_p,
                                                      C.c_uint64(int(seed) & (2**64 - 1)), _ptr(action), self._stream()))
         return action
+
+    # ------------------------------------------------------------------ policy prior (ABI 11)
+    def bind_policy(self, sd: Dict[str, torch.Tensor], prefix: str = "_pi"):
+        """Bind the policy prior's fp32 copy (`_pi.{0,1,2}.{weight,bias}`, `_pi.{0,1}.ln.{weight,bias}`) for `pi` / `act_pi` /
+        `act_pi_pix`.  Separate from `bind_state_dict` (whose policy copy is in the planner's MFMA layouts); not part of the
+        packed blob: bind again after `import_packed`."""
+        keep = []
+        with torch.cuda.device(self.device):
+            for layer in range(3):
+                ts = []
+                for name in ("weight", "bias", "ln.weight", "ln.bias"):
+                    k = f"{prefix}.{layer}.{name}"
+                    t = sd[k].detach().to(self.device, torch.float32).contiguous() if k in sd else None
+                    keep.append(t)
+                    ts.append(t)
+                W = ts[0]
+                self._check(self.lib.tdmpc2_plan_bind_policy(self._h, layer, _ptr(W), _ptr(ts[1]), _ptr(ts[2]), _ptr(ts[3]),
+                                                             int(W.shape[0]), int(W.shape[1]), self._stream()))
+            torch.cuda.current_stream(self.device).synchronize()  # sources may now be freed
+        self.policy_bound = True
+
+    def set_policy_route(self, mode: int):
+        """TDMPC2_TUNE_POLICY_ROUTE: 0 auto (default), 1 the row route, 2 the spread route."""
+        self._check(self.lib.tdmpc2_plan_set_tuning(self._h, TUNE_POLICY_ROUTE, int(mode)))
+
+    def _policy_io(self, n, task_emb, act_mask, eps, return_eps):
+        cfg, dev, A = self.cfg, self.device, self.cfg.action_dim
+        if cfg.multitask:
+            if task_emb is None or act_mask is None:
+                raise ValueError("a multitask policy prior needs task_emb and act_mask")
+            _chk_tensor("task_emb", task_emb, torch.float32, (n, cfg.task_dim), dev)
+            _chk_tensor("act_mask", act_mask, torch.float32, (n, A), dev)
+        else:
+            task_emb = act_mask = None
+        if eps is not None:
+            _chk_tensor("eps", eps, torch.float32, (n, A), dev)
+        f = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)  # noqa: E731
+        info = {"mean": f(n, A), "log_std": f(n, A), "action_prob": 1.0, "entropy": f(n, 1), "scaled_entropy": f(n, 1)}
+        if return_eps:
+            info["eps"] = f(n, A)
+        action = f(n, A)
+        out = PolicyOut(action=action.data_ptr(), mean=info["mean"].data_ptr(), log_std=info["log_std"].data_ptr(),
+                        entropy=info["entropy"].data_ptr(), scaled_entropy=info["scaled_entropy"].data_ptr(),
+                        eps_out=info["eps"].data_ptr() if return_eps else None)
+        return task_emb, act_mask, action, info, out
+
+    def pi(self, z, task_emb=None, act_mask=None, eps=None, seed: int = 0, return_eps: bool = False):
+        """WorldModel.pi (world_model.py:144-184) on z [n, L] -> (action [n, A], info) with the reference's info keys
+        ('mean', 'log_std', 'action_prob', 'entropy' [n, 1], 'scaled_entropy' [n, 1]).  Multitask: per-row task_emb [n, T] and
+        act_mask [n, A].  eps [n, A] (torch.randn_like's draws) or None: drawn in the kernel from Philox(seed, call counter);
+        return_eps adds info['eps'], the draws used (passed back as eps they replay the call bit for bit)."""
+        n = int(z.shape[0])
+        _chk_tensor("z", z, torch.float32, (n, self.cfg.latent_dim), self.device)
+        emb, mask, action, info, out = self._policy_io(n, task_emb, act_mask, eps, return_eps)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.tdmpc2_plan_pi(self._h, n, _ptr(z), _ptr(emb), _ptr(mask), _ptr(eps),
+                                                C.c_uint64(int(seed) & (2**64 - 1)), C.byref(out), self._stream()))
+        return action, info
+
+    def act_pi(self, obs, task_emb=None, act_mask=None, eps=None, eval_mode: bool = False, seed: int = 0,
+               return_eps: bool = False):
+        """TDMPC2.act with mpc = False (tdmpc2.py:114-120) for state observations: encode + pi in the library (the 5M model:
+        one launch).  eval_mode returns info['mean'] as the action."""
+        E = int(obs.shape[0])
+        _chk_tensor("obs", obs, torch.float32, (E, self.obs_dim), self.device)
+        emb, mask, action, info, out = self._policy_io(E, task_emb, act_mask, eps, return_eps)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.tdmpc2_plan_act_pi(self._h, E, _ptr(obs), int(self.obs_dim or 0), _ptr(emb), _ptr(mask), _ptr(eps),
+                                                    int(bool(eval_mode)), C.c_uint64(int(seed) & (2**64 - 1)), C.byref(out),
+                                                    self._stream()))
+        return action, info
+
+    def act_pi_pix(self, obs, shift, eps=None, eval_mode: bool = False, seed: int = 0, return_eps: bool = False):
+        """The same for rgb observations: encode_pix (obs, ShiftAug's `shift`: `draw_shift`) + pi (single-task models)."""
+        E, dt = self._pix_inputs(obs, shift)
+        _, _, action, info, out = self._policy_io(E, None, None, eps, return_eps)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.tdmpc2_plan_act_pi_pix(self._h, E, _ptr(obs), dt, self.pix_channels, _ptr(shift), _ptr(eps),
+                                                        int(bool(eval_mode)), C.c_uint64(int(seed) & (2**64 - 1)), C.byref(out),
+                                                        self._stream()))
+        return action, info
 
     def _noise(self, tape, E):
         shapes = self.noise_shapes(E)

@@ -52,6 +52,9 @@ class TDMPC2(torch.nn.Module):
         # conv module encodes them and the planner is handed the latent
         self.native_pixel_encoder = False
         self._pix_shift = None      # ShiftAug's shifts of the last native pixel plan (a re-planned step reuses them)
+        # True: act() with cfg.mpc == False (the policy prior, tdmpc2.py:114-120) runs inside the library too (tdmpc2_plan_act_pi /
+        # act_pi_pix / pi); off by default -- the PyTorch-ROCm modules encode and evaluate _pi
+        self.native_policy = False
         self._reuse_shift = False
         self._planner: Optional[NativePlanner] = None
         self._planner_log_std = None
@@ -111,6 +114,10 @@ class TDMPC2(torch.nn.Module):
         sd = {k: v for k, v in self.model.state_dict().items() if torch.is_tensor(v) and k.startswith("_encoder.rgb.")}
         self._planner.bind_pixel_encoder(sd)
 
+    def _bind_policy(self):
+        sd = {k: v for k, v in self.model.state_dict().items() if torch.is_tensor(v) and k.startswith("_pi.")}
+        self._planner.bind_policy(sd)
+
     def sync_planner_weights(self):
         """Re-pack the model's current weights into the planner (after load / a training step)."""
         if self._planner is not None and self._planner_log_std != self._log_std():
@@ -119,6 +126,8 @@ class TDMPC2(torch.nn.Module):
         if self._planner is not None:
             self._planner.bind_state_dict(self.model.planner_state_dict())
             self._bind_encoder()
+            if self._planner.policy_bound:
+                self._bind_policy()
 
     def _disc_pow(self, tasks):
         """discount^0..discount^H exactly as tdmpc2.py:126,130-132 accumulates it: python-float
@@ -160,6 +169,8 @@ class TDMPC2(torch.nn.Module):
                 finally:
                     self._reuse_shift = False
             return a
+        if self.native_policy:
+            return self._act_policy(obs, eval_mode, task)[0].cpu()
         z = self.model.encode(obs, task)
         action, info = self.model.pi(z, task)
         if eval_mode:
@@ -212,6 +223,75 @@ class TDMPC2(torch.nn.Module):
             finally:
                 self._reuse_shift = False
         return a
+
+    # ------------------------------------------------------------------ policy prior (act() with cfg.mpc == False)
+    @torch.no_grad()
+    def act_policy_batch(self, obs, eval_mode=False, tasks=None):
+        """act() without planning (tdmpc2.py:114-120) for E environments: obs [E, ...]; tasks int64 [E] or None -> action [E, A]
+        on the host.  The library route with `native_policy`, the PyTorch-ROCm modules otherwise."""
+        obs = obs.to(self.device)
+        tasks = torch.as_tensor(tasks, device=self.device).long() if self.cfg.multitask else None
+        if self.native_policy:
+            return self._act_policy(obs, eval_mode, tasks).cpu()
+        z = self.model.encode(obs, tasks)
+        action, info = self.model.pi(z, tasks)
+        return (info["mean"] if eval_mode else action).cpu()
+
+    def _act_policy(self, obs, eval_mode, tasks):
+        """The policy prior in the library.  eps is drawn with torch.randn on the host framework's generator -- the draw
+        WorldModel.pi's randn_like makes, after ShiftAug's for pixels -- so the RNG stream stays the reference's."""
+        E = obs.shape[0]
+        planner = self.planner()
+        if E > planner.max_envs:
+            raise ValueError(f"{E} environments exceed max_envs={planner.max_envs} given at construction")
+        if not planner.policy_bound:
+            self._bind_policy()
+        emb = mask = None
+        if self.cfg.multitask:
+            emb = self.model._task_emb(tasks.long()).to(torch.float32).contiguous()
+            mask = self.model._action_masks[tasks.long()].to(torch.float32).contiguous()
+        if self.native_encoder and self.cfg.obs == "state":
+            eps = torch.randn(E, self.cfg.action_dim, device=self.device)
+            a, _ = planner.act_pi(obs.to(torch.float32).contiguous(), task_emb=emb, act_mask=mask, eps=eps, eval_mode=eval_mode)
+            return a
+        if self._native_pix():
+            if planner.__dict__.get("pix_channels") is None:
+                self._bind_pixel_encoder()
+            if obs.dtype not in (torch.uint8, torch.float32):
+                obs = obs.to(torch.float32)
+            shift = planner.draw_shift(E, self.device)
+            eps = torch.randn(E, self.cfg.action_dim, device=self.device)
+            a, _ = planner.act_pi_pix(obs.contiguous(), shift, eps=eps, eval_mode=eval_mode)
+            return a
+        z = self.model.encode(obs, tasks).to(torch.float32).contiguous()
+        eps = torch.randn(E, self.cfg.action_dim, device=self.device)
+        a, info = planner.pi(z, task_emb=emb, act_mask=mask, eps=eps)
+        return info["mean"] if eval_mode else a
+
+    @torch.no_grad()
+    def policy(self, zs, task=None, eps=None):
+        """WorldModel.pi on a training batch in the library (the policy-prior counterpart of `policy_value`): zs [..., L], task
+        int64 [B] (broadcast over a leading horizon axis, as in update_pi) -> (action [..., A], info with the reference's keys).
+        eps [..., A] pins the noise; by default it is drawn inside the library.  Forward only: no gradients."""
+        lead = zs.shape[:-1]
+        z2 = zs.reshape(-1, zs.shape[-1]).to(self.device, torch.float32).contiguous()
+        planner = self.planner()
+        if not planner.policy_bound:
+            self._bind_policy()
+        emb = mask = None
+        if self.cfg.multitask:
+            task = torch.as_tensor(task, device=self.device)
+            if zs.dim() == 3 and task.numel() == zs.shape[1]:
+                task = task.repeat(zs.shape[0])
+            emb_t, mask_t, _ = self._task_tables()
+            task = task.long().reshape(-1)
+            emb, mask = emb_t[task].contiguous(), mask_t[task].contiguous()
+        if eps is not None:
+            eps = eps.reshape(-1, eps.shape[-1]).to(self.device, torch.float32).contiguous()
+        self._seed += 1
+        a, info = planner.pi(z2, task_emb=emb, act_mask=mask, eps=eps, seed=self._seed)
+        info = {k: (v.reshape(*lead, v.shape[-1]) if torch.is_tensor(v) else v) for k, v in info.items()}
+        return a.reshape(*lead, -1), info
 
     def _plan_inputs(self, E, tasks):
         planner = self.planner()

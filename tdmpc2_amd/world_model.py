@@ -129,7 +129,8 @@ class WorldModel(nn.Module):
         return self._reward(torch.cat([z, a], dim=-1))
 
     def pi(self, z, task):
-        """Returns (action, info) with info['mean'] like the reference (world_model.py:144-184)."""
+        """Returns (action, info) like the reference (world_model.py:144-184, math.py:12-29): info carries 'mean', 'log_std',
+        'action_prob', 'entropy' and 'scaled_entropy' (a dict; the reference's TensorDict has the same keys)."""
         if self.cfg.multitask:
             z = self.task_emb(z, task)
         mean, log_std = self._pi(z).chunk(2, dim=-1)
@@ -138,8 +139,17 @@ class WorldModel(nn.Module):
         if self.cfg.multitask:
             m = self._action_masks[task]
             mean, log_std, eps = mean * m, log_std * m, eps * m
+            action_dims = self._action_masks.sum(-1)[task].unsqueeze(-1)
+        else:
+            action_dims = None
+        log_prob = (-0.5 * eps.pow(2) - log_std - 0.9189385175704956).sum(-1, keepdim=True)  # math.gaussian_logprob
+        scaled_log_prob = log_prob * (eps.shape[-1] if action_dims is None else action_dims)
         action = mean + eps * log_std.exp()
-        return torch.tanh(action), {"mean": torch.tanh(mean), "log_std": log_std}
+        mean, action = torch.tanh(mean), torch.tanh(action)  # math.squash
+        log_prob = log_prob - torch.log(F.relu(1 - action.pow(2)) + 1e-6).sum(-1, keepdim=True)
+        entropy_scale = scaled_log_prob / (log_prob + 1e-8)
+        return action, {"mean": mean, "log_std": log_std, "action_prob": 1.0, "entropy": -log_prob,
+                        "scaled_entropy": -log_prob * entropy_scale}
 
     def Q(self, z, a, task, return_type="min"):
         assert return_type in {"min", "avg", "all"}
