@@ -25,6 +25,8 @@
  *   tdmpc2_plan_act_pi[_pix]  <- TDMPC2.act with cfg.mpc == False       tdmpc2/tdmpc2.py:114-120
  *   tdmpc2_plan_td_target[_mt]    <- TDMPC2._td_target                  tdmpc2/tdmpc2.py:239-254
  *   tdmpc2_plan_policy_value[_mt] <- forward half of TDMPC2.update_pi   tdmpc2/tdmpc2.py:208-225
+ *   tdmpc2_plan_model_rollout[_mt] <- the open-loop latent rollout and predictions of TDMPC2._update  tdmpc2/tdmpc2.py:268-283
+ *   tdmpc2_plan_model_losses[_mt]  <- ... and its four losses                                       tdmpc2/tdmpc2.py:285-304
  *   tdmpc2_plan_export_packed / import_packed <- TDMPC2.save / load of the planner's weights  tdmpc2/tdmpc2.py:72-95
  *   tdmpc2_plan_export_noise  <- the six RNG draw sites of one plan    tdmpc2/tdmpc2.py:176,204, tdmpc2/common/world_model.py:156,212,
  *                                (what torch.manual_seed pins there)   tdmpc2/common/math.py:90
@@ -61,7 +63,7 @@
 extern "C" {
 #endif
 
-#define TDMPC2_PLAN_ABI_VERSION 11
+#define TDMPC2_PLAN_ABI_VERSION 12
 
 typedef struct tdmpc2_plan tdmpc2_plan_t;
 
@@ -203,7 +205,7 @@ int tdmpc2_plan_run(tdmpc2_plan_t *h, int n_envs, const float *z0, const float *
  * of a noise tape: tdmpc2_plan_run(..., tape = the export, ...) then reproduces the tape = NULL plan bit for bit, and the
  * same tape replays through a CPU restatement of the reference.  Every kernel family draws the same numbers.
  *   call  = the value tdmpc2_plan_call_counter returned BEFORE the run being reproduced (run / run_obs / shard_begin /
- *           policy_value / td_target each consume one count). */
+ *           policy_value / td_target / model_rollout / model_losses each consume one count). */
 int tdmpc2_plan_export_noise(tdmpc2_plan_t *h, int env_first, int n_envs, uint64_t seed, uint32_t call,
                              const tdmpc2_noise_out *out, void *stream);
 /* The per-handle call counter mixed into the Philox key (so that consecutive plans under one seed draw fresh noise).
@@ -325,6 +327,67 @@ int tdmpc2_plan_policy_value_mt(tdmpc2_plan_t *h, int n_rows, const float *z, co
 int tdmpc2_plan_td_target_mt(tdmpc2_plan_t *h, int n_rows, const float *next_z, const float *reward,
                              const float *terminated, float discount, const tdmpc2_task_tables *tasks,
                              const float *pi_eps, const int32_t *qidx, uint64_t seed, float *td, void *stream);
+
+/* Model rollout and losses (ABI 12): the rest of the forward half of TDMPC2._update (tdmpc2/tdmpc2.py:259-304) -- what
+ * tdmpc2_plan_encode and tdmpc2_plan_td_target do not cover.  Forward only, EVAL MODE, fp32 in / fp32 out, no gradients.  Eval
+ * mode means dropout off: the Q heads' first layer has Dropout(cfg.dropout) in the reference (common/layers.py, mlp(..., dropout=)),
+ * which is active inside _update (model.train(), tdmpc2.py:266); the numbers here equal what _update reports when cfg.dropout == 0
+ * and are the dropout-free values otherwise.  Both kernel families, both arithmetics (the contractions run in the handle's
+ * arithmetic; log-softmax, two-hot targets, MSE, BCE and every reduction are plain fp32); single-task and multitask handles.
+ *
+ * model_rollout: z0 [B, L], actions [steps, B, A] (used as given: the reference does not mask recorded actions in _update),
+ * 0 <= steps <= 8, use_target: the online (0) or target (1: bind TDMPC2_NET_TARGET_Q first) Q ensemble.  Outputs are optional
+ * device pointers (NULL = not wanted; a chain whose outputs are all NULL is not computed):
+ *   zs            [steps + 1, B, L]   zs[0] = z0, zs[t+1] = next(zs[t], actions[t])        tdmpc2.py:269-276, world_model.py:114-121
+ *   reward_logits [steps, B, nb]      WorldModel.reward(zs[:-1], actions), nb = max(num_bins, 1)   world_model.py:123-130
+ *   reward        [steps, B]          two_hot_inv of them                                  math.py:74-83
+ *   q_logits      [num_q, steps, B, nb]  EVERY head: WorldModel.Q(zs[:-1], actions, return_type='all')  world_model.py:186-210
+ *   q             [num_q, steps, B]   two_hot_inv of them
+ *   term_logit    [steps + 1, B]      WorldModel.termination(zs, unnormalized=True); episodic handles only  world_model.py:132-141
+ * steps = 1 is WorldModel.next / reward / Q on a batch of rows; steps = 0 is WorldModel.termination(z0).
+ * _mt: tasks->task_ids is [B], ONE TASK PER ROW of the batch (the reference repeats task [B] over the leading step axis); rows use
+ * the first-layer bias of their task (tasks->discount is not read).
+ *
+ * model_losses: the same inputs and optional outputs (`out` may be NULL) plus the targets of _update ->
+ *   losses [5] = consistency, reward, value, termination, total (tdmpc2.py:285-304): mse(zs[t+1], next_z[t]) rho^t summed, / steps;
+ *   soft_ce (math.py:5-9: log_softmax of the logits against two_hot of the target, math.py:58-71) averaged over the batch per
+ *   step, rho^t, / steps and for the value loss also / num_q; binary_cross_entropy_with_logits(term_logit[1:], terminated) over all
+ *   steps x B rows (0 when not episodic); total = the coefficient-weighted sum.
+ *   step_means [4, steps] (may be NULL): the unweighted per-step batch means of consistency, reward, value (mean over the heads
+ *   too) and termination -- loss against rollout depth.
+ * When only losses are asked for, no logits go through HBM.  Deterministic: per-row terms go to a workspace and ONE workgroup adds
+ * them in a fixed order (no float atomics) -- the same inputs give the same bits, whatever else is asked for.
+ * Launches (tdmpc2_amd/csrc/model_route.h): FUSED one workgroup per 64-row tile rolls the dynamics chain, then ONE launch of
+ * tiles x steps x (1 + num_q) workgroups runs the reward and Q chains of every step side by side, one more for the termination
+ * head; LAYERED the dynamics chain per step over B rows, then every other chain once over all steps x B rows.  No workgroup
+ * waits for another one in the new kernels; the LAYERED GEMMs keep their NormedLinear epilogue (TDMPC2_TUNE_FUSE_LN), whose fault
+ * contract applies unchanged: NaN in every output and tdmpc2_plan_take_fault.
+ * Workspace (zs when not asked for, per-row loss terms, the multitask tables) grows at the first call of a shape: keep that call
+ * outside a hipGraph capture; after it the calls allocate nothing and never synchronise the host.
+ * Refusals: steps outside [0, 8], batch < 1, model_losses with steps < 1, a missing target, `terminated` on a non-episodic handle or
+ * term_logit asked of one, tasks on a single-task handle (or none on a multitask one), LAYERED: batch x steps beyond max_envs x
+ * num_samples rows -- TDMPC2_ERR_INVALID; use_target without the target ensemble -- TDMPC2_ERR_STATE; model_losses with
+ * num_bins < 2 (the reference's soft_ce is identically 0 there) -- TDMPC2_ERR_UNSUPPORTED. */
+typedef struct tdmpc2_model_out {   /* device pointers, any may be NULL */
+    float *zs, *reward_logits, *reward, *q_logits, *q, *term_logit;
+} tdmpc2_model_out;
+typedef struct tdmpc2_model_targets {
+    const float *next_z;      /* [steps, B, L]  encode(obs[1:])                                    tdmpc2.py:262 */
+    const float *reward;      /* [steps, B] */
+    const float *td_target;   /* [steps, B]     tdmpc2_plan_td_target's output                     tdmpc2.py:263 */
+    const float *terminated;  /* [steps, B] in {0, 1}; NULL unless episodic */
+    float rho, consistency_coef, reward_coef, value_coef, termination_coef;   /* config.yaml:17-21 */
+} tdmpc2_model_targets;
+int tdmpc2_plan_model_rollout(tdmpc2_plan_t *h, int batch, int steps, const float *z0, const float *actions, int use_target,
+                              const tdmpc2_model_out *out, void *stream);
+int tdmpc2_plan_model_rollout_mt(tdmpc2_plan_t *h, int batch, int steps, const float *z0, const float *actions,
+                                 const tdmpc2_task_tables *tasks, int use_target, const tdmpc2_model_out *out, void *stream);
+int tdmpc2_plan_model_losses(tdmpc2_plan_t *h, int batch, int steps, const float *z0, const float *actions, int use_target,
+                             const tdmpc2_model_targets *targets, const tdmpc2_model_out *out, float *losses, float *step_means,
+                             void *stream);
+int tdmpc2_plan_model_losses_mt(tdmpc2_plan_t *h, int batch, int steps, const float *z0, const float *actions,
+                                const tdmpc2_task_tables *tasks, int use_target, const tdmpc2_model_targets *targets,
+                                const tdmpc2_model_out *out, float *losses, float *step_means, void *stream);
 
 /* Packed weight file (the native counterpart of TDMPC2.save / load, tdmpc2.py:72-95).
  * export_packed copies everything the binds produced -- weights in MFMA fragment order (hi / lo split and scaled for the

@@ -40,6 +40,12 @@ class Config:
     min_std: float = 0.05
     max_std: float = 2.0
     temperature: float = 0.5
+    # training losses (config.yaml:17-21): read by TDMPC2.model_losses, the forward half of _update
+    rho: float = 0.5
+    consistency_coef: float = 20.0
+    reward_coef: float = 0.1
+    value_coef: float = 0.1
+    termination_coef: float = 1.0
     # actor (config.yaml:44-47)
     log_std_min: float = -10.0
     log_std_max: float = 2.0

@@ -108,6 +108,10 @@ struct tdmpc2_plan {
     int *task_rows = nullptr;  // [rows] copy of the row -> task map, padded to whole GEMM tiles (layered family)
     int tab_tasks = 0;
     size_t task_rows_cap = 0;
+    // model rollout / losses (tdmpc2_plan_model_rollout / model_losses): zs [H + 1, B, L] when the caller does not ask for it, and
+    // the per-row loss terms [3 + num_q][H B]; grown at first use
+    float *model_zs = nullptr, *model_rowloss = nullptr;
+    size_t model_zs_cap = 0, model_rowloss_cap = 0;
     // cluster path of the fused family (cluster_kernels.cuh): single-plan latency
     int cluster_mode = 2;            // TDMPC2_TUNE_CLUSTER: 0 never, 1 whenever the call fits, 2 auto (= 1 today)
     int cl_max_clusters = 0;         // clusters the buffers below were sized for (0: path not available on this handle)

@@ -9,8 +9,10 @@ namespace {
 #include "layered_split.cuh"
 #include "layered_wide.cuh"
 #include "layered_mid.cuh"
+#include "model_layered.cuh"  // model rollout / losses: row kernels
 }  // namespace
 
 namespace tdk {
 #include "layered_host.cuh"
+#include "model_layered_host.cuh"
 }  // namespace tdk

@@ -41,6 +41,8 @@ struct PolHeadParams {
 
 namespace tdk {
 
+#include "model_params.h"  // model rollout / losses (k_model.hip, model_layered.cuh in k_layered.hip)
+
 // ---- fused 512-wide family: one table per action padding (k_fused.hip, compiled once per -DTU_APAD=16|32|48|64).
 // ar: 0 = f16x2 split, 1 = exact fp32 MFMA; nst: 32-row sample tiles per workgroup (1 | 2).
 struct FusedOps {
@@ -92,6 +94,22 @@ int lay_sample_iteration(tdmpc2_plan *h, hipStream_t st, int E, int iter, const 
 // the two Q heads of a single evaluation (td_target / estimate_value entry points): copied from `qidx` ([E, 2], row stride
 // `stride`) or drawn (Philox) when it is null
 int lay_set_qidx(tdmpc2_plan *h, hipStream_t st, int E, const int *qidx, long stride, int nq, int iter, uint64_t seed, unsigned call, int *dst);
+
+// ---- model rollout / losses (k_model.hip per action padding: the fused family's kernels; its generic unit: the row kernels;
+// k_layered.hip: the layered family's stages).  Routes: model_route.h.
+struct ModelOps {
+    void (*dyn)(int ar, const ModelParamsT<NetS> &p, int gx, size_t lds, hipStream_t st);
+    void (*chain)(int ar, const ModelParamsT<NetS> &p, int gx, int gy, int gz, size_t lds, hipStream_t st);
+    int (*set_lds)(int ar, size_t lds_bytes);
+};
+const ModelOps &model_ops_ap16(); const ModelOps &model_ops_ap32(); const ModelOps &model_ops_ap48(); const ModelOps &model_ops_ap64();
+int model_launch_cons(const ModelConsParams &p, int gx, hipStream_t st);
+int model_launch_tail(const ModelTailParams &p, hipStream_t st);
+int model_launch_tile_tasks(const int *task_ids, int B, int rows, int rows_p, int *out, hipStream_t st);
+// layered family: the stages of a call (r: model_route's answer).  zs [H + 1, B, L] with zs[0] already written; row_task: the
+// row -> task map tiled over (H + 1) * B rows and padded, or null.
+int lay_model(tdmpc2_plan *h, hipStream_t st, const ModelRoute &r, int B, int H, const float *actions, float *zs, bool target,
+              const int *row_task, const ModelOutArgs &out, const ModelLossArgs &ls);
 
 // ---- policy prior (k_policy.hip)
 int pol_set_lds();  // the GEMV instantiations' dynamic LDS limit (once per handle, at bind)

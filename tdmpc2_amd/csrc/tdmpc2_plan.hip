@@ -372,6 +372,21 @@ int check_ready(tdmpc2_plan *h) {
 #ifndef TDMPC2_DEFAULT_THROUGHPUT_ST
 #define TDMPC2_DEFAULT_THROUGHPUT_ST 2  // sample tiles per workgroup when a call has enough plans to fill the chip
 #endif
+const ModelOps &model_ops(int apad) {
+#ifdef TDMPC2_ONLY_APAD
+#define TDK_MOPS_CAT_(a, b) a##b
+#define TDK_MOPS_CAT(a, b) TDK_MOPS_CAT_(a, b)
+    (void)apad;
+    return TDK_MOPS_CAT(model_ops_ap, TDMPC2_ONLY_APAD)();
+#else
+    switch (apad) {
+        case 16: return model_ops_ap16();
+        case 32: return model_ops_ap32();
+        case 48: return model_ops_ap48();
+        default: return model_ops_ap64();
+    }
+#endif
+}
 const FusedOps &fused_ops(int apad) {
 #ifdef TDMPC2_ONLY_APAD  // experiment builds (tools/ablate.sh): one action padding only, a quarter of the compile time
 #define TDK_OPS_CAT_(a, b) a##b
@@ -966,6 +981,7 @@ int tdmpc2_plan_create(const tdmpc2_plan_cfg *cfg, tdmpc2_plan_t **out) {
     if (!h->lay.on) {
         const int ar = h->split ? 0 : 1;
         rc = fused_ops(h->Apad).set_lds(ar, c.episodic, h->lds_bytes);
+        if (!rc) rc = model_ops(h->Apad).set_lds(ar, h->lds_bytes);
         if (rc) {
             tdmpc2_plan_destroy(h);
             return TDMPC2_ERR_HIP;
@@ -1612,7 +1628,7 @@ int tdmpc2_plan_act_pi_pix(tdmpc2_plan_t *h, int n_envs, const void *obs, int ob
 namespace {
 // per-task tables of a multitask value call: effective first-layer biases of pi and of the chosen Q ensemble, action
 // masks, discounts; (re)built on every call (the weights may have been re-bound), storage grown on demand
-int build_task_tables(tdmpc2_plan *h, const tdmpc2_task_tables *tk, bool target, size_t rows_p, hipStream_t st) {
+int build_task_tables(tdmpc2_plan *h, const tdmpc2_task_tables *tk, bool target, size_t rows_p, hipStream_t st, bool all_nets = false) {
     const tdmpc2_plan_cfg &c = h->cfg;
     const int nt = tk->n_tasks;
     const size_t width = h->lay.on ? (size_t)h->lay.Mp : (size_t)WIDTH;
@@ -1642,6 +1658,10 @@ int build_task_tables(tdmpc2_plan *h, const tdmpc2_task_tables *tk, bool target,
     TaskBiasParams p{};
     p.T = c.task_dim; p.nq = c.num_q; p.nnets = h->nnets; p.task_emb = tk->task_emb; p.beff_tab = h->beff_tab;
     p.wemb[BE_PI] = h->pi.l[0].wemb; p.bias[BE_PI] = h->pi.l[0].bias;
+    if (all_nets) {  // model rollout: the dynamics and reward first layers take the row's task as well
+        p.wemb[BE_DYN] = h->dyn.l[0].wemb; p.bias[BE_DYN] = h->dyn.l[0].bias;
+        p.wemb[BE_REW] = h->rew.l[0].wemb; p.bias[BE_REW] = h->rew.l[0].bias;
+    }
     for (int i = 0; i < c.num_q; ++i) { p.wemb[BE_Q0 + i] = qarr[i].l[0].wemb; p.bias[BE_Q0 + i] = qarr[i].l[0].bias; }
     hipLaunchKernelGGL(ks_task_bias, dim3(nt), dim3(WIDTH), 0, st, p);
     HIP_TRY(hipGetLastError());
@@ -1734,6 +1754,156 @@ int tdmpc2_plan_td_target_mt(tdmpc2_plan_t *h, int n_rows, const float *next_z, 
 int tdmpc2_plan_td_target(tdmpc2_plan_t *h, int n_rows, const float *next_z, const float *reward, const float *terminated,
                           float discount, const float *pi_eps, const int32_t *qidx, uint64_t seed, float *td, void *stream) {
     return tdmpc2_plan_td_target_mt(h, n_rows, next_z, reward, terminated, discount, nullptr, pi_eps, qidx, seed, td, stream);
+}
+
+// ---------------------------------------------------------------- model rollout + losses: the forward half of TDMPC2._update
+// (tdmpc2/tdmpc2.py:259-304).  model_route.h decides the stages; the fused family launches ks_value_roll / ks_value_chain
+// (k_model.hip), the layered family its GEMM chains (lay_model); the loss rows and the fixed-order tail are shared.
+namespace {
+int grow_ws(tdmpc2_plan *h, float **buf, size_t *cap, size_t floats, hipStream_t st) {
+    if (floats <= *cap) return 0;
+    HIP_TRY(hipStreamSynchronize(st));  // (first use or a larger call: outside a hipGraph capture, like the task tables)
+    dev_release(h, *buf);
+    *buf = nullptr;
+    *cap = 0;
+    int rc = dev_alloc(h, (void **)buf, floats * 4);
+    if (rc) return rc;
+    *cap = floats;
+    return 0;
+}
+
+int launch_model(tdmpc2_plan *h, int B, int H, const float *z0, const float *actions, bool target, const tdmpc2_task_tables *tk,
+                 const tdmpc2_model_targets *tg, const tdmpc2_model_out *out, float *losses, float *step_means, hipStream_t st) {
+    const tdmpc2_plan_cfg &c = h->cfg;
+    static const tdmpc2_model_out none{};
+    if (!out) out = &none;
+    unsigned want = 0;
+    if (out->zs) want |= MW_ZS;
+    if (out->reward_logits) want |= MW_REW_LOGITS;
+    if (out->reward) want |= MW_REW;
+    if (out->q_logits) want |= MW_Q_LOGITS;
+    if (out->q) want |= MW_Q;
+    if (out->term_logit) want |= MW_TERM;
+    if (tg) want |= MW_LOSSES;
+    if (tg && c.num_bins < 2) return fail(TDMPC2_ERR_UNSUPPORTED, "model_losses needs two-hot heads (num_bins %d: the reference's soft_ce is identically 0)", c.num_bins);
+    if (tg && tg->terminated && !c.episodic) return fail(TDMPC2_ERR_INVALID, "`terminated` given to a non-episodic handle");
+    const size_t cap = round_up((size_t)c.max_envs * c.num_samples, GBM);
+    const ModelRoute r = model_route(ModelIn{h->lay.on ? MODEL_LAYERED : MODEL_FUSED, B, H, c.num_q, c.num_bins, c.episodic, want, (long)cap,
+                                                 (h->split && h->lay.fuse_ln) ? 0 : 1});
+    switch (r.refuse) {
+        case MR_OK: break;
+        case MR_BAD_H: return fail(TDMPC2_ERR_INVALID, "steps %d outside [0, %d]", H, MAXH);
+        case MR_BAD_B: return fail(TDMPC2_ERR_INVALID, "batch %d < 1", B);
+        case MR_LOSSES_H0: return fail(TDMPC2_ERR_INVALID, "model_losses needs at least one step");
+        case MR_NOT_EPISODIC: return fail(TDMPC2_ERR_INVALID, "term_logit asked of a non-episodic handle");
+        case MR_ROWS: return fail(TDMPC2_ERR_INVALID, "the layered workspace holds %zu rows (max_envs x num_samples); got batch x steps = %d x %d", cap, B, H);
+        default: return fail(TDMPC2_ERR_UNSUPPORTED, "model_losses needs two-hot heads (num_bins %d)", c.num_bins);
+    }
+    if (H > 0 && !actions) return fail(TDMPC2_ERR_INVALID, "null actions");
+    if (tg) {
+        if (!tg->next_z || !tg->reward || !tg->td_target || !losses) return fail(TDMPC2_ERR_INVALID, "null target / losses argument");
+        if (c.episodic && !tg->terminated) return fail(TDMPC2_ERR_INVALID, "episodic handle: `terminated` is required");
+    }
+    if (c.multitask) {
+        if (!tk || !tk->task_ids || !tk->task_emb || !tk->act_mask || tk->n_tasks < 1)
+            return fail(TDMPC2_ERR_INVALID, "multitask model_rollout / model_losses need the row -> task map and the per-task tables");
+    } else if (tk) {
+        return fail(TDMPC2_ERR_INVALID, "task tables given to a single-task handle");
+    }
+    int rc = check_ready(h);
+    if (rc) return rc;
+    (void)fault_poll(h);
+    if (!h->in_shard && (rc = fault_fresh(h, st))) return rc;
+    if (target)
+        for (int i = 0; i < 3; ++i)
+            for (int qh = 0; qh < c.num_q; ++qh)
+                if (!h->tq[qh].l[i].bound)
+                    return fail(TDMPC2_ERR_STATE, "layer %d of target Q head %d is not bound (net TDMPC2_NET_TARGET_Q)", i, qh);
+    h->call++;  // one tick like policy_value / td_target (nothing is drawn here: the tick keeps the siblings' numbering uniform)
+    const size_t Ld = (size_t)c.latent_dim, HB = (size_t)H * B;
+    if (r.launches == 0) {  // H = 0 and no termination logit: zs[0] = z0 is all there is
+        if (out->zs && out->zs != z0) HIP_TRY(hipMemcpyAsync(out->zs, z0, (size_t)B * Ld * 4, hipMemcpyDeviceToDevice, st));
+        return 0;
+    }
+    float *zs = out->zs;
+    if (!zs) {
+        if ((rc = grow_ws(h, &h->model_zs, &h->model_zs_cap, (size_t)(H + 1) * B * Ld, st))) return rc;
+        zs = h->model_zs;
+    }
+    if (tg && (rc = grow_ws(h, &h->model_rowloss, &h->model_rowloss_cap, (size_t)model_rowloss_floats(B, H, c.num_q), st))) return rc;
+    const size_t trows = (size_t)(H + 1) * B, trows_p = round_up(trows, GBM);
+    if (c.multitask) {
+        if ((rc = build_task_tables(h, tk, target, h->lay.on ? trows_p : 0, st, true))) return rc;
+        if (h->lay.on && (rc = model_launch_tile_tasks(tk->task_ids, B, (int)trows, (int)trows_p, h->task_rows, st))) return rc;
+    }
+    if (zs != z0) HIP_TRY(hipMemcpyAsync(zs, z0, (size_t)B * Ld * 4, hipMemcpyDeviceToDevice, st));
+    ModelLossArgs ls{};
+    ls.num_bins = c.num_bins; ls.vmin = c.vmin; ls.vmax = c.vmax;
+    ls.bin_size = c.num_bins > 1 ? (float)(((double)c.vmax - (double)c.vmin) / (c.num_bins - 1)) : 1.f;  // parser.py: cfg.bin_size
+    ls.bins = h->bins; ls.HB = (long)HB;
+    if (tg) { ls.t_reward = tg->reward; ls.t_td = tg->td_target; ls.t_term = tg->terminated; ls.rowloss = h->model_rowloss; }
+    const ModelOutArgs oa{out->reward_logits, out->reward, out->q_logits, out->q, out->term_logit};
+    if (h->lay.on) {
+        if ((rc = lay_model(h, st, r, B, H, actions, zs, target, c.multitask ? h->task_rows : nullptr, oa, ls))) return rc;
+    } else {
+        ModelParamsT<NetS> p{};
+        p.B = B; p.H = H; p.A = c.action_dim; p.Apad = h->Apad; p.nq = c.num_q; p.nnets = h->nnets; p.steps = r.st[MS_DYN].steps;
+        p.dyn = to_dev<NetS>(h->dyn); p.rew = to_dev<NetS>(h->rew);
+        if (c.episodic) p.term = to_dev<NetS>(h->term);
+        for (int i = 0; i < c.num_q; ++i) p.q[i] = to_dev<NetS>(target ? h->tq[i] : h->q[i]);
+        p.z0 = z0; p.actions = actions; p.zs = zs; p.out = oa; p.ls = ls;
+        if (c.multitask) { p.task_ids = tk->task_ids; p.beff_tab = h->beff_tab; }
+        const int ar = h->split ? 0 : 1;
+        const ModelOps &ops = model_ops(h->Apad);
+        if (r.st[MS_DYN].run) {
+            ops.dyn(ar, p, r.st[MS_DYN].gx, h->lds_bytes, st);
+            HIP_TRY(hipGetLastError());
+        }
+        if (r.st[MS_HEADS].run) {
+            for (int k = 0; k < r.nchain; ++k) p.chain[k] = r.chain[k];
+            ops.chain(ar, p, r.st[MS_HEADS].gx, r.st[MS_HEADS].gy, r.st[MS_HEADS].gz, h->lds_bytes, st);
+            HIP_TRY(hipGetLastError());
+        }
+        if (r.st[MS_TERM].run) {
+            p.chain[0] = MC_TERM;
+            ops.chain(ar, p, r.st[MS_TERM].gx, r.st[MS_TERM].gy, 1, h->lds_bytes, st);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    if (!tg) return 0;
+    const unsigned int *err = (h->lay.on && h->split && h->lay.fuse_ln) ? h->cl_err_dev : nullptr;
+    ModelConsParams cp{zs + (size_t)B * Ld, tg->next_z, (int)HB, c.latent_dim, h->model_rowloss};
+    if ((rc = model_launch_cons(cp, r.st[MS_CONS].gx, st))) return rc;
+    ModelTailParams tp{};
+    tp.rowloss = h->model_rowloss; tp.B = B; tp.H = H; tp.L = c.latent_dim; tp.nq = c.num_q; tp.episodic = c.episodic;
+    for (int t = 0; t < H; ++t) tp.rho_pow[t] = (float)std::pow((double)tg->rho, t);
+    tp.coef[0] = tg->consistency_coef; tp.coef[1] = tg->reward_coef; tp.coef[2] = tg->value_coef; tp.coef[3] = tg->termination_coef;
+    tp.losses = losses; tp.step_means = step_means; tp.err = err;
+    return model_launch_tail(tp, st);
+}
+}  // namespace
+
+int tdmpc2_plan_model_rollout_mt(tdmpc2_plan_t *h, int batch, int steps, const float *z0, const float *actions,
+                                 const tdmpc2_task_tables *tasks, int use_target, const tdmpc2_model_out *out, void *stream) {
+    if (!h || !z0 || !out) return fail(TDMPC2_ERR_INVALID, "null argument");
+    ENTER_ON(h, stream);
+    return launch_model(h, batch, steps, z0, actions, use_target != 0, tasks, nullptr, out, nullptr, nullptr, (hipStream_t)stream);
+}
+int tdmpc2_plan_model_rollout(tdmpc2_plan_t *h, int batch, int steps, const float *z0, const float *actions, int use_target,
+                              const tdmpc2_model_out *out, void *stream) {
+    return tdmpc2_plan_model_rollout_mt(h, batch, steps, z0, actions, nullptr, use_target, out, stream);
+}
+int tdmpc2_plan_model_losses_mt(tdmpc2_plan_t *h, int batch, int steps, const float *z0, const float *actions,
+                                const tdmpc2_task_tables *tasks, int use_target, const tdmpc2_model_targets *targets,
+                                const tdmpc2_model_out *out, float *losses, float *step_means, void *stream) {
+    if (!h || !z0 || !targets || !losses) return fail(TDMPC2_ERR_INVALID, "null argument");
+    ENTER_ON(h, stream);
+    return launch_model(h, batch, steps, z0, actions, use_target != 0, tasks, targets, out, losses, step_means, (hipStream_t)stream);
+}
+int tdmpc2_plan_model_losses(tdmpc2_plan_t *h, int batch, int steps, const float *z0, const float *actions, int use_target,
+                             const tdmpc2_model_targets *targets, const tdmpc2_model_out *out, float *losses, float *step_means,
+                             void *stream) {
+    return tdmpc2_plan_model_losses_mt(h, batch, steps, z0, actions, nullptr, use_target, targets, out, losses, step_means, stream);
 }
 
 // ---------------------------------------------------------------- one plan sharded over several GPUs (last row)

@@ -17,7 +17,7 @@ import torch
 _LIB_PATH = os.environ.get("TDMPC2_PLAN_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtdmpc2_plan.so")
 _lib = None
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 # every symbol include/tdmpc2_plan.h declares (tests check the .so exports all of them)
 ABI_SYMBOLS = [
@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "tdmpc2_plan_fault_info", "tdmpc2_plan_fault_word",
     "tdmpc2_plan_bind_pixel_encoder", "tdmpc2_plan_encode_pix", "tdmpc2_plan_run_pix",
     "tdmpc2_plan_bind_policy", "tdmpc2_plan_pi", "tdmpc2_plan_act_pi", "tdmpc2_plan_act_pi_pix",
+    "tdmpc2_plan_model_rollout", "tdmpc2_plan_model_rollout_mt", "tdmpc2_plan_model_losses", "tdmpc2_plan_model_losses_mt",
 ]
 
 NET_DYNAMICS, NET_REWARD, NET_PI, NET_Q, NET_TERMINATION, NET_TARGET_Q = range(6)
@@ -62,6 +63,20 @@ class TaskTables(C.Structure):
     """struct tdmpc2_task_tables: one task per row of a training batch + the per-task tables."""
     _fields_ = [("task_ids", C.c_void_p), ("task_emb", C.c_void_p), ("act_mask", C.c_void_p), ("discount", C.c_void_p),
                 ("n_tasks", C.c_int32)]
+
+
+class ModelOut(C.Structure):
+    """struct tdmpc2_model_out: optional device outputs of the model rollout."""
+    _fields_ = [(n, C.c_void_p) for n in ("zs", "reward_logits", "reward", "q_logits", "q", "term_logit")]
+
+
+class ModelTargets(C.Structure):
+    """struct tdmpc2_model_targets: the targets and weights of TDMPC2._update's losses."""
+    _fields_ = [(n, C.c_void_p) for n in ("next_z", "reward", "td_target", "terminated")] + \
+               [(n, C.c_float) for n in ("rho", "consistency_coef", "reward_coef", "value_coef", "termination_coef")]
+
+
+MODEL_OUTPUTS = ("zs", "reward_logits", "reward", "q_logits", "q", "term_logit")
 
 
 class PolicyOut(C.Structure):
@@ -162,6 +177,11 @@ def _open(path):
     lib.tdmpc2_plan_policy_value_mt.restype = i32
     lib.tdmpc2_plan_td_target_mt.argtypes = [vp, i32, vp, vp, vp, C.c_float, C.POINTER(TaskTables), vp, vp, u64, vp, vp]
     lib.tdmpc2_plan_td_target_mt.restype = i32
+    lib.tdmpc2_plan_model_rollout_mt.argtypes = [vp, i32, i32, vp, vp, C.POINTER(TaskTables), i32, C.POINTER(ModelOut), vp]
+    lib.tdmpc2_plan_model_rollout_mt.restype = i32
+    lib.tdmpc2_plan_model_losses_mt.argtypes = [vp, i32, i32, vp, vp, C.POINTER(TaskTables), i32, C.POINTER(ModelTargets),
+                                                C.POINTER(ModelOut), vp, vp, vp]
+    lib.tdmpc2_plan_model_losses_mt.restype = i32
     lib.tdmpc2_plan_packed_size.argtypes = [vp, C.POINTER(u64)]
     lib.tdmpc2_plan_packed_size.restype = i32
     lib.tdmpc2_plan_export_packed.argtypes = [vp, vp, u64, vp]
@@ -711,6 +731,64 @@ class NativePlanner:
                                                           _ptr(pi_eps), _ptr(qidx), C.c_uint64(int(seed) & (2**64 - 1)),
                                                           _ptr(td), self._stream()))
         return td
+
+    def _model_out(self, B, H, want):
+        """Output tensors of a model rollout, shaped as the reference returns them, and the struct pointing at them."""
+        cfg, dev = self.cfg, self.device
+        nb = max(cfg.num_bins, 1)
+        shapes = {"zs": (H + 1, B, cfg.latent_dim), "reward_logits": (H, B, nb), "reward": (H, B, 1),
+                  "q_logits": (cfg.num_q, H, B, nb), "q": (cfg.num_q, H, B, 1), "term_logit": (H + 1, B, 1)}
+        for k in want:
+            if k not in shapes:
+                raise ValueError(f"unknown model output {k!r} (one of {MODEL_OUTPUTS})")
+        res = {k: torch.empty(shapes[k], device=dev) for k in want}
+        mo = ModelOut(**{k: (res[k].data_ptr() if k in res else None) for k in MODEL_OUTPUTS})
+        return res, mo
+
+    def model_rollout(self, z0, actions, use_target=False, want=MODEL_OUTPUTS[:5], task_ids=None, task_emb_table=None,
+                      act_mask_table=None):
+        """The open-loop latent rollout on recorded actions and the predictions on it (tdmpc2.py:268-283): z0 [B, L], actions
+        [H, B, A] -> dict of the outputs named in `want` (tdmpc2_model_out; q_logits [num_q, H, B, bins]).  Multitask models:
+        `task_ids` int32 [B], one task per row of the batch."""
+        cfg, dev = self.cfg, self.device
+        B, H = int(z0.shape[0]), int(actions.shape[0])
+        _chk_tensor("z0", z0, torch.float32, (B, cfg.latent_dim), dev)
+        _chk_tensor("actions", actions, torch.float32, (H, B, cfg.action_dim), dev)
+        tt, keep = self._task_tables(B, task_ids, task_emb_table, act_mask_table)
+        res, mo = self._model_out(B, H, tuple(want))
+        with torch.cuda.device(dev):
+            self._check(self.lib.tdmpc2_plan_model_rollout_mt(self._h, B, H, _ptr(z0), _ptr(actions), tt, int(bool(use_target)),
+                                                              C.byref(mo), self._stream()))
+        return res
+
+    def model_losses(self, z0, actions, next_z, reward, td_target, terminated=None, rho=0.5, coefs=(20.0, 0.1, 0.1, 1.0),
+                     use_target=False, want=(), step_means=False, task_ids=None, task_emb_table=None, act_mask_table=None):
+        """The rollout plus the losses of TDMPC2._update (tdmpc2.py:285-304): targets next_z [H, B, L], reward / td_target /
+        terminated [H, B] (terminated: episodic models only); coefs = (consistency, reward, value, termination).  Returns a dict:
+        "losses" [5] (consistency, reward, value, termination, total), optionally "step_means" [4, H], and the outputs in `want`."""
+        cfg, dev = self.cfg, self.device
+        B, H = int(z0.shape[0]), int(actions.shape[0])
+        _chk_tensor("z0", z0, torch.float32, (B, cfg.latent_dim), dev)
+        _chk_tensor("actions", actions, torch.float32, (H, B, cfg.action_dim), dev)
+        _chk_tensor("next_z", next_z, torch.float32, (H, B, cfg.latent_dim), dev)
+        _chk_tensor("reward", reward, torch.float32, (H, B), dev)
+        _chk_tensor("td_target", td_target, torch.float32, (H, B), dev)
+        if terminated is not None:
+            _chk_tensor("terminated", terminated, torch.float32, (H, B), dev)
+        tt, keep = self._task_tables(B, task_ids, task_emb_table, act_mask_table)
+        res, mo = self._model_out(B, H, tuple(want))
+        tg = ModelTargets(next_z=next_z.data_ptr(), reward=reward.data_ptr(), td_target=td_target.data_ptr(),
+                          terminated=None if terminated is None else terminated.data_ptr(), rho=float(rho),
+                          consistency_coef=float(coefs[0]), reward_coef=float(coefs[1]), value_coef=float(coefs[2]),
+                          termination_coef=float(coefs[3]))
+        res["losses"] = torch.empty(5, device=dev)
+        if step_means:
+            res["step_means"] = torch.empty(4, H, device=dev)
+        with torch.cuda.device(dev):
+            self._check(self.lib.tdmpc2_plan_model_losses_mt(self._h, B, H, _ptr(z0), _ptr(actions), tt, int(bool(use_target)),
+                                                             C.byref(tg), C.byref(mo), _ptr(res["losses"]),
+                                                             _ptr(res.get("step_means")), self._stream()))
+        return res
 
     # ------------------------------------------------------------------ packed weight file
     def export_packed(self) -> bytes:

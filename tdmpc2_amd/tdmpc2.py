@@ -388,3 +388,69 @@ class TDMPC2(torch.nn.Module):
         self._seed += 1
         a, q = self.planner().policy_value(z2, use_target=target, reduce=reduce, pi_eps=pi_eps, qidx=qidx, seed=self._seed, **kw)
         return a.reshape(*lead, -1), q.reshape(*lead, 1)
+
+    # ------------------------------------------------------------------ the rest of _update's forward half
+    def _batch_task_kw(self, task):
+        """task int64 [B] -> the keyword arguments of the native batch calls (multitask models), else {}."""
+        if not self.cfg.multitask:
+            return {}
+        emb, mask, _ = self._task_tables()
+        task = torch.as_tensor(task, device=self.device)
+        return dict(task_ids=task.to(torch.int32).contiguous(), task_emb_table=emb, act_mask_table=mask)
+
+    @torch.no_grad()
+    def model_rollout(self, z0, actions, task=None, target=False, want=("zs", "reward_logits", "reward", "q_logits", "q")):
+        """The open-loop latent rollout of `_update` on recorded actions and the predictions on it (reference tdmpc2.py:268-283)
+        in the library: z0 [B, L], actions [H, B, A] -> dict with the keys in `want` out of zs [H+1, B, L], reward_logits
+        [H, B, bins], reward [H, B, 1], q_logits [num_q, H, B, bins] (every head: Q(..., return_type='all')), q [num_q, H, B, 1],
+        term_logit [H+1, B, 1] (episodic models).  Eval mode: no dropout."""
+        z0 = z0.to(self.device, torch.float32).contiguous()
+        actions = actions.to(self.device, torch.float32).contiguous()
+        return self.planner().model_rollout(z0, actions, use_target=target, want=tuple(want), **self._batch_task_kw(task))
+
+    @torch.no_grad()
+    def model_losses_latent(self, z0, next_z, action, reward, td_targets, terminated=None, task=None, want=("zs",),
+                            step_means=False):
+        """The losses of `_update` (reference tdmpc2.py:285-304) from latents: z0 [B, L] = encode(obs[0]), next_z [H, B, L] =
+        encode(obs[1:]), action [H, B, A], reward / td_targets / terminated [H, B, 1].  Returns the reference's keys
+        consistency_loss, reward_loss, value_loss, termination_loss, total_loss (0-d tensors) plus the outputs in `want`
+        (and step_means [4, H]).  Eval mode: equal to what `_update` logs when cfg.dropout == 0."""
+        cfg, dev = self.cfg, self.device
+        f = lambda x: None if x is None else x.to(dev, torch.float32).contiguous()
+        H, B = action.shape[0], action.shape[1]
+        res = self.planner().model_losses(
+            f(z0), f(action), f(next_z), f(reward).reshape(H, B), f(td_targets).reshape(H, B),
+            None if (terminated is None or not cfg.episodic) else f(terminated).reshape(H, B), rho=cfg.rho,
+            coefs=(cfg.consistency_coef, cfg.reward_coef, cfg.value_coef, cfg.termination_coef), want=tuple(want),
+            step_means=step_means, **self._batch_task_kw(task))
+        losses = res.pop("losses")
+        for i, k in enumerate(("consistency_loss", "reward_loss", "value_loss", "termination_loss", "total_loss")):
+            res[k] = losses[i]
+        return res
+
+    @torch.no_grad()
+    def model_losses(self, obs, action, reward, terminated=None, task=None, pi_eps=None, qidx=None):
+        """The forward half of `_update` (reference tdmpc2.py:259-304) with its argument shapes: obs [H+1, B, *], action
+        [H, B, A], reward / terminated [H, B, 1], task [B].  encode(obs[0]), encode(obs[1:]) (state observations in the library;
+        pixel observations through the PyTorch-ROCm modules), `_td_target`, then the rollout and the losses in one library call.
+        Returns the reference's loss keys plus td_targets [H, B, 1] and zs [H+1, B, L]."""
+        cfg = self.cfg
+        obs = obs.to(self.device)
+        H, B = action.shape[0], action.shape[1]
+        if terminated is None:
+            terminated = torch.zeros(H, B, 1, device=self.device)
+        if self.native_encoder and cfg.obs == "state":
+            flat = obs.reshape((H + 1) * B, -1).to(torch.float32).contiguous()
+            emb = None
+            if cfg.multitask:
+                t = torch.as_tensor(task, device=self.device).long()
+                emb = self.model._task_emb(t.repeat(H + 1)).to(torch.float32).contiguous()
+            z_all = self.planner().encode(flat, emb).reshape(H + 1, B, cfg.latent_dim)
+        else:
+            t = None if task is None else torch.as_tensor(task, device=self.device)
+            z_all = torch.stack([self.model.encode(obs[i], t) for i in range(H + 1)])
+        z0, next_z = z_all[0], z_all[1:].contiguous()
+        td = self._td_target(next_z, reward, terminated, task, pi_eps=pi_eps, qidx=qidx)
+        res = self.model_losses_latent(z0, next_z, action, reward, td, terminated, task)
+        res["td_targets"] = td
+        return res
