@@ -353,6 +353,9 @@ int tdmpc2_plan_td_target_mt(tdmpc2_plan_t *h, int n_rows, const float *next_z, 
  *   soft_ce (math.py:5-9: log_softmax of the logits against two_hot of the target, math.py:58-71) averaged over the batch per
  *   step, rho^t, / steps and for the value loss also / num_q; binary_cross_entropy_with_logits(term_logit[1:], terminated) over all
  *   steps x B rows (0 when not episodic); total = the coefficient-weighted sum.
+ *   Non-finite targets: a NaN in reward / td_target / next_z / terminated makes exactly the losses that consume it NaN (that loss,
+ *   its step_means entry and total; the others keep their bits), as every torch op of the reference propagates it; +-Inf in
+ *   reward / td_target stays finite, the vmin / vmax-clamped bin as in two_hot.
  *   step_means [4, steps] (may be NULL): the unweighted per-step batch means of consistency, reward, value (mean over the heads
  *   too) and termination -- loss against rollout depth.
  * When only losses are asked for, no logits go through HBM.  Deterministic: per-row terms go to a workspace and ONE workgroup adds

@@ -29,20 +29,28 @@ __device__ __forceinline__ void model_row_stats(const float *rp, int part, int n
     val = symexp_f(x / es);
 }
 
-__device__ __forceinline__ float symlog_f(float x) {  // math.py:42-47: sign(x) * log(1 + |x|)
-    const float m = logf(1.f + fabsf(x));
-    return x > 0.f ? m : (x < 0.f ? -m : 0.f);
+// math.py:42-47: sign(x) * log(1 + |x|); +-0 and NaN come back as they are.  The log of the fp32 sum is taken in fp64 and rounded
+// once: near a bin boundary soft_ce amplifies an ulp of it by (l[i0] - l[i1]) / bin_size (4.8e-6 x 1e4 on a one-hot row at the
+// clamp), and logf is only good to an ulp.  Measured on the MI355X with logf: target -22025.4 (symlog -9.999997) on the row
+// "hot0" (-1e4 but bin 0) is 0.043 off, 3.9 x the gate of tests/test_gpu_model_edges.py, which the reference's fp32 meets
+// (DESIGN 3.4d).  One call per row and head, by one lane; ks_value_chain keeps its registers (145 / 174 VGPRs either way).
+__device__ __forceinline__ float symlog_f(float x) {
+    const float m = (float)log((double)(1.f + fabsf(x)));
+    return x > 0.f ? m : (x < 0.f ? -m : x);
 }
 
 // soft_ce(logits, target) of one row (math.py:5-9) with the two target bins picked by index (math.py:58-71): no two-hot
 // row is materialised.  The upper bin wraps to 0 at vmax, where its weight is 0, exactly as the reference's scatter does.
+// +-Inf targets clamp to vmin / vmax like any other; a NaN target gives a NaN term (fminf / fmaxf alone would drop it: every
+// torch op of the reference propagates it), read from bin 0 so that nothing indexes outside the row.
 __device__ __forceinline__ float model_soft_ce(const float *rp, float lse, float target, const ModelLossArgs &a) {
-    const float x = fminf(fmaxf(symlog_f(target), a.vmin), a.vmax);
+    const float s = symlog_f(target);
+    const float x = s != s ? s : fminf(fmaxf(s, a.vmin), a.vmax);
     const float u = (x - a.vmin) / a.bin_size;
     const float fl = floorf(u);
     const float off = u - fl;
-    int i0 = (int)fl;
-    i0 = i0 < 0 ? 0 : (i0 > a.num_bins - 1 ? a.num_bins - 1 : i0);  // (a NaN target must not index outside the row)
+    int i0 = fl == fl ? (int)fl : 0;
+    i0 = i0 < 0 ? 0 : (i0 > a.num_bins - 1 ? a.num_bins - 1 : i0);
     const int i1 = (i0 + 1) % a.num_bins;
     return -((1.f - off) * (rp[i0] - lse) + off * (rp[i1] - lse));
 }

@@ -84,3 +84,108 @@ def losses_from(cfg, zs, reward_logits, q_logits, term_logit, next_z, reward, td
     term = sm[3].mean() if cfg.episodic else 0.0
     total = cfg.consistency_coef * cons + cfg.reward_coef * rew + cfg.termination_coef * term + cfg.value_coef * val
     return np.array([cons, rew, val, term, total], zs.dtype), sm
+
+
+# ---------------------------------------------------------------- pinned logits and edge inputs (tests/test_model_edges.py,
+# tests/test_gpu_model_edges.py).  A head whose last layer has weight 0 and bias l gives the logits l on every row, exactly
+# (0 x + b = b for finite x in either arithmetic): known logits reach the loss kernels through the public entry points.
+EDGE_FLOOR = 1e-5   # the project's loss-stage floor (tests/test_gpu_model.py, "the loss stage alone")
+
+
+def symexp(x):
+    return np.sign(x) * (np.exp(np.abs(x)) - 1)
+
+
+def two_hot_inv_rows(logits, cfg):
+    """two_hot_inv of rows (math.py:74-83): logits [..., bins] -> [...], in the dtype of the logits."""
+    b = np.linspace(cfg.vmin, cfg.vmax, cfg.num_bins).astype(logits.dtype)
+    e = np.exp(logits - logits.max(-1, keepdims=True))
+    p = e / e.sum(-1, keepdims=True)
+    return symexp((p * b).sum(-1))
+
+
+def pin_heads(sd, cfg, reward_row=None, q_rows=None, term_x=None):
+    """A copy of a state dict (torch tensors) with the named heads' last layers pinned: weight 0, bias the given fp32 logits.
+    reward_row [bins]; q_rows [num_q, bins], written to the online and the target ensemble; term_x a scalar."""
+    import torch
+
+    out = {k: torch.as_tensor(v).clone() for k, v in sd.items()}
+
+    def pin(key, bias):
+        b = torch.as_tensor(np.asarray(bias, np.float32)).reshape(out[f"{key}.bias"].shape)
+        out[f"{key}.weight"] = torch.zeros_like(out[f"{key}.weight"])
+        out[f"{key}.bias"] = b.to(out[f"{key}.bias"].dtype)
+
+    if reward_row is not None:
+        pin("_reward.2", reward_row)
+    if q_rows is not None:
+        for key in ("_Qs.params.2", "_target_Qs_params.2", "_detach_Qs_params.2"):
+            if f"{key}.weight" in out:
+                pin(key, q_rows)
+    if term_x is not None:
+        pin("_termination.2", [term_x])
+    return out
+
+
+def edge_gate(v64, v32):
+    """Per element: max(1e-5 max(1, |v|), 2 x |restatement in fp32 - restatement in fp64|), both restatements evaluated on the
+    host from the exact fp32 logits and targets; nothing in it comes from a HIP result."""
+    v64 = np.asarray(v64, np.float64)
+    return np.maximum(EDGE_FLOOR * np.maximum(1.0, np.abs(v64)), 2.0 * np.abs(np.asarray(v32, np.float64) - v64))
+
+
+EDGE_KS = (0, 1, 2, 49, 50, 51, 98, 99, 100)
+
+
+def edge_targets(cfg):
+    """fp32 targets at the edges of symlog / the clamp / the bins: 45 values, padded with three ordinary ones to 6 x 8."""
+    t = [0.0, -0.0, 1e-8, -1e-8, 1e-30, -1e-30]
+    bin_size = (cfg.vmax - cfg.vmin) / (cfg.num_bins - 1)
+    for k in EDGE_KS:
+        c = np.float32(symexp(np.float64(cfg.vmin + k * bin_size)))
+        t += [np.nextafter(c, np.float32(-np.inf)), c, np.nextafter(c, np.float32(np.inf))]
+    t += [22025.4, -22025.4, 22026.5, -22026.5, 22027.0, -22027.0]   # symexp(10) = 22025.47: both sides of the clamp
+    t += [1e6, -1e6, 3e38, -3e38, np.inf, -np.inf]
+    t += [1.0, -2.5, 123.0]
+    return np.array(t, np.float32)
+
+
+EDGE_OFFSETS = (0.0, 30.0, -30.0, 300.0, -300.0)
+UNGATED_ROW = "off+10000"   # lse = m + log(sum) loses the digits of log(sum) at m = 1e4: printed, not gated
+
+
+def edge_logit_rows(cfg):
+    """name -> fp32 logits row [bins] (seeded or literal)."""
+    nb = cfg.num_bins
+    rng = np.random.default_rng(20)
+    rows = {"zero": np.zeros(nb)}
+    for s in (1, 10, 30, 100):
+        rows[f"n{s}"] = rng.standard_normal(nb) * s
+    for j in (0, nb // 2, nb - 1):
+        r = np.full(nb, -1e4)
+        r[j] = 0.0
+        rows[f"hot{j}"] = r
+    r = rng.standard_normal(nb) * 3
+    r[40] = r[41] = r.max() + 1.0
+    rows["twomax"] = r
+    base = rng.standard_normal(nb) * 3
+    for c in EDGE_OFFSETS:
+        rows[f"off{c:+.0f}"] = base.astype(np.float32) + np.float32(c)
+    rows[UNGATED_ROW] = base.astype(np.float32) + np.float32(1e4)
+    return {k: np.asarray(v, np.float32) for k, v in rows.items()}
+
+
+# (row, target) pairs at which the REFERENCE's own fp32 soft_ce leaves the gate (tests/test_model_edges.py measures it): not
+# asked of the library either.  Filled from that test's output; each entry names the measured err / gate.
+EDGE_REMOVED = {}
+
+
+def edge_pairs(cfg):
+    """Every gated (row name, target index) of the edge table."""
+    t = edge_targets(cfg)
+    return [(name, i) for name in edge_logit_rows(cfg) if name != UNGATED_ROW for i in range(len(t))
+            if (name, i) not in EDGE_REMOVED]
+
+
+TERM_XS = (0.0, -0.0, 1e-8, 20.0, -20.0, 88.0, -88.0, 104.0, -104.0, 1e4, -1e4)
+TERM_YS = (0.0, 1.0, 0.3)
