@@ -25,6 +25,9 @@
  *   tdmpc2_plan_act_pi[_pix]  <- TDMPC2.act with cfg.mpc == False       tdmpc2/tdmpc2.py:114-120
  *   tdmpc2_plan_td_target[_mt]    <- TDMPC2._td_target                  tdmpc2/tdmpc2.py:239-254
  *   tdmpc2_plan_policy_value[_mt] <- forward half of TDMPC2.update_pi   tdmpc2/tdmpc2.py:208-225
+ *   tdmpc2_plan_policy_loss[_mt]  <- TDMPC2.update_pi's whole forward   tdmpc2/tdmpc2.py:208-239
+ *   tdmpc2_plan_running_scale     <- RunningScale.update                tdmpc2/common/scale.py:39-42
+ *   tdmpc2_plan_termination_stats <- math.termination_statistics        tdmpc2/common/math.py:97-109
  *   tdmpc2_plan_model_rollout[_mt] <- the open-loop latent rollout and predictions of TDMPC2._update  tdmpc2/tdmpc2.py:268-283
  *   tdmpc2_plan_model_losses[_mt]  <- ... and its four losses                                       tdmpc2/tdmpc2.py:285-304
  *   tdmpc2_plan_export_packed / import_packed <- TDMPC2.save / load of the planner's weights  tdmpc2/tdmpc2.py:72-95
@@ -63,7 +66,7 @@
 extern "C" {
 #endif
 
-#define TDMPC2_PLAN_ABI_VERSION 12
+#define TDMPC2_PLAN_ABI_VERSION 13
 
 typedef struct tdmpc2_plan tdmpc2_plan_t;
 
@@ -391,6 +394,61 @@ int tdmpc2_plan_model_losses(tdmpc2_plan_t *h, int batch, int steps, const float
 int tdmpc2_plan_model_losses_mt(tdmpc2_plan_t *h, int batch, int steps, const float *z0, const float *actions,
                                 const tdmpc2_task_tables *tasks, int use_target, const tdmpc2_model_targets *targets,
                                 const tdmpc2_model_out *out, float *losses, float *step_means, void *stream);
+
+/* Policy loss (ABI 13): the forward of TDMPC2.update_pi (tdmpc2/tdmpc2.py:208-239), with the running Q scale.  Forward only, EVAL
+ * MODE (the caveat of model_losses applies: the reference's dropout on the Q heads' first layer is active inside update_pi), fp32
+ * in / fp32 out, no gradients.
+ *   action, info = pi(zs, task)         pi_eps [steps + 1, B, A], or Philox(seed) when NULL; the call advances the handle's
+ *                                       counter by one, as policy_value does
+ *   qs = Q(zs, action, 'avg')           two heads of the ONLINE ensemble (the reference's _detach_Qs carries the same weights):
+ *                                       qidx (device int32[2]) or drawn once per call like randperm(num_q)[:2]
+ *   scale.update(qs[0]); qs /= scale    update_scale = 1: *scale is lerped towards max(p95 - p5, 1) of q[0] BEFORE the division, as
+ *                                       update_pi does; 0: *scale is read only
+ *   pi_loss = mean_t(-mean_B(entropy_coef * scaled_entropy + qs) * rho^t) over the steps + 1 rows of zs.
+ * zs [steps + 1, B, L], 0 <= steps <= 8.  scale: DEVICE float[1] (RunningScale.value).  loss: DEVICE float[4] = pi_loss, mean
+ * entropy, mean scaled_entropy, the scale after the call.  _mt: tasks->task_ids is [B] as in model_rollout_mt; the action mask and
+ * action_dims of a row are its task's.
+ * Rows (both kernel families, both arithmetics): the value chain of policy_value with the entropy terms of WorldModel.pi per row
+ * (log_prob = sum_a(-0.5 eps^2 - log_std - log(2 pi)/2), the squash correction sum_a log(relu(1 - a^2) + 1e-6), entropy =
+ * -log_prob, scaled_entropy = -log_prob * scaled / (log_prob + 1e-8)): FUSED ks_value_ent, one launch; LAYERED the GEMM chain of
+ * lay_value with the row kernel l_pi_head_ent, in pieces of max_envs x num_samples rows when the call has more (the two heads are
+ * drawn once per call and a row's Philox / tape index is its row in the call: piece boundaries change no bit).  q, entropy and
+ * scaled_entropy go to a workspace; k_running_scale, then k_policy_loss_tail -- ONE workgroup each, fixed order, no float atomics:
+ * the same inputs give the same bits whatever optional outputs are asked for.  No new inter-workgroup wait; the LAYERED GEMMs keep
+ * their fault contract: NaN in every output, *scale left as it was, tdmpc2_plan_take_fault.  The workspace grows at the first call
+ * of a shape (keep that call outside a hipGraph capture); after it the call allocates nothing, never synchronises the host and
+ * can be captured.
+ * Refusals: NULL zs / in / scale / loss, batch < 1, steps outside [0, 8], tasks on a single-task handle (or none on a multitask
+ * one) -- TDMPC2_ERR_INVALID; update_scale with batch > 16384 (the percentile kernel's limit) -- TDMPC2_ERR_UNSUPPORTED. */
+typedef struct tdmpc2_policy_loss_in {
+    float rho, entropy_coef, tau;   /* config.yaml rho, entropy_coef, tau */
+    int update_scale;               /* 1: RunningScale.update(qs[0]) BEFORE the division, as update_pi does; 0: divide by *scale as it is */
+} tdmpc2_policy_loss_in;
+typedef struct tdmpc2_policy_loss_out {  /* device pointers, any may be NULL */
+    float *action;          /* [steps+1, B, A] */
+    float *q;               /* [steps+1, B]  avg of the two heads, UNSCALED */
+    float *entropy;         /* [steps+1, B]  info["entropy"] */
+    float *scaled_entropy;  /* [steps+1, B]  info["scaled_entropy"] */
+    float *step_means;      /* [3, steps+1]  per-step batch means of q/scale, scaled_entropy, entropy */
+    float *percentiles;     /* [2]           the 5th / 95th percentile of q[0] (written only when update_scale) */
+} tdmpc2_policy_loss_out;
+int tdmpc2_plan_policy_loss(tdmpc2_plan_t *h, int batch, int steps, const float *zs, const float *pi_eps, const int32_t *qidx,
+                            uint64_t seed, const tdmpc2_policy_loss_in *in, float *scale, const tdmpc2_policy_loss_out *out,
+                            float *loss, void *stream);
+int tdmpc2_plan_policy_loss_mt(tdmpc2_plan_t *h, int batch, int steps, const float *zs, const tdmpc2_task_tables *tasks,
+                               const float *pi_eps, const int32_t *qidx, uint64_t seed, const tdmpc2_policy_loss_in *in,
+                               float *scale, const tdmpc2_policy_loss_out *out, float *loss, void *stream);
+/* RunningScale.update alone (common/scale.py:21-42): x [n] (device) -> *scale += tau (max(p95 - p5, 1) - *scale); percentiles [2]
+ * optional.  torch.sort's order (NaN last, after +Inf); positions pct (n - 1) / 100, floor, min(floor + 1, n - 1) and the weights
+ * in fp32, products and sum unfused, as the reference forms them.  Non-finite inputs give what the formula gives (a NaN that the
+ * order statistics do not touch leaves the scale finite).  Any handle (no weights needed).  n < 1 or NULL x / scale --
+ * TDMPC2_ERR_INVALID; n > 16384 -- TDMPC2_ERR_UNSUPPORTED. */
+int tdmpc2_plan_running_scale(tdmpc2_plan_t *h, int n, const float *x, float tau, float *scale, float *percentiles, void *stream);
+/* math.termination_statistics(sigmoid(term_logit), terminated) (common/math.py:97-109): n rows (device) -> stats [2] = rate, f1.
+ * pred = sigmoid(logit) > 0.5 with the library's fp32 sigmoid; integer tp / fn / fp counts; eps = 1e-9.  n < 1 or a NULL
+ * pointer -- TDMPC2_ERR_INVALID. */
+int tdmpc2_plan_termination_stats(tdmpc2_plan_t *h, int n, const float *term_logit, const float *terminated, float *stats,
+                                  void *stream);
 
 /* Packed weight file (the native counterpart of TDMPC2.save / load, tdmpc2.py:72-95).
  * export_packed copies everything the binds produced -- weights in MFMA fragment order (hi / lo split and scaled for the

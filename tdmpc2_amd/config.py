@@ -46,6 +46,9 @@ class Config:
     reward_coef: float = 0.1
     value_coef: float = 0.1
     termination_coef: float = 1.0
+    # policy loss and its running Q scale (config.yaml:25,47): read by TDMPC2.policy_loss, the forward of update_pi
+    entropy_coef: float = 1e-4
+    tau: float = 0.01
     # actor (config.yaml:44-47)
     log_std_min: float = -10.0
     log_std_max: float = 2.0

@@ -9,8 +9,10 @@
 #   k_policy.hip               policy prior (WorldModel.pi, act() with mpc = False): row route, GEMV, head
 #   k_model.hip   x {16,32,48,64}   ks_value_roll / ks_value_chain (model rollout and losses, fused family)
 #   k_model.hip                generic unit (no TU_APAD): the loss row kernels of both families
+#   k_policy_loss.hip x {16,32,48,64}   ks_value_ent (update_pi's forward per row, fused family)
+#   k_policy_loss.hip          generic unit: running scale, policy-loss tail, termination statistics
 # Objects are cached under build/ and rebuilt when a source they include is newer (make-style), so an experiment on one
-# family recompiles one file.  TDMPC2_EXTRA_FLAGS (all units), TDMPC2_FLAGS_<unit> (one unit: main, fused, cluster, layered, policy, model),
+# family recompiles one file.  TDMPC2_EXTRA_FLAGS (all units), TDMPC2_FLAGS_<unit> (one unit: main, fused, cluster, layered, policy, model, ploss),
 # TDMPC2_ONLY_APAD=48 (experiment builds: the fused / cluster units of one padding only), TDMPC2_OUT, TDMPC2_BUILD_DIR, JOBS.
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
@@ -33,10 +35,12 @@ UNITS+=("main|tdmpc2_plan.hip|${ONLY} ${TDMPC2_FLAGS_main:-}")
 UNITS+=("layered|k_layered.hip|${TDMPC2_FLAGS_layered:-}")
 UNITS+=("policy|k_policy.hip|${TDMPC2_FLAGS_policy:-}")
 UNITS+=("model|k_model.hip|${TDMPC2_FLAGS_model:-}")
+UNITS+=("ploss|k_policy_loss.hip|${TDMPC2_FLAGS_ploss:-}")
 for ap in ${APADS}; do
     UNITS+=("fused${ap}|k_fused.hip|-DTU_APAD=${ap} ${TDMPC2_FLAGS_fused:-}")
     UNITS+=("cluster${ap}|k_cluster.hip|-DTU_APAD=${ap} ${TDMPC2_FLAGS_cluster:-}")
     UNITS+=("model${ap}|k_model.hip|-DTU_APAD=${ap} ${TDMPC2_FLAGS_model:-}")
+    UNITS+=("ploss${ap}|k_policy_loss.hip|-DTU_APAD=${ap} ${TDMPC2_FLAGS_ploss:-}")
 done
 
 compile_unit() {  # name src flags

@@ -215,6 +215,13 @@ struct ValueParamsT {
     const float *disc_tab;   // [n_tasks] or null (scalar `discount`)
 };
 
+// ks_value_ent: the same rows with the policy head's entropy terms (tdmpc2_plan_policy_loss)
+template <class NET>
+struct ValueEntParamsT : ValueParamsT<NET> {
+    float *entropy, *scaled_entropy;  // [rows] each
+    int task_mod;                     // multitask: task of row r = task_ids[r % task_mod] (rows = [steps + 1, B], task_ids [B])
+};
+
 // net slots inside `beff`
 enum { BE_DYN = 0, BE_REW = 1, BE_PI = 2, BE_Q0 = 3 };
 

@@ -112,6 +112,9 @@ struct tdmpc2_plan {
     // the per-row loss terms [3 + num_q][H B]; grown at first use
     float *model_zs = nullptr, *model_rowloss = nullptr;
     size_t model_zs_cap = 0, model_rowloss_cap = 0;
+    // per-row q | entropy | scaled_entropy of tdmpc2_plan_policy_loss (grown on demand)
+    float *ploss_rows = nullptr;
+    size_t ploss_rows_cap = 0;
     // cluster path of the fused family (cluster_kernels.cuh): single-plan latency
     int cluster_mode = 2;            // TDMPC2_TUNE_CLUSTER: 0 never, 1 whenever the call fits, 2 auto (= 1 today)
     int cl_max_clusters = 0;         // clusters the buffers below were sized for (0: path not available on this handle)

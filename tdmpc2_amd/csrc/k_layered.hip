@@ -10,6 +10,7 @@ namespace {
 #include "layered_wide.cuh"
 #include "layered_mid.cuh"
 #include "model_layered.cuh"  // model rollout / losses: row kernels
+#include "policy_loss_layered.cuh"  // policy loss: the policy head row kernel with the entropy terms
 }  // namespace
 
 namespace tdk {

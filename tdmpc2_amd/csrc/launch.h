@@ -86,7 +86,8 @@ int lay_run(tdmpc2_plan *h, hipStream_t st, int E, const float *z0, const float 
             float *action, const tdmpc2_debug *dbg);
 int lay_value(tdmpc2_plan *h, hipStream_t st, int rows, const float *z, bool target, bool reduce_min, const float *pi_eps,
               const int *qidx_dev /* [2] */, unsigned long long seed, unsigned call, const float *reward, const float *terminated,
-              float discount, const int *row_task /* padded [rows_p] or null */, float *action, float *out);
+              float discount, const int *row_task /* padded [rows_p] or null */, float *action, float *out, int n_off = 0,
+              float *entropy = nullptr, float *scaled_entropy = nullptr);  // (policy loss: a piece of rows, the entropy terms)
 // one CEM iteration's sampled actions (rows n >= P of h->actions, every step) and its two Q heads per plan -> qbuf [E, 2]
 // (used by both families when a plan is sharded: tdmpc2_plan_shard_values)
 int lay_sample_iteration(tdmpc2_plan *h, hipStream_t st, int E, int iter, const float *act_mask, const tdmpc2_noise *tape,
@@ -110,6 +111,18 @@ int model_launch_tile_tasks(const int *task_ids, int B, int rows, int rows_p, in
 // row -> task map tiled over (H + 1) * B rows and padded, or null.
 int lay_model(tdmpc2_plan *h, hipStream_t st, const ModelRoute &r, int B, int H, const float *actions, float *zs, bool target,
               const int *row_task, const ModelOutArgs &out, const ModelLossArgs &ls);
+
+// ---- policy loss (k_policy_loss.hip per action padding: ks_value_ent of the fused family; its generic unit: the one-workgroup kernels)
+#include "policy_loss_params.h"
+struct PolicyLossOps {
+    void (*value_ent)(int ar, const ValueEntParamsT<NetS> &p, int grid, size_t lds, hipStream_t st);
+    int (*set_lds)(int ar, size_t lds_bytes);
+};
+const PolicyLossOps &policy_loss_ops_ap16(); const PolicyLossOps &policy_loss_ops_ap32(); const PolicyLossOps &policy_loss_ops_ap48(); const PolicyLossOps &policy_loss_ops_ap64();
+int pl_set_lds();  // k_running_scale's dynamic LDS limit (once per handle, at creation)
+int pl_launch_scale(const RunningScaleParams &p, hipStream_t st);
+int pl_launch_tail(const PolicyLossTailParams &p, hipStream_t st);
+int pl_launch_term_stats(const TerminationStatsParams &p, hipStream_t st);
 
 // ---- policy prior (k_policy.hip)
 int pol_set_lds();  // the GEMV instantiations' dynamic LDS limit (once per handle, at bind)

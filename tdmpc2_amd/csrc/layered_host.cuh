@@ -255,7 +255,8 @@ int lay_dynamics(tdmpc2_plan *h, hipStream_t st, size_t rows, size_t rows_p, int
 // a <- pi(z) into X[:, L:L+A) (+ actions[e, t, n < P] for the policy-prior trajectories)  (world_model.py:144-184)
 int lay_policy(tdmpc2_plan *h, hipStream_t st, size_t rows, size_t rows_p, int rpe, int nvalid, const float *mask,
                const float *eps, long eps_estride, unsigned long long seed, unsigned call, int site, int iter,
-               float *actions, int t, float *trace = nullptr, int n_off = 0) {
+               float *actions, int t, float *trace = nullptr, int n_off = 0, float *entropy = nullptr,
+               float *scaled_entropy = nullptr) {
     const Layered &L = h->lay;
     const tdmpc2_plan_cfg &c = h->cfg;
     int rc;
@@ -268,6 +269,13 @@ int lay_policy(tdmpc2_plan *h, hipStream_t st, size_t rows, size_t rows_p, int r
     p.X = L.X; p.actions = actions; p.t = t; p.H = c.horizon; p.N = c.num_samples; p.trace = trace;
     p.row_env = L.row_env; p.n_off = n_off;
     if (L.row_env) { p.H = 1; p.N = (int)rows; }  // value mode: actions is a flat [rows, A] output
+    if (entropy) {  // policy loss: one wavefront per row, the entropy terms of the row beside its action
+        const dim3 grid((unsigned)((rows + 3) / 4));
+        if (h->split) hipLaunchKernelGGL(l_pi_head_ent<true>, grid, dim3(256), 0, st, p, entropy, scaled_entropy);
+        else hipLaunchKernelGGL(l_pi_head_ent<false>, grid, dim3(256), 0, st, p, entropy, scaled_entropy);
+        LAUNCH_CHECK();
+        return 0;
+    }
     const int total = (int)rows * c.action_dim;
     if (h->split) hipLaunchKernelGGL(l_pi_head_s, dim3((total + 255) / 256), dim3(256), 0, st, p);
     else hipLaunchKernelGGL(l_pi_head, dim3((total + 255) / 256), dim3(256), 0, st, p);
@@ -835,7 +843,8 @@ int lay_run(tdmpc2_plan *h, hipStream_t st, int E, const float *z0, const float 
 // selecting the first-layer bias, action mask and discount of each row.
 int lay_value(tdmpc2_plan *h, hipStream_t st, int rows, const float *z, bool target, bool reduce_min, const float *pi_eps,
               const int *qidx_dev /* [2] */, unsigned long long seed, unsigned call, const float *reward, const float *terminated,
-              float discount, const int *row_task /* padded [rows_p] or null */, float *action, float *out) {
+              float discount, const int *row_task /* padded [rows_p] or null */, float *action, float *out, int n_off,
+              float *entropy, float *scaled_entropy) {
     const tdmpc2_plan_cfg &c = h->cfg;
     Layered &L = h->lay;
     const size_t rows_p = round_up((size_t)rows, GBM);
@@ -855,8 +864,9 @@ int lay_value(tdmpc2_plan *h, hipStream_t st, int rows, const float *z, bool tar
     if (c.multitask) { L.bias_tab = h->beff_tab; L.row_env = row_task; }
     int rc;
     // a = pi(z): into the action columns of X, and into `action` [rows, A] when asked for
+    // (n_off: the call's row index of this piece's first row -- the Philox / tape index of a row does not depend on the pieces)
     if ((rc = lay_policy(h, st, (size_t)rows, rows_p, rpe, rows, c.multitask ? h->mask_tab : nullptr, pi_eps, 0, seed, call, SITE_PI, 0,
-                         action, 0))) return rc;
+                         action, 0, nullptr, n_off, entropy, scaled_entropy))) return rc;
     for (int j = 0; j < 2; ++j) {
         if ((rc = lay_hidden(h, st, L.qarr[0], BE_Q0, (size_t)rows, rows_p, rpe, qidx_dev + j, true))) return rc;
         if ((rc = lay_gemm(h, st, L.HB, L.Mp, rows_p, rpe, L.qarr[0].l[2], q_wstride(h, 2), q_bstride(h, 2), -1, qidx_dev + j, L.LG,

@@ -387,6 +387,21 @@ const ModelOps &model_ops(int apad) {
     }
 #endif
 }
+const PolicyLossOps &policy_loss_ops(int apad) {
+#ifdef TDMPC2_ONLY_APAD
+#define TDK_PLOPS_CAT_(a, b) a##b
+#define TDK_PLOPS_CAT(a, b) TDK_PLOPS_CAT_(a, b)
+    (void)apad;
+    return TDK_PLOPS_CAT(policy_loss_ops_ap, TDMPC2_ONLY_APAD)();
+#else
+    switch (apad) {
+        case 16: return policy_loss_ops_ap16();
+        case 32: return policy_loss_ops_ap32();
+        case 48: return policy_loss_ops_ap48();
+        default: return policy_loss_ops_ap64();
+    }
+#endif
+}
 const FusedOps &fused_ops(int apad) {
 #ifdef TDMPC2_ONLY_APAD  // experiment builds (tools/ablate.sh): one action padding only, a quarter of the compile time
 #define TDK_OPS_CAT_(a, b) a##b
@@ -978,10 +993,15 @@ int tdmpc2_plan_create(const tdmpc2_plan_cfg *cfg, tdmpc2_plan_t **out) {
         tdmpc2_plan_destroy(h);
         return fail(TDMPC2_ERR_HIP, "hipEventCreate failed");
     }
+    if (pl_set_lds()) {  // (both families: the running scale's key array)
+        tdmpc2_plan_destroy(h);
+        return TDMPC2_ERR_HIP;
+    }
     if (!h->lay.on) {
         const int ar = h->split ? 0 : 1;
         rc = fused_ops(h->Apad).set_lds(ar, c.episodic, h->lds_bytes);
         if (!rc) rc = model_ops(h->Apad).set_lds(ar, h->lds_bytes);
+        if (!rc) rc = policy_loss_ops(h->Apad).set_lds(ar, h->lds_bytes);
         if (rc) {
             tdmpc2_plan_destroy(h);
             return TDMPC2_ERR_HIP;
@@ -1904,6 +1924,107 @@ int tdmpc2_plan_model_losses(tdmpc2_plan_t *h, int batch, int steps, const float
                              const tdmpc2_model_targets *targets, const tdmpc2_model_out *out, float *losses, float *step_means,
                              void *stream) {
     return tdmpc2_plan_model_losses_mt(h, batch, steps, z0, actions, nullptr, use_target, targets, out, losses, step_means, stream);
+}
+
+// ---------------------------------------------------------------- policy loss: the forward of TDMPC2.update_pi (tdmpc2/tdmpc2.py:208-239)
+// ks_value_ent (pi + two online Q heads + the entropy terms, per row into the handle's workspace), then one workgroup each for
+// RunningScale.update on q[0] and for the fixed-order tail.
+namespace {
+int launch_policy_loss(tdmpc2_plan *h, int B, int steps, const float *zs, const tdmpc2_task_tables *tk, const float *pi_eps,
+                       const int32_t *qidx, uint64_t seed, const tdmpc2_policy_loss_in *in, float *scale,
+                       const tdmpc2_policy_loss_out *out, float *loss, hipStream_t st) {
+    const tdmpc2_plan_cfg &c = h->cfg;
+    static const tdmpc2_policy_loss_out none{};
+    if (!out) out = &none;
+    if (B < 1) return fail(TDMPC2_ERR_INVALID, "batch %d < 1", B);
+    if (steps < 0 || steps > PL_MAX_STEPS) return fail(TDMPC2_ERR_INVALID, "steps %d outside [0, %d]", steps, (int)PL_MAX_STEPS);
+    if (c.multitask) {
+        if (!tk || !tk->task_ids || !tk->task_emb || !tk->act_mask || tk->n_tasks < 1)
+            return fail(TDMPC2_ERR_INVALID, "multitask policy_loss needs the row -> task map and the per-task tables");
+    } else if (tk) {
+        return fail(TDMPC2_ERR_INVALID, "task tables given to a single-task handle");
+    }
+    if (in->update_scale && B > PL_SCALE_MAX_N)
+        return fail(TDMPC2_ERR_UNSUPPORTED, "the running scale takes at most %d values; got batch %d", (int)PL_SCALE_MAX_N, B);
+    int rc = check_ready(h);
+    if (rc) return rc;
+    (void)fault_poll(h);
+    if (!h->in_shard && (rc = fault_fresh(h, st))) return rc;
+    const unsigned call = h->call++;
+    const int T = steps + 1;
+    const size_t rows = (size_t)T * B;
+    if ((rc = grow_ws(h, &h->ploss_rows, &h->ploss_rows_cap, 3 * rows, st))) return rc;
+    float *wq = h->ploss_rows, *went = wq + rows, *wsent = went + rows;
+    const unsigned int *err = nullptr;
+    if (h->lay.on) {
+        // LAYERED: pi, then the two heads, as lay_value runs them -- in pieces of the workspace's rows (max_envs x num_samples) when
+        // the call has more; the two heads are drawn once, and a row's noise index is its row in the call, whatever the pieces
+        const size_t cap = round_up((size_t)c.max_envs * c.num_samples, GBM), rows_p = round_up(rows, GBM);
+        if (c.multitask) {
+            if ((rc = build_task_tables(h, tk, false, rows_p, st))) return rc;
+            if ((rc = model_launch_tile_tasks(tk->task_ids, B, (int)rows, (int)rows_p, h->task_rows, st))) return rc;
+        }
+        if ((rc = lay_set_qidx(h, st, 1, qidx, 2L, c.num_q, 0, seed, call, h->lay.qidx))) return rc;
+        for (size_t r0 = 0; r0 < rows; r0 += cap) {
+            const int n = (int)std::min(cap, rows - r0);
+            if ((rc = lay_value(h, st, n, zs + r0 * c.latent_dim, false, false, pi_eps, h->lay.qidx, seed, call, nullptr, nullptr, 0.f,
+                                c.multitask ? h->task_rows + r0 : nullptr, out->action ? out->action + r0 * c.action_dim : nullptr,
+                                wq + r0, (int)r0, went + r0, wsent + r0))) return rc;
+        }
+        err = (h->split && h->lay.fuse_ln) ? h->cl_err_dev : nullptr;
+    } else {
+        if (c.multitask && (rc = build_task_tables(h, tk, false, 0, st))) return rc;
+        ValueEntParamsT<NetS> p{};
+        p.rows = (int)rows; p.A = c.action_dim; p.Apad = h->Apad; p.nq = c.num_q; p.num_bins = c.num_bins; p.reduce_min = 0;
+        p.log_std_min = c.log_std_min; p.log_std_dif = c.log_std_dif;
+        p.pi = to_dev<NetS>(h->pi);
+        for (int i = 0; i < c.num_q; ++i) p.q[i] = to_dev<NetS>(h->q[i]);
+        p.bins = h->bins; p.z = zs; p.pi_eps = pi_eps; p.qidx = qidx; p.seed = seed; p.call = call;
+        p.action = out->action; p.out = wq; p.entropy = went; p.scaled_entropy = wsent;
+        p.nnets = h->nnets;
+        if (c.multitask) { p.task_ids = tk->task_ids; p.beff_tab = h->beff_tab; p.mask_tab = h->mask_tab; p.task_mod = B; }
+        policy_loss_ops(h->Apad).value_ent(h->split ? 0 : 1, p, (int)((rows + ROWS - 1) / ROWS), h->lds_bytes, st);
+        HIP_TRY(hipGetLastError());
+    }
+    if (in->update_scale && (rc = pl_launch_scale(RunningScaleParams{wq, B, in->tau, scale, out->percentiles, err}, st))) return rc;
+    PolicyLossTailParams tp{};
+    tp.q = wq; tp.entropy = went; tp.scaled_entropy = wsent; tp.scale = scale; tp.B = B; tp.T = T; tp.entropy_coef = in->entropy_coef;
+    for (int t = 0; t < T; ++t) tp.rho_pow[t] = std::pow(in->rho, (float)t);  // torch.pow(rho, arange) in fp32 (tdmpc2.py:227)
+    tp.step_means = out->step_means; tp.loss = loss; tp.err = err;
+    tp.action = out->action; tp.A = c.action_dim;
+    if ((rc = pl_launch_tail(tp, st))) return rc;
+    if (out->q) HIP_TRY(hipMemcpyAsync(out->q, wq, rows * 4, hipMemcpyDeviceToDevice, st));
+    if (out->entropy) HIP_TRY(hipMemcpyAsync(out->entropy, went, rows * 4, hipMemcpyDeviceToDevice, st));
+    if (out->scaled_entropy) HIP_TRY(hipMemcpyAsync(out->scaled_entropy, wsent, rows * 4, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+}  // namespace
+
+int tdmpc2_plan_policy_loss_mt(tdmpc2_plan_t *h, int batch, int steps, const float *zs, const tdmpc2_task_tables *tasks,
+                               const float *pi_eps, const int32_t *qidx, uint64_t seed, const tdmpc2_policy_loss_in *in,
+                               float *scale, const tdmpc2_policy_loss_out *out, float *loss, void *stream) {
+    if (!h || !zs || !in || !scale || !loss) return fail(TDMPC2_ERR_INVALID, "null argument");
+    ENTER_ON(h, stream);
+    return launch_policy_loss(h, batch, steps, zs, tasks, pi_eps, qidx, seed, in, scale, out, loss, (hipStream_t)stream);
+}
+int tdmpc2_plan_policy_loss(tdmpc2_plan_t *h, int batch, int steps, const float *zs, const float *pi_eps, const int32_t *qidx,
+                            uint64_t seed, const tdmpc2_policy_loss_in *in, float *scale, const tdmpc2_policy_loss_out *out,
+                            float *loss, void *stream) {
+    return tdmpc2_plan_policy_loss_mt(h, batch, steps, zs, nullptr, pi_eps, qidx, seed, in, scale, out, loss, stream);
+}
+int tdmpc2_plan_running_scale(tdmpc2_plan_t *h, int n, const float *x, float tau, float *scale, float *percentiles, void *stream) {
+    if (!h || !x || !scale) return fail(TDMPC2_ERR_INVALID, "null argument");
+    if (n < 1) return fail(TDMPC2_ERR_INVALID, "n %d < 1", n);
+    if (n > PL_SCALE_MAX_N) return fail(TDMPC2_ERR_UNSUPPORTED, "the running scale takes at most %d values; got %d", (int)PL_SCALE_MAX_N, n);
+    ENTER_ON(h, stream);
+    return pl_launch_scale(RunningScaleParams{x, n, tau, scale, percentiles, nullptr}, (hipStream_t)stream);
+}
+int tdmpc2_plan_termination_stats(tdmpc2_plan_t *h, int n, const float *term_logit, const float *terminated, float *stats,
+                                  void *stream) {
+    if (!h || !term_logit || !terminated || !stats) return fail(TDMPC2_ERR_INVALID, "null argument");
+    if (n < 1) return fail(TDMPC2_ERR_INVALID, "n %d < 1", n);
+    ENTER_ON(h, stream);
+    return pl_launch_term_stats(TerminationStatsParams{term_logit, terminated, n, stats}, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------- one plan sharded over several GPUs (last row)

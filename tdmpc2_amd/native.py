@@ -17,7 +17,7 @@ import torch
 _LIB_PATH = os.environ.get("TDMPC2_PLAN_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtdmpc2_plan.so")
 _lib = None
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 # every symbol include/tdmpc2_plan.h declares (tests check the .so exports all of them)
 ABI_SYMBOLS = [
@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "tdmpc2_plan_bind_pixel_encoder", "tdmpc2_plan_encode_pix", "tdmpc2_plan_run_pix",
     "tdmpc2_plan_bind_policy", "tdmpc2_plan_pi", "tdmpc2_plan_act_pi", "tdmpc2_plan_act_pi_pix",
     "tdmpc2_plan_model_rollout", "tdmpc2_plan_model_rollout_mt", "tdmpc2_plan_model_losses", "tdmpc2_plan_model_losses_mt",
+    "tdmpc2_plan_policy_loss", "tdmpc2_plan_policy_loss_mt", "tdmpc2_plan_running_scale", "tdmpc2_plan_termination_stats",
 ]
 
 NET_DYNAMICS, NET_REWARD, NET_PI, NET_Q, NET_TERMINATION, NET_TARGET_Q = range(6)
@@ -77,6 +78,20 @@ class ModelTargets(C.Structure):
 
 
 MODEL_OUTPUTS = ("zs", "reward_logits", "reward", "q_logits", "q", "term_logit")
+
+
+class PolicyLossIn(C.Structure):
+    """struct tdmpc2_policy_loss_in."""
+    _fields_ = [("rho", C.c_float), ("entropy_coef", C.c_float), ("tau", C.c_float), ("update_scale", C.c_int32)]
+
+
+POLICY_LOSS_OUTPUTS = ("action", "q", "entropy", "scaled_entropy", "step_means", "percentiles")
+RUNNING_SCALE_MAX_N = 16384  # tdmpc2_plan_running_scale / the batch of a policy_loss call that updates the scale
+
+
+class PolicyLossOut(C.Structure):
+    """struct tdmpc2_policy_loss_out: optional device outputs of the policy loss."""
+    _fields_ = [(n, C.c_void_p) for n in POLICY_LOSS_OUTPUTS]
 
 
 class PolicyOut(C.Structure):
@@ -182,6 +197,15 @@ def _open(path):
     lib.tdmpc2_plan_model_losses_mt.argtypes = [vp, i32, i32, vp, vp, C.POINTER(TaskTables), i32, C.POINTER(ModelTargets),
                                                 C.POINTER(ModelOut), vp, vp, vp]
     lib.tdmpc2_plan_model_losses_mt.restype = i32
+    lib.tdmpc2_plan_policy_loss_mt.argtypes = [vp, i32, i32, vp, C.POINTER(TaskTables), vp, vp, u64, C.POINTER(PolicyLossIn), vp,
+                                               C.POINTER(PolicyLossOut), vp, vp]
+    lib.tdmpc2_plan_policy_loss_mt.restype = i32
+    lib.tdmpc2_plan_policy_loss.argtypes = [vp, i32, i32, vp, vp, vp, u64, C.POINTER(PolicyLossIn), vp, C.POINTER(PolicyLossOut), vp, vp]
+    lib.tdmpc2_plan_policy_loss.restype = i32
+    lib.tdmpc2_plan_running_scale.argtypes = [vp, i32, vp, C.c_float, vp, vp, vp]
+    lib.tdmpc2_plan_running_scale.restype = i32
+    lib.tdmpc2_plan_termination_stats.argtypes = [vp, i32, vp, vp, vp, vp]
+    lib.tdmpc2_plan_termination_stats.restype = i32
     lib.tdmpc2_plan_packed_size.argtypes = [vp, C.POINTER(u64)]
     lib.tdmpc2_plan_packed_size.restype = i32
     lib.tdmpc2_plan_export_packed.argtypes = [vp, vp, u64, vp]
@@ -789,6 +813,64 @@ class NativePlanner:
                                                              C.byref(tg), C.byref(mo), _ptr(res["losses"]),
                                                              _ptr(res.get("step_means")), self._stream()))
         return res
+
+    def policy_loss(self, zs, scale, rho=0.5, entropy_coef=1e-4, tau=0.01, update_scale=True, pi_eps=None, qidx=None, seed: int = 0,
+                    want=(), task_ids=None, task_emb_table=None, act_mask_table=None):
+        """The forward of TDMPC2.update_pi (tdmpc2.py:208-239): zs [T, B, L], `scale` the fp32 [1] device tensor RunningScale.value
+        (updated in place from q[0] before the division when `update_scale`).  Returns a dict: "loss" [4] (pi_loss, mean entropy,
+        mean scaled_entropy, the scale after the call) and the outputs named in `want` (tdmpc2_policy_loss_out: action [T, B, A],
+        q / entropy / scaled_entropy [T, B, 1], step_means [3, T], percentiles [2]).  Multitask models: `task_ids` int32 [B]."""
+        cfg, dev = self.cfg, self.device
+        T, B = int(zs.shape[0]), int(zs.shape[1])
+        _chk_tensor("zs", zs, torch.float32, (T, B, cfg.latent_dim), dev)
+        _chk_tensor("scale", scale, torch.float32, (1,), dev)
+        if pi_eps is not None:
+            _chk_tensor("pi_eps", pi_eps, torch.float32, (T, B, cfg.action_dim), dev)
+        if qidx is not None:
+            _chk_tensor("qidx", qidx, torch.int32, (2,), dev)
+        tt, keep = self._task_tables(B, task_ids, task_emb_table, act_mask_table)
+        shapes = {"action": (T, B, cfg.action_dim), "q": (T, B, 1), "entropy": (T, B, 1), "scaled_entropy": (T, B, 1),
+                  "step_means": (3, T), "percentiles": (2,)}
+        for k in want:
+            if k not in shapes:
+                raise ValueError(f"unknown policy_loss output {k!r} (one of {POLICY_LOSS_OUTPUTS})")
+        res = {k: torch.empty(shapes[k], device=dev) for k in want}
+        po = PolicyLossOut(**{k: (res[k].data_ptr() if k in res else None) for k in POLICY_LOSS_OUTPUTS})
+        pin = PolicyLossIn(rho=float(rho), entropy_coef=float(entropy_coef), tau=float(tau), update_scale=int(bool(update_scale)))
+        res["loss"] = torch.empty(4, device=dev)
+        with torch.cuda.device(dev):
+            self._check(self.lib.tdmpc2_plan_policy_loss_mt(self._h, B, T - 1, _ptr(zs), tt, _ptr(pi_eps), _ptr(qidx),
+                                                            C.c_uint64(int(seed) & (2**64 - 1)), C.byref(pin), _ptr(scale),
+                                                            C.byref(po), _ptr(res["loss"]), self._stream()))
+        return res
+
+    def running_scale(self, x, scale, tau=0.01, percentiles=None):
+        """RunningScale.update (common/scale.py:39-42): x (any shape, n values) lerps the fp32 [1] device tensor `scale` in place;
+        `percentiles` (fp32 [2] device tensor, optional) receives the 5th / 95th percentile."""
+        dev = self.device
+        n = int(x.numel())
+        _chk_tensor("x", x, torch.float32, tuple(x.shape), dev)
+        _chk_tensor("scale", scale, torch.float32, (1,), dev)
+        if percentiles is not None:
+            _chk_tensor("percentiles", percentiles, torch.float32, (2,), dev)
+        with torch.cuda.device(dev):
+            self._check(self.lib.tdmpc2_plan_running_scale(self._h, n, _ptr(x), C.c_float(float(tau)), _ptr(scale), _ptr(percentiles),
+                                                           self._stream()))
+        return scale
+
+    def termination_stats(self, term_logit, terminated):
+        """math.termination_statistics(sigmoid(term_logit), terminated) (common/math.py:97-109): n rows each -> fp32 [2] = rate, f1."""
+        dev = self.device
+        n = int(term_logit.numel())
+        _chk_tensor("term_logit", term_logit, torch.float32, tuple(term_logit.shape), dev)
+        _chk_tensor("terminated", terminated, torch.float32, tuple(terminated.shape), dev)
+        if int(terminated.numel()) != n:
+            raise ValueError(f"term_logit has {n} rows, terminated {int(terminated.numel())}")
+        stats = torch.empty(2, device=dev)
+        with torch.cuda.device(dev):
+            self._check(self.lib.tdmpc2_plan_termination_stats(self._h, n, _ptr(term_logit), _ptr(terminated), _ptr(stats),
+                                                               self._stream()))
+        return stats
 
     # ------------------------------------------------------------------ packed weight file
     def export_packed(self) -> bytes:

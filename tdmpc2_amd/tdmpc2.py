@@ -21,6 +21,7 @@ import torch
 from . import checkpoint
 from .config import get_discount
 from .native import NativePlanner
+from .scale import RunningScale
 from .world_model import WorldModel
 
 
@@ -46,6 +47,7 @@ class TDMPC2(torch.nn.Module):
         else:
             self.discount = get_discount(cfg, cfg.episode_length)
         self._prev_mean = torch.nn.Buffer(torch.zeros(cfg.horizon, cfg.action_dim, device=self.device))
+        self.scale = RunningScale(cfg, self.planner, self.device)  # reference tdmpc2.py:38
         self.max_envs = int(max_envs)
         self.native_encoder = True  # False: encode with the PyTorch-ROCm module (the parity tests compare both)
         # True: rgb observations are encoded inside the library too (tdmpc2_plan_run_pix); off by default -- the PyTorch-ROCm
@@ -429,7 +431,7 @@ class TDMPC2(torch.nn.Module):
         return res
 
     @torch.no_grad()
-    def model_losses(self, obs, action, reward, terminated=None, task=None, pi_eps=None, qidx=None):
+    def model_losses(self, obs, action, reward, terminated=None, task=None, pi_eps=None, qidx=None, want=("zs",)):
         """The forward half of `_update` (reference tdmpc2.py:259-304) with its argument shapes: obs [H+1, B, *], action
         [H, B, A], reward / terminated [H, B, 1], task [B].  encode(obs[0]), encode(obs[1:]) (state observations in the library;
         pixel observations through the PyTorch-ROCm modules), `_td_target`, then the rollout and the losses in one library call.
@@ -451,6 +453,47 @@ class TDMPC2(torch.nn.Module):
             z_all = torch.stack([self.model.encode(obs[i], t) for i in range(H + 1)])
         z0, next_z = z_all[0], z_all[1:].contiguous()
         td = self._td_target(next_z, reward, terminated, task, pi_eps=pi_eps, qidx=qidx)
-        res = self.model_losses_latent(z0, next_z, action, reward, td, terminated, task)
+        res = self.model_losses_latent(z0, next_z, action, reward, td, terminated, task, want=want)
         res["td_targets"] = td
         return res
+
+    # ------------------------------------------------------------------ update_pi's forward and the info dict of _update
+    @torch.no_grad()
+    def policy_loss(self, zs, task=None, pi_eps=None, qidx=None, update_scale=True, want=()):
+        """The forward of `update_pi` (reference tdmpc2.py:208-239) in one library call: action, info = pi(zs), qs = Q(zs, action,
+        'avg') on the online ensemble, `self.scale.update(qs[0])` (unless `update_scale` is False), qs / scale and the rho-weighted
+        loss.  zs [H+1, B, L], task [B].  Returns pi_loss, pi_entropy, pi_scaled_entropy (means, as `_update` reports them) and
+        pi_scale [1] (the scale after the call), plus the outputs in `want` (action, q, entropy, scaled_entropy, step_means,
+        percentiles).  Eval mode; no gradients, no optimiser step."""
+        cfg = self.cfg
+        zs = zs.to(self.device, torch.float32).contiguous()
+        if pi_eps is not None:
+            pi_eps = pi_eps.to(self.device, torch.float32).contiguous()
+        self._seed += 1
+        res = self.planner().policy_loss(zs, self.scale.value, rho=cfg.rho, entropy_coef=cfg.entropy_coef, tau=cfg.tau,
+                                         update_scale=update_scale, pi_eps=pi_eps, qidx=qidx, seed=self._seed, want=tuple(want),
+                                         **self._batch_task_kw(task))
+        loss = res.pop("loss")
+        res["pi_loss"], res["pi_entropy"], res["pi_scaled_entropy"], res["pi_scale"] = loss[0], loss[1], loss[2], loss[3:4]
+        return res
+
+    @torch.no_grad()
+    def update_info(self, obs, action, reward, terminated=None, task=None, pi_eps=None, qidx=None):
+        """The info dict of `_update` (reference tdmpc2.py:259-331) without `grad_norm` / `pi_grad_norm`: `model_losses`, then (episodic
+        models) `termination_statistics` on the last step's termination logit, then `policy_loss` on the rollout's zs.  It equals what
+        `_update` returns when no optimiser step is taken between the model loss and `update_pi`, and when cfg.dropout == 0.
+        `pi_eps` [H+1, B, A] / `qidx` pin the noise and the two heads of `update_pi` (the TD target draws its own)."""
+        cfg = self.cfg
+        if cfg.episodic and terminated is None:
+            terminated = torch.zeros(action.shape[0], action.shape[1], 1, device=self.device)
+        res = self.model_losses(obs, action, reward, terminated, task, want=("zs", "term_logit") if cfg.episodic else ("zs",))
+        info = {k: res[k] for k in ("consistency_loss", "reward_loss", "value_loss", "termination_loss", "total_loss")}
+        if cfg.episodic:
+            st = self.planner().termination_stats(res["term_logit"][-1].contiguous(),
+                                                  terminated[-1].to(self.device, torch.float32).contiguous())
+            info["termination_rate"], info["termination_f1"] = st[0], st[1]
+        pl = self.policy_loss(res["zs"], task, pi_eps=pi_eps, qidx=qidx)
+        for k in ("pi_loss", "pi_entropy", "pi_scaled_entropy"):
+            info[k] = pl[k]
+        info["pi_scale"] = pl["pi_scale"].mean()
+        return info
