@@ -66,7 +66,7 @@
 extern "C" {
 #endif
 
-#define TDMPC2_PLAN_ABI_VERSION 13
+#define TDMPC2_PLAN_ABI_VERSION 14
 
 typedef struct tdmpc2_plan tdmpc2_plan_t;
 
@@ -449,6 +449,48 @@ int tdmpc2_plan_running_scale(tdmpc2_plan_t *h, int n, const float *x, float tau
  * pointer -- TDMPC2_ERR_INVALID. */
 int tdmpc2_plan_termination_stats(tdmpc2_plan_t *h, int n, const float *term_logit, const float *terminated, float *stats,
                                   void *stream);
+
+/* Weight refresh (ABI 14): the whole model re-packed from the trainer's own parameter tensors in a constant, small number of
+ * launches -- what a training loop needs after every optimiser step (TDMPC2._update, tdmpc2/tdmpc2.py:259-316, changes every
+ * parameter; the per-layer binds above cost about ten small launches per ensemble member and layer).
+ *
+ * tdmpc2_weight_table: device pointers, fp32, in the checkpoint's layout -- per net and layer exactly the W, b, ln_g, ln_b that
+ * tdmpc2_plan_bind_weights takes (the Q nets stacked over num_q; ln_g / ln_b NULL where the layer has no LayerNorm), and the
+ * state encoder's layers as tdmpc2_plan_bind_encoder takes them (enc_layers of them, shapes in enc_out / enc_in;
+ * enc_layers = 0: the encoder is left as it is).  A net whose twelve entries are all NULL is left as it is; a net that is
+ * named must bring all three layers.  Shapes of the nets come from the handle's cfg.  The table is read on the host at call
+ * time and travels to the kernels as a kernel argument: no host-to-device copy is enqueued, and a call captured into a
+ * hipGraph reads, at every replay, THE TENSORS WHOSE POINTERS THE TABLE HELD AT CAPTURE (update them in place). */
+typedef struct tdmpc2_weight_entry {
+    const float *W, *b, *ln_g, *ln_b;
+} tdmpc2_weight_entry;
+typedef struct tdmpc2_weight_table {
+    tdmpc2_weight_entry net[6][3];   /* [enum tdmpc2_net][layer] */
+    tdmpc2_weight_entry enc[6];      /* state encoder, layers 0 .. enc_layers - 1 */
+    int32_t enc_layers;
+    int32_t enc_out[6], enc_in[6];   /* nn.Linear out_features / in_features of the encoder's layers */
+} tdmpc2_weight_table;
+/* Produces, for every net the table names, exactly what the sequence of tdmpc2_plan_bind_weights / tdmpc2_plan_bind_encoder
+ * calls produces (tdmpc2_plan_export_packed is byte-identical): operand slabs, per-layer scale records, padded biases,
+ * LayerNorm vectors, task-embedding columns, the transposed encoder; if the policy prior's fp32 copy is bound
+ * (tdmpc2_plan_bind_policy) and TDMPC2_NET_PI is named, that copy as well.  Both kernel families, both arithmetics.  At most 4
+ * launches on a SPLIT_F16 handle (reset of the maxima, scan, scales, pack of everything), 1 on an FP32 handle, whatever num_q
+ * and however many nets (csrc/refresh_route.h).  Storage of a (net, layer) is allocated at its first refresh or bind; after
+ * that the call neither allocates nor synchronises and may be captured.  A handle whose nets were never bound becomes ready
+ * through this call alone.  The pixel encoder is not part of the table (tdmpc2_plan_bind_pixel_encoder).
+ * TDMPC2_ERR_INVALID: NULL handle / table, a named net with a missing W / b (or LayerNorm vector where the layer has one),
+ * termination entries on a non-episodic handle, encoder shapes that tdmpc2_plan_bind_encoder refuses; the encoder's
+ * TDMPC2_ERR_UNSUPPORTED / TDMPC2_ERR_STATE cases are its own.  The handle stays usable after a refusal. */
+int tdmpc2_plan_refresh_weights(tdmpc2_plan_t *h, const tdmpc2_weight_table *tab, void *stream);
+/* WorldModel.soft_update_target_Q (common/world_model.py:82-86; the last line of TDMPC2._update, tdmpc2.py:316): the caller's
+ * fp32 target tensors target[layer] = {weight, bias, ln.weight, ln.bias} of _target_Qs_params (stacked over num_q; the
+ * LayerNorm entries of layer 2 NULL) are lerped IN PLACE towards online->net[TDMPC2_NET_Q] with torch.lerp's forms
+ * (t + tau (o - t) for tau < 0.5, else o - (o - t) (1 - tau)), and TDMPC2_NET_TARGET_Q is re-packed from the lerped values in
+ * the same call: the lerp is part of the scan launch, every element is written once, and the packed target is the pack of the
+ * tensors the caller now holds.  Launches: those of a one-net refresh (FP32 handles: 2).  Only online->net[TDMPC2_NET_Q] is
+ * read.  TDMPC2_ERR_INVALID: tau outside [0, 1] or NaN, online Q missing from the table, a NULL target tensor. */
+int tdmpc2_plan_soft_update_target(tdmpc2_plan_t *h, const tdmpc2_weight_table *online, float *const target[3][4], float tau,
+                                   void *stream);
 
 /* Packed weight file (the native counterpart of TDMPC2.save / load, tdmpc2.py:72-95).
  * export_packed copies everything the binds produced -- weights in MFMA fragment order (hi / lo split and scaled for the

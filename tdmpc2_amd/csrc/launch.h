@@ -124,6 +124,10 @@ int pl_launch_scale(const RunningScaleParams &p, hipStream_t st);
 int pl_launch_tail(const PolicyLossTailParams &p, hipStream_t st);
 int pl_launch_term_stats(const TerminationStatsParams &p, hipStream_t st);
 
+// ---- grouped weight refresh (k_refresh.hip: refresh_kernels.cuh, launch list in refresh_route.h)
+#include "refresh_params.h"
+int refresh_launch(int op /* RO_* */, const RfParams &p, hipStream_t st);
+
 // ---- policy prior (k_policy.hip)
 int pol_set_lds();  // the GEMV instantiations' dynamic LDS limit (once per handle, at bind)
 int pol_launch_row(const PolRowParams &p, const PolGrid &g, hipStream_t st);

@@ -1519,6 +1519,157 @@ int tdmpc2_plan_bind_policy(tdmpc2_plan_t *h, int layer, const float *W, const f
     return TDMPC2_OK;
 }
 
+// ================================================================ grouped weight refresh (k_refresh.hip: refresh_kernels.cuh, refresh_route.h)
+namespace {
+// One job per (net, layer) the table names (every ensemble member inside it), the encoder's and the policy copy's transposes,
+// and the workgroup ranges of the scan and pack launches.  Everything that can refuse, refuses before anything is enqueued;
+// first-time storage is allocated here.  `targets`: soft update -- the sources of TDMPC2_NET_TARGET_Q are the caller's target
+// tensors and `tab` names the online ensemble they move towards.
+int refresh_build(tdmpc2_plan *h, const tdmpc2_weight_table *tab, float *const targets[3][4], float tau, RfParams &p, RefreshRoute &route) {
+    const tdmpc2_plan_cfg &c = h->cfg;
+    p = RfParams{};
+    p.split = h->split ? 1 : 0;
+    p.lerp_net = -1;
+    unsigned nets = 0;
+    for (int net = TDMPC2_NET_DYNAMICS; net <= TDMPC2_NET_TARGET_Q; ++net) {
+        tdmpc2_weight_entry src[3];
+        if (targets) {
+            if (net != TDMPC2_NET_TARGET_Q) continue;
+            for (int l = 0; l < 3; ++l) {
+                src[l] = tdmpc2_weight_entry{targets[l][0], targets[l][1], targets[l][2], targets[l][3]};
+                const tdmpc2_weight_entry &on = tab->net[TDMPC2_NET_Q][l];
+                const bool ln = layer_shape(h, net, l).has_ln;
+                if (!on.W || !on.b || (ln && (!on.ln_g || !on.ln_b)))
+                    return fail(TDMPC2_ERR_INVALID, "soft update: the table lacks the online Q ensemble (layer %d)", l);
+                if (!src[l].W || !src[l].b || (ln && (!src[l].ln_g || !src[l].ln_b)))
+                    return fail(TDMPC2_ERR_INVALID, "soft update: null target tensor (layer %d)", l);
+                p.online[l][0] = on.W; p.online[l][1] = on.b; p.online[l][2] = ln ? on.ln_g : nullptr; p.online[l][3] = ln ? on.ln_b : nullptr;
+            }
+            p.lerp_net = net;
+            p.tau = tau;
+        } else {
+            int named = 0;
+            for (int l = 0; l < 3; ++l) {
+                src[l] = tab->net[net][l];
+                named += (src[l].W != nullptr) + (src[l].b != nullptr) + (src[l].ln_g != nullptr) + (src[l].ln_b != nullptr);
+            }
+            if (!named) continue;  // left as it is
+            if (net == TDMPC2_NET_TERMINATION && !c.episodic)
+                return fail(TDMPC2_ERR_INVALID, "termination head in the table of a non-episodic planner");
+            for (int l = 0; l < 3; ++l) {
+                if (!src[l].W || !src[l].b) return fail(TDMPC2_ERR_INVALID, "net %d is named but layer %d lacks its weight or bias", net, l);
+                if (layer_shape(h, net, l).has_ln && (!src[l].ln_g || !src[l].ln_b))
+                    return fail(TDMPC2_ERR_INVALID, "net %d layer %d needs LayerNorm parameters", net, l);
+            }
+        }
+        RfNet &N = p.net[net];
+        for (int l = 0; l < 3; ++l) {
+            const LayerShape sh = layer_shape(h, net, l);
+            if (int rc = ensure_layer_alloc(h, net, l, sh)) return rc;
+            const HostLayer &L0 = net_of(h, net, 0)->l[l];
+            RfLayer &J = N.l[l];
+            J.W = src[l].W; J.b = src[l].b; J.g = sh.has_ln ? src[l].ln_g : nullptr; J.beta = sh.has_ln ? src[l].ln_b : nullptr;
+            J.wdst = h->split ? reinterpret_cast<float *>(L0.wps) : L0.wp;
+            J.bias = L0.bias; J.gd = L0.g; J.bd = L0.b; J.wemb = L0.wemb;
+            J.out = sh.out; J.in = sh.in; J.nz = sh.nz; J.nt = sh.nt; J.na = sh.na; J.CT = sh.CT; J.KB = sh.KB;
+            J.has_ln = sh.has_ln ? 1 : 0; J.mish = sh.mish ? 1 : 0;
+            J.scan_nbw = rf_scan_wblocks((long)sh.out * sh.in);
+            N.heads = sh.heads;
+        }
+        N.scal = h->split ? net_of(h, net, 0)->scal : nullptr;
+        N.on = 1;
+        nets |= 1u << net;
+    }
+    // the state encoder: bind_encoder's rules
+    const int nenc = targets ? 0 : tab->enc_layers;
+    if (nenc < 0 || nenc > ENC_MAX_LAYERS) return fail(TDMPC2_ERR_INVALID, "encoder depth %d outside [0, %d]", nenc, ENC_MAX_LAYERS);
+    if (nenc && h->enc_layers && h->enc_layers != nenc) return fail(TDMPC2_ERR_STATE, "encoder depth changed from %d to %d", h->enc_layers, nenc);
+    for (int l = 0; l < nenc; ++l) {
+        const tdmpc2_weight_entry &e = tab->enc[l];
+        const int of = tab->enc_out[l], inf = tab->enc_in[l];
+        if (!e.W || !e.b || !e.ln_g || !e.ln_b) return fail(TDMPC2_ERR_INVALID, "encoder layer %d: null tensor", l);
+        if (of < 1 || of > ENC_THREADS * ENC_MAX_PER_THREAD || inf < 1)
+            return fail(TDMPC2_ERR_UNSUPPORTED, "encoder layer %d: width %d outside [1, %d]", l, of, ENC_THREADS * ENC_MAX_PER_THREAD);
+        if (l == nenc - 1 && of != c.latent_dim)
+            return fail(TDMPC2_ERR_INVALID, "the last encoder layer has %d outputs, latent_dim is %d", of, c.latent_dim);
+        if (l == nenc - 1 && (c.latent_dim % c.simnorm_dim || (c.simnorm_dim & (c.simnorm_dim - 1)) || c.simnorm_dim > 64))
+            return fail(TDMPC2_ERR_UNSUPPORTED, "SimNorm groups of %d over %d latents", c.simnorm_dim, c.latent_dim);
+        if (h->enc[l].wt && (h->enc[l].in != inf || h->enc[l].out != of))
+            return fail(TDMPC2_ERR_STATE, "encoder layer %d refreshed with a different shape", l);
+    }
+    for (int l = 0; l < nenc; ++l) {
+        if (int rc = ensure_enc_alloc(h, l, tab->enc_in[l], tab->enc_out[l])) return rc;
+        const tdmpc2_plan::Enc &E = h->enc[l];
+        const tdmpc2_weight_entry &e = tab->enc[l];
+        p.tr[p.ntrans++] = RfTrans{e.W, e.b, e.ln_g, e.ln_b, E.wt, E.bias, E.g, E.b, E.out, E.in};
+    }
+    // the policy prior's fp32 copy, when its buffers exist
+    const bool pol = !targets && h->pol.x && (nets & (1u << TDMPC2_NET_PI));
+    if (pol)
+        for (int l = 0; l < 3; ++l) {
+            const RfLayer &J = p.net[TDMPC2_NET_PI].l[l];
+            const tdmpc2_plan::Pol &P = h->pol;
+            p.tr[p.ntrans++] = RfTrans{J.W, J.b, l < 2 ? J.g : nullptr, l < 2 ? J.beta : nullptr, P.wt[l], P.bias[l],
+                                       l < 2 ? P.g[l] : nullptr, l < 2 ? P.b[l] : nullptr, J.out, J.in};
+        }
+    route = refresh_route(RefreshIn{p.split, nets, nenc, pol ? 1 : 0, targets ? 1 : 0, c.num_q, c.episodic});
+    // workgroup ranges
+    long sb = 0, pb = 0;
+    for (int net = 0; net < RF_NETS; ++net)
+        for (int l = 0; l < 3; ++l) {
+            const RfNet &N = p.net[net];
+            const RfLayer &J = N.l[l];
+            p.scan_blk0[net * 3 + l] = (int)sb;
+            p.pack_blk0[net * 3 + l] = (int)pb;
+            if (!N.on) continue;
+            sb += (long)N.heads * (J.scan_nbw + 1);
+            pb += (long)N.heads * rf_pack_blocks(J.CT, J.KB * (p.split ? 16 : 8), J.nt);
+        }
+    p.scan_blk0[3 * RF_NETS] = (int)sb;
+    for (int t = 0; t < RF_MAX_TRANS; ++t) {
+        p.pack_blk0[3 * RF_NETS + t] = (int)pb;
+        if (t < p.ntrans) pb += rf_transpose_blocks(p.tr[t].out, p.tr[t].in);
+    }
+    p.pack_blk0[RF_SEGS] = (int)pb;
+    if (pb > 0x7fffffffL || sb > 0x7fffffffL) return fail(TDMPC2_ERR_UNSUPPORTED, "weight refresh: %ld workgroups", pb);
+    return 0;
+}
+
+int refresh_run(tdmpc2_plan *h, const RfParams &p, const RefreshRoute &route, int nenc, hipStream_t st) {
+    for (int i = 0; i < route.nops; ++i)
+        if (int rc = tdk::refresh_launch(route.op[i], p, st)) return rc;
+    for (int net = 0; net < RF_NETS; ++net)
+        if (p.net[net].on)
+            for (int hd = 0; hd < p.net[net].heads; ++hd)
+                for (int l = 0; l < 3; ++l) net_of(h, net, hd)->l[l].bound = true;
+    for (int l = 0; l < nenc; ++l) h->enc[l].bound = true;
+    if (nenc) h->enc_layers = nenc;
+    if (route.policy_copy)
+        for (int l = 0; l < 3; ++l) h->pol.bound[l] = true;
+    return TDMPC2_OK;
+}
+}  // namespace
+
+int tdmpc2_plan_refresh_weights(tdmpc2_plan_t *h, const tdmpc2_weight_table *tab, void *stream) {
+    if (!h || !tab) return fail(TDMPC2_ERR_INVALID, "null argument");
+    ENTER_ON(h, stream);
+    RfParams p;
+    RefreshRoute route;
+    if (int rc = refresh_build(h, tab, nullptr, 0.f, p, route)) return rc;
+    return refresh_run(h, p, route, tab->enc_layers, (hipStream_t)stream);
+}
+
+int tdmpc2_plan_soft_update_target(tdmpc2_plan_t *h, const tdmpc2_weight_table *online, float *const target[3][4], float tau,
+                                   void *stream) {
+    if (!h || !online || !target) return fail(TDMPC2_ERR_INVALID, "null argument");
+    if (!(tau >= 0.f && tau <= 1.f)) return fail(TDMPC2_ERR_INVALID, "soft update: tau %g outside [0, 1]", (double)tau);
+    ENTER_ON(h, stream);
+    RfParams p;
+    RefreshRoute route;
+    if (int rc = refresh_build(h, online, target, tau, p, route)) return rc;
+    return refresh_run(h, p, route, 0, (hipStream_t)stream);
+}
+
 namespace {
 int check_pol_call(tdmpc2_plan *h, const float *task_emb, const float *act_mask, const tdmpc2_policy_out *out) {
     if (!out || !out->action) return fail(TDMPC2_ERR_INVALID, "null policy output (out / out->action)");

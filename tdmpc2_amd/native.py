@@ -17,7 +17,7 @@ import torch
 _LIB_PATH = os.environ.get("TDMPC2_PLAN_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtdmpc2_plan.so")
 _lib = None
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 # every symbol include/tdmpc2_plan.h declares (tests check the .so exports all of them)
 ABI_SYMBOLS = [
@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "tdmpc2_plan_bind_policy", "tdmpc2_plan_pi", "tdmpc2_plan_act_pi", "tdmpc2_plan_act_pi_pix",
     "tdmpc2_plan_model_rollout", "tdmpc2_plan_model_rollout_mt", "tdmpc2_plan_model_losses", "tdmpc2_plan_model_losses_mt",
     "tdmpc2_plan_policy_loss", "tdmpc2_plan_policy_loss_mt", "tdmpc2_plan_running_scale", "tdmpc2_plan_termination_stats",
+    "tdmpc2_plan_refresh_weights", "tdmpc2_plan_soft_update_target",
 ]
 
 NET_DYNAMICS, NET_REWARD, NET_PI, NET_Q, NET_TERMINATION, NET_TARGET_Q = range(6)
@@ -92,6 +93,22 @@ RUNNING_SCALE_MAX_N = 16384  # tdmpc2_plan_running_scale / the batch of a policy
 class PolicyLossOut(C.Structure):
     """struct tdmpc2_policy_loss_out: optional device outputs of the policy loss."""
     _fields_ = [(n, C.c_void_p) for n in POLICY_LOSS_OUTPUTS]
+
+
+class WeightEntry(C.Structure):
+    """struct tdmpc2_weight_entry: W, b, ln_g, ln_b of one nn.Linear (+ LayerNorm) as device pointers."""
+    _fields_ = [(n, C.c_void_p) for n in ("W", "b", "ln_g", "ln_b")]
+
+
+class WeightTable(C.Structure):
+    """struct tdmpc2_weight_table (ABI 14): the model's parameter tensors for tdmpc2_plan_refresh_weights."""
+    _fields_ = [("net", WeightEntry * 3 * 6), ("enc", WeightEntry * 6), ("enc_layers", C.c_int32),
+                ("enc_out", C.c_int32 * 6), ("enc_in", C.c_int32 * 6)]
+
+
+NET_PREFIX = {NET_DYNAMICS: "_dynamics", NET_REWARD: "_reward", NET_PI: "_pi", NET_Q: "_Qs.params",
+              NET_TERMINATION: "_termination", NET_TARGET_Q: "_target_Qs_params"}
+WEIGHT_FIELDS = (("W", "weight"), ("b", "bias"), ("ln_g", "ln.weight"), ("ln_b", "ln.bias"))
 
 
 class PolicyOut(C.Structure):
@@ -206,6 +223,10 @@ def _open(path):
     lib.tdmpc2_plan_running_scale.restype = i32
     lib.tdmpc2_plan_termination_stats.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.tdmpc2_plan_termination_stats.restype = i32
+    lib.tdmpc2_plan_refresh_weights.argtypes = [vp, C.POINTER(WeightTable), vp]
+    lib.tdmpc2_plan_refresh_weights.restype = i32
+    lib.tdmpc2_plan_soft_update_target.argtypes = [vp, C.POINTER(WeightTable), C.POINTER(C.c_void_p * 4), C.c_float, vp]
+    lib.tdmpc2_plan_soft_update_target.restype = i32
     lib.tdmpc2_plan_packed_size.argtypes = [vp, C.POINTER(u64)]
     lib.tdmpc2_plan_packed_size.restype = i32
     lib.tdmpc2_plan_export_packed.argtypes = [vp, vp, u64, vp]
@@ -376,6 +397,92 @@ class NativePlanner:
                     self._check(self.lib.tdmpc2_plan_bind_weights(self._h, net, layer, _ptr(W), _ptr(b), _ptr(g),
                                                                   _ptr(beta), out_f, in_f, self._stream()))
             torch.cuda.current_stream(self.device).synchronize()  # sources may now be freed
+
+    # ------------------------------------------------------------------ weight refresh (ABI 14)
+    def _src(self, key, t, shape):
+        """Pointer of a tensor the library reads IN PLACE: it must already be what the kernels take (no copy is made)."""
+        if not torch.is_tensor(t) or t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
+            raise NativeError(f"{key}: the refresh reads the tensor itself -- it must be a contiguous float32 tensor on {self.device}")
+        if tuple(t.shape) != tuple(shape):
+            raise NativeError(f"{key}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+        return t.data_ptr()
+
+    def _net_shapes(self, net, layer):
+        """Shapes of `_<net>.{layer}.{weight,bias,ln.weight,ln.bias}` as the handle's cfg gives them (ln entries None without LayerNorm)."""
+        c = self.cfg
+        is_q = net in (NET_Q, NET_TARGET_Q)
+        takes_action = net in (NET_DYNAMICS, NET_REWARD) or is_q
+        if layer == 0:
+            fin, fout = c.latent_dim + c.task_dim + (c.action_dim if takes_action else 0), c.mlp_dim
+        else:
+            fin = c.mlp_dim
+            fout = c.mlp_dim if layer == 1 else (c.latent_dim if net == NET_DYNAMICS else 2 * c.action_dim if net == NET_PI
+                                                 else 1 if net == NET_TERMINATION else max(int(c.num_bins), 1))
+        lead = (int(c.num_q),) if is_q else ()
+        ln = layer < 2 or net == NET_DYNAMICS
+        vec = lead + (fout,)
+        return {"weight": lead + (fout, fin), "bias": vec, "ln.weight": vec if ln else None, "ln.bias": vec if ln else None}
+
+    def weight_table(self, sd: Dict[str, torch.Tensor], nets=None, encoder_prefix: str = "_encoder.state") -> WeightTable:
+        """struct tdmpc2_weight_table over the tensors of `sd` themselves (checkpoint keys, as `bind_state_dict` / `bind_encoder`
+        read them).  `nets`: the NET_* to name (default: every net whose `.0.weight` is in `sd`); the state encoder is named when
+        its keys are in `sd`.  NativeError if a tensor is not fp32, not contiguous, not on the handle's device or of another shape."""
+        tab = WeightTable()
+        for net, prefix in NET_PREFIX.items():
+            if (net not in nets) if nets is not None else (f"{prefix}.0.weight" not in sd):
+                continue
+            for layer in range(3):
+                shapes = self._net_shapes(net, layer)
+                for field, name in WEIGHT_FIELDS:
+                    k = f"{prefix}.{layer}.{name}"
+                    if shapes[name] is None:
+                        continue
+                    if k not in sd:
+                        raise KeyError(f"state dict lacks {k}")
+                    setattr(tab.net[net][layer], field, self._src(k, sd[k], shapes[name]))
+        n = 0
+        while nets is None and f"{encoder_prefix}.{n}.weight" in sd:
+            n += 1
+        if n > 6:
+            raise NativeError(f"state encoder of {n} layers (at most 6)")
+        for layer in range(n):
+            W = sd[f"{encoder_prefix}.{layer}.weight"]
+            fout, fin = int(W.shape[0]), int(W.shape[1])
+            for field, name in WEIGHT_FIELDS:
+                k = f"{encoder_prefix}.{layer}.{name}"
+                setattr(tab.enc[layer], field, self._src(k, sd[k], (fout, fin) if field == "W" else (fout,)))
+            tab.enc_out[layer], tab.enc_in[layer] = fout, fin
+        tab.enc_layers = n
+        return tab
+
+    def refresh_state_dict(self, sd: Dict[str, torch.Tensor], nets=None):
+        """Re-pack the planner's weights from the tensors of `sd` THEMSELVES in at most four launches (tdmpc2_plan_refresh_weights):
+        what `bind_state_dict` + `bind_encoder` (+ `bind_policy` when the policy prior is bound) produce, without copies, without
+        a stream synchronisation, capturable.  The tensors are read when the launches run: keep them alive and unchanged until
+        the stream has passed the call (a training loop's parameters are both)."""
+        tab = self.weight_table(sd, nets)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.tdmpc2_plan_refresh_weights(self._h, C.byref(tab), self._stream()))
+        if tab.enc_layers:
+            self.encoder_layers = int(tab.enc_layers)
+            self.obs_dim = int(tab.enc_in[0]) - int(self.cfg.task_dim)
+
+    def soft_update_target(self, sd: Dict[str, torch.Tensor], tau: float):
+        """WorldModel.soft_update_target_Q (world_model.py:82-86): `_target_Qs_params.*` of `sd` are lerped IN PLACE towards
+        `_Qs.params.*` with weight `tau` and the target ensemble is re-packed from the result (tdmpc2_plan_soft_update_target)."""
+        tab = self.weight_table(sd, nets=(NET_Q,))
+        tgt = (C.c_void_p * 4 * 3)()
+        for layer in range(3):
+            shapes = self._net_shapes(NET_TARGET_Q, layer)
+            for i, (_, name) in enumerate(WEIGHT_FIELDS):
+                if shapes[name] is None:
+                    continue
+                k = f"_target_Qs_params.{layer}.{name}"
+                if k not in sd:
+                    raise KeyError(f"state dict lacks {k}")
+                tgt[layer][i] = self._src(k, sd[k], shapes[name])
+        with torch.cuda.device(self.device):
+            self._check(self.lib.tdmpc2_plan_soft_update_target(self._h, C.byref(tab), tgt, C.c_float(float(tau)), self._stream()))
 
     def bind_encoder(self, sd: Dict[str, torch.Tensor], prefix: str = "_encoder.state"):
         """Bind the state encoder (tdmpc2/common/layers.py:153-164) from checkpoint keys

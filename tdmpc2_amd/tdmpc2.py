@@ -57,6 +57,9 @@ class TDMPC2(torch.nn.Module):
         # True: act() with cfg.mpc == False (the policy prior, tdmpc2.py:114-120) runs inside the library too (tdmpc2_plan_act_pi /
         # act_pi_pix / pi); off by default -- the PyTorch-ROCm modules encode and evaluate _pi
         self.native_policy = False
+        # True: sync_planner_weights() re-packs an existing handle from the model's own parameter tensors in at most four launches
+        # (tdmpc2_plan_refresh_weights: no copies, no stream synchronisation); off by default -- the per-layer binds
+        self.native_refresh = False
         self._reuse_shift = False
         self._planner: Optional[NativePlanner] = None
         self._planner_log_std = None
@@ -125,11 +128,29 @@ class TDMPC2(torch.nn.Module):
         if self._planner is not None and self._planner_log_std != self._log_std():
             self._planner.close()
             self._planner = None  # rebuilt (with the new constants and weights) by the next planner() call
-        if self._planner is not None:
+        if self._planner is not None and self.native_refresh:
+            self._planner.refresh_state_dict(self._refresh_state_dict())  # the policy prior's copy included, when bound
+            if self.native_pixel_encoder and self.cfg.obs == "rgb":
+                self._bind_pixel_encoder()
+        elif self._planner is not None:
             self._planner.bind_state_dict(self.model.planner_state_dict())
             self._bind_encoder()
             if self._planner.policy_bound:
                 self._bind_policy()
+
+    def _refresh_state_dict(self):
+        """The model's own tensors (no copies) that a refresh reads: the planner's nets and, where the library encodes, the state encoder."""
+        sd = self.model.planner_state_dict()
+        if self.native_encoder and self.cfg.obs == "state":
+            sd.update({k: v for k, v in self.model.state_dict().items() if torch.is_tensor(v) and k.startswith("_encoder.state.")})
+        return sd
+
+    def soft_update_target_Q(self):
+        """reference world_model.py:82-86 (the last line of TDMPC2._update, tdmpc2.py:316): `_target_Qs_params` lerped in place
+        towards `_Qs.params` with cfg.tau inside the library, which leaves its target ensemble packed from the result."""
+        sd = self.model.planner_state_dict()
+        self.planner().soft_update_target({k: v for k, v in sd.items() if k.startswith(("_Qs.params.", "_target_Qs_params."))},
+                                          float(self.cfg.tau))
 
     def _disc_pow(self, tasks):
         """discount^0..discount^H exactly as tdmpc2.py:126,130-132 accumulates it: python-float
