@@ -694,7 +694,10 @@ int fused_run(tdmpc2_plan *h, hipStream_t st, int E, const float *z0, const floa
             fp.sample_eps = rp.sample_eps; fp.sample_eps_estride = rp.sample_eps_estride;
         }
         if (h->profiling && h->ev_used + 2 <= (int)h->ev.size()) HIP_TRY(hipEventRecord(h->ev[h->ev_used], st));
-        if (cluster2) cluster_ops(h->Apad).rollout_cl2(rp, (int)((2 * clusters + 7) / 8 * 64), h->cl_lds, st);
+        // ks_rollout_cl2 maps blocks to (tile, role) in groups of 8 tiles x 2 roles: BOTH roles of every started group of 8
+        // tiles need their blocks ((2 * clusters + 7) / 8 groups left tiles 0 .. 3 of a 64- / 128-sample plan without their R
+        // cluster: D's mailbox wait gave up and the plan returned NaN)
+        if (cluster2) cluster_ops(h->Apad).rollout_cl2(rp, (int)((clusters + 7) / 8 * 2 * 64), h->cl_lds, st);
         else if (cluster) Kern<NET>::rollout_cluster(h, rp, (int)clusters, st);
         else Kern<NET>::rollout(h, rp, E * rp.tiles, st, nst, nw);
         HIP_TRY(hipGetLastError());
