@@ -2,7 +2,7 @@
 # Build the planner's C-ABI shared library for gfx950 (cross-compiles without a GPU).
 # One translation unit per kernel family (and, for the fused 512-wide family, per action padding), compiled in parallel and
 # linked into ONE libtdmpc2_plan.so:
-#   tdmpc2_plan.hip            C ABI, handle, bind / pack kernels, refit, encoder, host side of the fused family
+#   tdmpc2_plan.hip            C ABI, handle (its sizes: plan_layout.h), bind / pack kernels, refit, encoder, host side of the fused family
 #   k_fused.hip   x {16,32,48,64}   ks_setup / ks_pitraj / ks_rollout / ks_value
 #   k_cluster.hip x {16,32,48,64}   ks_rollout_cl
 #   k_layered.hip              layered GEMMs + row kernels + their host orchestration

@@ -22,7 +22,6 @@
 // Included by k_cluster.hip after cluster_kernels.cuh.
 #pragma once
 
-constexpr int CL2_SLOTS = 6 + 2 * MAXH;  // exchange tiles per cluster: 0 / 1 layers, 4 head, 5 policy head, 6 + t: Z[t], 6 + MAXH + t: prior policy head of step t
 constexpr int CL2_MAIL = 15;         // arrival word of R's cluster that carries the mailbox's launch tag
 
 // poll the 8 arrival words of a PEER cluster until all have reached `phase` (bounded)

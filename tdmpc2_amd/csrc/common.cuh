@@ -14,6 +14,7 @@
 
 #include "../../include/tdmpc2_plan.h"
 #include "layer_route.h"  // GBM and the other tile constants the layered family's routes share with its kernels
+#include "plan_layout.h"  // ROWS, WIDTH, MAXQ, MAXH, GBK, BE_*, CL* : the constants the handle's buffers are sized with
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -22,24 +23,15 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 namespace tdk {
 
-constexpr int ROWS = 64;        // sample rows per rollout workgroup
 constexpr int NTHREADS = 512;   // 8 wavefronts
-constexpr int WIDTH = 512;      // latent_dim == mlp_dim of the fused size class
-constexpr int MAXQ = 8;
-constexpr int MAXH = 8;
 constexpr float LN_EPS = 1e-5f;
 
-// layered family (layered_kernels.cuh / layered_split.cuh): GEMM tile constants the host sizes buffers with (GBM: layer_route.h)
+// (ROWS, WIDTH, MAXQ, MAXH and the cluster path's CL* constants: plan_layout.h, which sizes the handle's buffers with them)
+// layered family (layered_kernels.cuh / layered_split.cuh): GEMM tile constants (GBM: layer_route.h, GBK: plan_layout.h)
 constexpr int GBN = 128;          // output columns per GEMM workgroup (4 column tiles of 32)
-constexpr int GBK = 32;           // k-chunk staged through LDS
 constexpr int GLD = GBK + 4;      // LDS row stride in floats (stride/4 = 9, odd -> conflict-free ds_read_b128)
 constexpr int GTHREADS = 256;     // 4 wavefronts: 2 (rows) x 2 (cols), each 64 x 64 = 2x2 MFMA tiles
 constexpr int RW_THREADS = 256;   // row kernels: 4 rows (wavefronts) per workgroup
-// cluster path (cluster_kernels.cuh)
-constexpr int CL = 8;                  // workgroups per cluster
-constexpr int CL_SLOTS = 6;            // exchange tiles per cluster (S4 holds a head's logits, [32][128] fp32; S5: episodic models)
-constexpr int CL_TILE = 32 * WIDTH;    // floats per exchange tile
-constexpr int CL_FLAG_STRIDE = 16;     // arrival words reserved per cluster (64 B)
 
 
 // Scale of bounded operands (SimNorm latents in [0, 1], actions in [-1, 1]) and the LARGEST scale of a hidden activation.
@@ -223,7 +215,6 @@ struct ValueEntParamsT : ValueParamsT<NET> {
 };
 
 // net slots inside `beff`
-enum { BE_DYN = 0, BE_REW = 1, BE_PI = 2, BE_Q0 = 3 };
 
 // ---------------------------------------------------------------- small math
 __device__ __forceinline__ float mish_f(float x) {

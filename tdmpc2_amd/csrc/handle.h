@@ -24,7 +24,6 @@ int fail(int code, const char *fmt, ...);
         hipError_t _e = hipGetLastError();                                                   \
         if (_e != hipSuccess) return fail(TDMPC2_ERR_HIP, "launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
     } while (0)
-inline size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
 
 struct HostLayer {
     float *wp = nullptr, *bias = nullptr, *g = nullptr, *b = nullptr, *wemb = nullptr;

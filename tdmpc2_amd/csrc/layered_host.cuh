@@ -60,7 +60,7 @@ int lay_ln(tdmpc2_plan *h, hipStream_t st, int act, float *x, int ld, int width,
 // What the handle offers a launch on the chain whose statistics exchange / K-split workspace are `stats` / `ksws` (layer_route.h)
 inline LayCtx lay_ctx(const tdmpc2_plan *h, const float *stats, const float *ksws) {
     const Layered &L = h->lay;
-    return LayCtx{h->num_cus > 0 ? h->num_cus : 256, L.ksplit, L.fuse_ln, L.row_env != nullptr, L.arrive != nullptr, L.arrive_off, L.arrive_cap,
+    return LayCtx{plan_cus(h->num_cus), L.ksplit, L.fuse_ln, L.row_env != nullptr, L.arrive != nullptr, L.arrive_off, L.arrive_cap,
                   stats != nullptr, L.stats_cap, ksws != nullptr, L.ksws_slots, L.knob.v};
 }
 
@@ -398,8 +398,8 @@ struct MidOp {
 // What the few-row path needs of the handle to take a call (layer_route.h: mid_ok)
 inline MidCtx mid_ctx(const tdmpc2_plan *h) {
     const Layered &L = h->lay;
-    return MidCtx{h->split, L.mid, L.ksplit, L.mws[0] != nullptr, L.HA2 != nullptr, L.row_env != nullptr, h->num_cus > 0 ? h->num_cus : 256,
-                  (std::max(h->cfg.mlp_dim, h->cfg.latent_dim) + 31) / 32};
+    return MidCtx{h->split, L.mid, L.ksplit, L.mws[0] != nullptr, L.HA2 != nullptr, L.row_env != nullptr, plan_cus(h->num_cus),
+                  plan_maxct(h->cfg)};
 }
 
 // one launch of g_gemm_m + one of m_rows for n (1 or 2) layers over the same `rows` sample rows; mid_route (layer_route.h) sizes both

@@ -307,25 +307,19 @@ void dev_release(tdmpc2_plan *h, void *p) {  // free one allocation made with de
     (void)hipFree(p);
 }
 
-// g_gemm_w's K-split workspaces (256 KiB per split tile and part, one workspace per chain), sized for what the handle's mode can
-// use (every layered handle used to pay for 1 024 slots per chain -- 0.5 GiB -- whatever its mode): mode 0 none; mode 2
-// (the default) only splits launches of at most cus / 2 tiles = at most cus / 16 tail tiles per XCD; mode 1 the last round of any
-// launch = 32 tail tiles per XCD.  Called at create and when tdmpc2_plan_set_tuning raises the mode (grows, never shrinks; the
-// smaller buffers stay with the handle until destroy).  `mode`: the K-split mode the workspaces are for -- the caller stores it
-// only once they are there; a failed second allocation releases the first.
+// g_gemm_w's K-split workspaces, one per chain, of ksws_slots(..., mode) slots (plan_layout.h).  Called at create and when
+// tdmpc2_plan_set_tuning raises the mode (grows, never shrinks; the smaller buffers stay with the handle until destroy).  `mode`: the
+// K-split mode the workspaces are for -- the caller stores it only once they are there; a failed second allocation releases the first.
 int ksws_ensure(tdmpc2_plan *h, int mode) {
     Layered &L = h->lay;
-    if (!L.ks_tiles || mode == 0) return 0;
-    const size_t cus = (size_t)(h->num_cus > 0 ? h->num_cus : 256);
-    const size_t cap_slots = mode == 2 ? 8 * ((cus / 16 + 3) / 4 * 4) * 4 : 8 * 32 * 4;
-    const size_t want = std::min<size_t>(cap_slots, L.ks_tiles * 4);
+    const size_t want = ksws_slots(L.ks_tiles, h->num_cus, mode);
     if (want <= L.ksws_slots) return 0;
     float *a = nullptr, *b = nullptr;
     int rc;
-    if ((rc = dev_alloc(h, (void **)&a, want * 65536 * 4))) return rc;
-    if (L.side && (rc = dev_alloc(h, (void **)&b, want * 65536 * 4))) {
+    if ((rc = dev_alloc(h, (void **)&a, want * KS_SLOT_FLOATS * 4))) return rc;
+    if (L.side && (rc = dev_alloc(h, (void **)&b, want * KS_SLOT_FLOATS * 4))) {
         dev_release(h, a);
-        h->bytes -= want * 65536 * 4;
+        h->bytes -= want * KS_SLOT_FLOATS * 4;
         return rc;
     }
     L.ksws = a; L.ksws2 = b; L.ksws_slots = want;
@@ -417,7 +411,6 @@ const FusedOps &fused_ops(int apad) {
     }
 #endif
 }
-constexpr int CL2_SLOTS_HOST = 6 + 2 * MAXH;  // = CL2_SLOTS of cluster2_kernels.cuh (exchange tiles per cluster of ks_rollout_cl2)
 const ClusterOps &cluster_ops(int apad) {
 #ifdef TDMPC2_ONLY_APAD
     (void)apad;
@@ -440,7 +433,7 @@ template <> struct Kern<NetS> {
     static int sample_tiles(const tdmpc2_plan *h, int E, bool tracing) {
         if (tracing) return 2;  // the activation trace is laid out per 64-row tile
         if (h->force_rows) return h->force_rows / 32;
-        const long cus = h->num_cus > 0 ? h->num_cus : 256;
+        const long cus = plan_cus(h->num_cus);
         const long w2 = (long)E * h->tiles, w1 = 2 * w2;
         const long r2 = (w2 + cus - 1) / cus, r1 = (w1 + cus - 1) / cus;
         return 0.61 * (double)r1 < (double)r2 ? 1 : TDMPC2_DEFAULT_THROUGHPUT_ST;
@@ -605,7 +598,7 @@ int fused_run(tdmpc2_plan *h, hipStream_t st, int E, const float *z0, const floa
     // single-plan latency: 8 workgroups per 32-row tile when the whole call then still fits the chip in one round
     const long clusters = (long)E * h->tiles * 2;
     const bool cluster = h->cluster_mode != 0 && h->cl_max_clusters > 0 && clusters <= h->cl_max_clusters &&
-                         (clusters + 7) / 8 * 64 <= (h->num_cus > 0 ? h->num_cus : 256);
+                         (clusters + 7) / 8 * 64 <= plan_cus(h->num_cus);
     // ... which also computes the policy-prior trajectories (cluster 0 of each plan, first launch) and needs no z0 products
     const bool pi_fold = cluster && P > 0 && P <= 32;
     if ((rc = launch_setup<NET>(h, E, z0, task_emb, prev_mean, t0, st, cluster))) return rc;
@@ -660,7 +653,7 @@ int fused_run(tdmpc2_plan *h, hipStream_t st, int E, const float *z0, const floa
     // auto: only when the whole launch is one round of workgroups (few plans: latency).  With several rounds every round
     // ends with the refits of the plans that completed in it, on CUs whose next workgroup then starts late: measured
     // +0.5 ms on the 4.4 ms launch of 256 plans, against 30 us for the separate k_refit launch.
-    const bool one_round = cluster || (long)E * rp.tiles <= (h->num_cus > 0 ? h->num_cus : 256);
+    const bool one_round = cluster || (long)E * rp.tiles <= plan_cus(h->num_cus);
     const bool fold = refit_stage && (h->fold_refit == 1 || (h->fold_refit == 2 && one_round));
     if (!fold) refit_lds = refit_lds_bytes(N, K, H, A, &refit_stage);
     for (int it = 0; it < I; ++it) {
@@ -756,6 +749,57 @@ int run_impl(tdmpc2_plan *h, int n_envs, const float *z0, const float *task_emb,
              const tdmpc2_debug *dbg, void *stream);
 }
 
+namespace {
+// ---- what tdmpc2_plan_create does around plan_layout (plan_layout.h decides; these touch the process and the device)
+// The creation-time switches of this process's environment, read once at the top of create.
+CreateEnv read_create_env() {
+    CreateEnv e;
+    e.one_stream = getenv("TDMPC2_ONE_STREAM") != nullptr;
+    if (const char *fl = getenv("TDMPC2_FUSE_LN")) e.fuse_ln = atoi(fl) != 0;
+    if (const char *ks = getenv("TDMPC2_KSPLIT")) e.ksplit = std::min(2, std::max(0, atoi(ks)));
+    if (const char *fr = getenv("TDMPC2_FEWROW")) e.fewrow = atoi(fr) != 0;
+    if (const char *cm = getenv("TDMPC2_CLUSTER")) e.cluster = atoi(cm);
+#ifdef GW_TIMING
+    e.gw_timing = getenv("TDMPC2_GW_TIMING") != nullptr;
+#endif
+#ifdef SPLIT_TIMING
+    e.timing = getenv("TDMPC2_TIMING") != nullptr;
+#endif
+    return e;
+}
+
+// The handle's field for a buffer of the layout.
+void **buf_field(tdmpc2_plan *h, PlanBufId id) {
+    Layered &L = h->lay;
+#define PB_FIELD(ID, FIELD) case ID: return (void **)&(FIELD)
+    switch (id) {
+        PB_FIELD(PB_BINS, h->bins); PB_FIELD(PB_ACTIONS, h->actions); PB_FIELD(PB_VALUE, h->value); PB_FIELD(PB_MEAN, h->mean);
+        PB_FIELD(PB_STD, h->std); PB_FIELD(PB_TICKET, h->ticket); PB_FIELD(PB_QIDX_BUF, h->qidx_buf); PB_FIELD(PB_ONE, h->one);
+        PB_FIELD(PB_BEFF, h->beff); PB_FIELD(PB_CVEC, h->cvec); PB_FIELD(PB_ZSCRATCH, h->zscratch);
+        PB_FIELD(PB_CL_XBUF, h->cl_xbuf); PB_FIELD(PB_CL_ZS, h->cl_zs); PB_FIELD(PB_CL_FLAGS, h->cl_flags);
+        PB_FIELD(PB_CL2_XBUF, h->cl2_xbuf); PB_FIELD(PB_CL2_ZS, h->cl2_zs); PB_FIELD(PB_CL2_FLAGS, h->cl2_flags); PB_FIELD(PB_CL2_MAIL, h->cl2_mail);
+        PB_FIELD(PB_X, L.X); PB_FIELD(PB_HA, L.HA); PB_FIELD(PB_HB, L.HB); PB_FIELD(PB_LG, L.LG); PB_FIELD(PB_G, L.G); PB_FIELD(PB_QT, L.QT);
+        PB_FIELD(PB_TERM, L.TERM); PB_FIELD(PB_QIDX, L.qidx); PB_FIELD(PB_Z0X, L.Z0X); PB_FIELD(PB_LCVEC, L.cvec);
+        PB_FIELD(PB_HA2, L.HA2); PB_FIELD(PB_HB2, L.HB2); PB_FIELD(PB_LG2, L.LG2);
+        PB_FIELD(PB_STATS, L.stats); PB_FIELD(PB_STATS2, L.stats2); PB_FIELD(PB_ARRIVE, L.arrive); PB_FIELD(PB_MWS0, L.mws[0]);
+        PB_FIELD(PB_MWS1, L.mws[1]); PB_FIELD(PB_PRE, L.PRE); PB_FIELD(PB_PRE2, L.PRE2);
+        case PB_COUNT: break;
+    }
+#undef PB_FIELD
+    return nullptr;
+}
+
+// The host-mapped error line of the bounded waits (cluster path, fused NormedLinear epilogue): allocated, zeroed, mapped.
+int err_line_create(tdmpc2_plan *h) {
+    if (hipHostMalloc((void **)&h->cl_err_host, 64, hipHostMallocMapped) != hipSuccess)
+        return fail(TDMPC2_ERR_HIP, "allocating the error line of the bounded waits failed");
+    memset(h->cl_err_host, 0, 64);  // hipHostMalloc does not zero: word 0 (verdict) AND word 8 (sticky, fault_poll)
+    if (hipHostGetDevicePointer((void **)&h->cl_err_dev, h->cl_err_host, 0) != hipSuccess)
+        return fail(TDMPC2_ERR_HIP, "hipHostGetDevicePointer failed");
+    return 0;
+}
+}  // namespace
+
 extern "C" {
 
 int tdmpc2_plan_abi_version(void) { return TDMPC2_PLAN_ABI_VERSION; }
@@ -765,312 +809,94 @@ int tdmpc2_plan_create(const tdmpc2_plan_cfg *cfg, tdmpc2_plan_t **out) {
     if (!cfg || !out) return fail(TDMPC2_ERR_INVALID, "null argument");
     *out = nullptr;
     const tdmpc2_plan_cfg &c = *cfg;
-    // ---- limits common to both kernel families
-    if (c.action_dim < 1 || c.action_dim > 64) return fail(TDMPC2_ERR_UNSUPPORTED, "action_dim %d outside [1, 64]", c.action_dim);
-    // num_bins 0 / 1: the reference's regression heads -- one output column, two_hot_inv = identity / symexp (math.py:76-79)
-    if (c.num_bins < 0 || c.num_bins > 128) return fail(TDMPC2_ERR_UNSUPPORTED, "num_bins %d outside [0, 128]", c.num_bins);
-    if (c.num_q < 2 || c.num_q > MAXQ) return fail(TDMPC2_ERR_UNSUPPORTED, "num_q %d outside [2, %d]", c.num_q, MAXQ);
-    if (c.horizon < 1 || c.horizon > MAXH) return fail(TDMPC2_ERR_UNSUPPORTED, "horizon %d outside [1, %d]", c.horizon, MAXH);
-    if (c.num_samples % ROWS != 0 || c.num_samples < ROWS || c.num_samples > 1024)
-        return fail(TDMPC2_ERR_UNSUPPORTED, "num_samples %d must be a multiple of %d in [%d, 1024]", c.num_samples, ROWS, ROWS);
-    if (c.num_pi_trajs < 0 || c.num_pi_trajs > ROWS || c.num_pi_trajs >= c.num_samples)
-        return fail(TDMPC2_ERR_UNSUPPORTED, "num_pi_trajs %d outside [0, %d]", c.num_pi_trajs, ROWS);
-    if (c.num_elites < 1 || c.num_elites > c.num_samples) return fail(TDMPC2_ERR_INVALID, "num_elites %d", c.num_elites);
-    if (c.num_valid_samples != 0 && (c.num_valid_samples < c.num_elites || c.num_valid_samples > c.num_samples ||
-                                     c.num_valid_samples <= c.num_pi_trajs || c.num_samples - c.num_valid_samples >= GBM))
-        return fail(TDMPC2_ERR_INVALID, "num_valid_samples %d: 0, or the true sample count behind num_samples %d rounded up to the row tile "
-                    "(>= num_elites %d, > num_pi_trajs %d)", c.num_valid_samples, c.num_samples, c.num_elites, c.num_pi_trajs);
-    if (c.simnorm_dim != 8) return fail(TDMPC2_ERR_UNSUPPORTED, "simnorm_dim %d (kernels are built for 8)", c.simnorm_dim);
-    if (c.multitask && c.task_dim < 1) return fail(TDMPC2_ERR_INVALID, "multitask needs task_dim > 0");
-    if (c.multitask && c.episodic)  // the reference asserts the same: tdmpc2/common/world_model.py:136
-        return fail(TDMPC2_ERR_UNSUPPORTED, "termination head with task ids is not supported (reference world_model.py:136)");
-    if (c.iterations < 1 || c.max_envs < 1) return fail(TDMPC2_ERR_INVALID, "iterations / max_envs must be positive");
-    if (c.latent_dim < 8 || c.mlp_dim < 8 || c.latent_dim % 8 != 0)
-        return fail(TDMPC2_ERR_UNSUPPORTED, "latent_dim %d / mlp_dim %d", c.latent_dim, c.mlp_dim);
-    // ---- kernel family
-    const bool fits_fused = c.latent_dim == WIDTH && c.mlp_dim == WIDTH;
-    const bool fits_layered = c.latent_dim % 32 == 0 && c.mlp_dim % 32 == 0 && c.num_samples % GBM == 0;
-    int path = c.path;
-    if (path == TDMPC2_PATH_AUTO) path = fits_fused ? TDMPC2_PATH_FUSED : TDMPC2_PATH_LAYERED;
-    if (path == TDMPC2_PATH_FUSED && !fits_fused)
-        return fail(TDMPC2_ERR_UNSUPPORTED, "fused planner kernels are built for latent_dim == mlp_dim == %d (got %d / %d)",
-                    WIDTH, c.latent_dim, c.mlp_dim);
-    if (path == TDMPC2_PATH_LAYERED && !fits_layered)
-        return fail(TDMPC2_ERR_UNSUPPORTED, "layered planner kernels need latent_dim %% 32 == 0, mlp_dim %% 32 == 0 and "
-                    "num_samples %% %d == 0 (got %d / %d / %d)", GBM, c.latent_dim, c.mlp_dim, c.num_samples);
-    if (path != TDMPC2_PATH_FUSED && path != TDMPC2_PATH_LAYERED) return fail(TDMPC2_ERR_INVALID, "unknown path %d", c.path);
-    int prec = c.precision;
-    if (prec == TDMPC2_PREC_AUTO) prec = TDMPC2_PREC_SPLIT_F16;
-    if (prec != TDMPC2_PREC_FP32 && prec != TDMPC2_PREC_SPLIT_F16) return fail(TDMPC2_ERR_INVALID, "unknown precision %d", c.precision);
-    if (prec == TDMPC2_PREC_SPLIT_F16 && path == TDMPC2_PATH_LAYERED && (c.mlp_dim > 4096 || c.latent_dim > 4096))
-        return fail(TDMPC2_ERR_UNSUPPORTED, "the layered f16x2-split row kernels hold a row of at most 4096 columns in registers");
+    const CreateEnv env = read_create_env();
+    int num_cus = 0;  // (a property of the device, read without making it current; plan_layout falls back where there is none)
+    if (hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, c.device) != hipSuccess) num_cus = 0;
+    // every configuration check, the kernel family, the arithmetic and every size: plan_layout.h
+    const PlanLayout lo = plan_layout(c, num_cus, env);
+    if (lo.err) return fail(lo.err, "%s", lo.msg);
     DevGuard dev_(c.device);
     if (!dev_.ok) return fail(TDMPC2_ERR_HIP, "hipSetDevice(%d) failed", c.device);
 
     tdmpc2_plan *h = new (std::nothrow) tdmpc2_plan();
     if (!h) return fail(TDMPC2_ERR_INVALID, "out of host memory");
+    Layered &L = h->lay;
     h->cfg = c;
-    h->cfg.path = path;
-    h->cfg.precision = prec;
-    h->lay.on = (path == TDMPC2_PATH_LAYERED);
-    h->lay.qarr = h->q;
-    h->split = (prec == TDMPC2_PREC_SPLIT_F16);
-    if (hipDeviceGetAttribute(&h->num_cus, hipDeviceAttributeMultiprocessorCount, c.device) != hipSuccess) h->num_cus = 0;
-    h->Apad = (c.action_dim + 15) / 16 * 16;  // the fused kernels are instantiated for action paddings 16 / 32 / 48 / 64
-    h->tiles = c.num_samples / ROWS;
-    h->nnets = BE_Q0 + c.num_q;
+    h->cfg.path = lo.path;
+    h->cfg.precision = lo.precision;
+    L.on = lo.layered;
+    L.qarr = h->q;
+    h->split = lo.split;
+    h->num_cus = num_cus;
+    h->Apad = lo.Apad; h->tiles = lo.tiles; h->nnets = lo.nnets; h->stride = lo.stride;
+    h->row_bytes = lo.row_bytes; h->lds_bytes = lo.lds_bytes; h->cl_lds = lo.cl_lds; h->cl_max_clusters = lo.cl_max_clusters;
+    L.Kin = lo.Kin; L.Mp = lo.Mp; L.ldl = lo.ldl; L.Ppad = lo.Ppad; L.ldpre = lo.ldpre;
+    L.cvec_rows = lo.cvec_rows; L.stats_cap = lo.stats_cap; L.arrive_cap = lo.arrive_cap; L.ks_tiles = lo.ks_tiles; L.mws_cap = lo.mws_cap;
+
+    struct Undo {  // whatever follows fails: the handle and all it owns so far go
+        tdmpc2_plan *h;
+        ~Undo() { if (h) tdmpc2_plan_destroy(h); }
+    } undo{h};
     int rc = 0;
-    const size_t E = c.max_envs, H = c.horizon, N = c.num_samples, A = c.action_dim;
-    if (!h->lay.on) {
-        if (h->split) {
-            // operand form: row = [hi: SH halfs | lo: SH halfs | 8 pad]; row stride in dwords SH + 4 = 4 x odd
-            const int SH = WIDTH + h->Apad;
-            h->stride = 2 * SH + 8;  // in halfs
-            h->row_bytes = (size_t)h->stride * 2;
-        } else {
-            // fp32 rows [z (512) | a (Apad) | 4 pad]: stride / 4 odd -> conflict-free ds_read_b128 across 16 rows
-            h->stride = WIDTH + h->Apad + 4;  // in floats
-            h->row_bytes = (size_t)h->stride * 4;
-        }
-        // after the tile: LayerNorm partials, LayerNorm affine (CtxT::gb), then mean / std [2 H A] of the rollout kernel or
-        // the 64 row -> task entries of ks_value
-        const size_t tail = std::max<size_t>((size_t)2 * c.horizon * c.action_dim * 4, 256);
-        h->lds_bytes = (size_t)ROWS * h->row_bytes + 4096 /* LayerNorm partials */ + 4096 /* LayerNorm affine */ + tail + 64;
-        if (h->lds_bytes > 160 * 1024) {
-            const size_t need = h->lds_bytes;
-            delete h;
-            return fail(TDMPC2_ERR_UNSUPPORTED, "LDS tile of %zu bytes exceeds 160 KiB", need);
-        }
+    for (int i = 0; i < lo.nbuf; ++i) {
+        const PlanBuf &b = lo.buf[i];
+        void **p = buf_field(h, b.id);
+        if ((rc = dev_alloc(h, p, b.bytes))) return rc;
+        if (b.zero && hipMemset(*p, 0, b.bytes) != hipSuccess) return fail(TDMPC2_ERR_HIP, "hipMemset(%s) failed", b.name);
     }
+    if (L.on) L.bias_tab = h->beff;
     // torch.linspace(vmin, vmax, num_bins) in fp32 (math.py:80): float step, product rounded once
     std::vector<float> bins(c.num_bins > 1 ? c.num_bins : 2, 0.f);
-    if (c.num_bins > 1)
-    {
+    if (c.num_bins > 1) {
         const float step = (c.vmax - c.vmin) / (float)(c.num_bins - 1);
         for (int i = 0; i < c.num_bins; ++i)
             bins[i] = (i < c.num_bins / 2) ? (float)((double)c.vmin + (double)step * i)
                                            : (float)((double)c.vmax - (double)step * (c.num_bins - 1 - i));
     }
-    if ((rc = dev_alloc(h, (void **)&h->bins, bins.size() * 4)) ||
-        (rc = dev_alloc(h, (void **)&h->actions, E * H * N * A * 4)) ||
-        (rc = dev_alloc(h, (void **)&h->value, E * N * 4)) ||
-        (rc = dev_alloc(h, (void **)&h->mean, E * H * A * 4)) ||
-        (rc = dev_alloc(h, (void **)&h->std, E * H * A * 4)) ||
-        (rc = dev_alloc(h, (void **)&h->ticket, E * 4)) || (rc = dev_alloc(h, (void **)&h->qidx_buf, E * 2 * 4))) {
-        tdmpc2_plan_destroy(h);
-        return rc;
-    }
-    if (hipMemset(h->ticket, 0, E * 4) != hipSuccess) {
-        tdmpc2_plan_destroy(h);
-        return fail(TDMPC2_ERR_HIP, "hipMemset(ticket) failed");
-    }
-    if (!h->split) {  // unit scale of the exact arithmetic (LayerS::oscale / ascale)
-        const float one = 1.f;
-        if ((rc = dev_alloc(h, (void **)&h->one, 4)) || hipMemcpy(h->one, &one, 4, hipMemcpyHostToDevice) != hipSuccess) {
-            tdmpc2_plan_destroy(h);
-            return fail(TDMPC2_ERR_HIP, "allocating the unit output scale failed");
-        }
-    }
-    if (!h->lay.on) {
-        if ((rc = dev_alloc(h, (void **)&h->cvec, E * 2 * WIDTH * 4)) ||
-            (rc = dev_alloc(h, (void **)&h->beff, E * h->nnets * WIDTH * 4)) ||
-            (rc = dev_alloc(h, (void **)&h->zscratch, E * h->tiles * ROWS * WIDTH * 4))) {
-            tdmpc2_plan_destroy(h);
-            return rc;
-        }
-    } else {
-        Layered &L = h->lay;
-        L.Kin = (int)round_up((size_t)c.latent_dim + A, GBK);
-        L.Mp = c.mlp_dim;
-        L.ldl = (int)round_up((size_t)(c.num_bins > 2 * c.action_dim ? c.num_bins : 2 * c.action_dim), 32);
-        L.Ppad = (int)round_up((size_t)(c.num_pi_trajs > 0 ? c.num_pi_trajs : 1), 32);
-        const size_t Rp = round_up(E * N, GBM);  // the policy-prior pass (E * Ppad rows) reuses the same buffers
-        // beff is read per ROW of a GEMM tile; tiles of the policy-prior pass may run past the last plan: + 4 plans
-        if ((rc = dev_alloc(h, (void **)&L.X, Rp * L.Kin * 4)) || (rc = dev_alloc(h, (void **)&L.HA, Rp * L.Mp * 4)) ||
-            (rc = dev_alloc(h, (void **)&L.HB, Rp * L.Mp * 4)) || (rc = dev_alloc(h, (void **)&L.LG, Rp * L.ldl * 4)) ||
-            (rc = dev_alloc(h, (void **)&L.G, Rp * 4)) || (rc = dev_alloc(h, (void **)&L.QT, Rp * 4)) ||
-            (rc = dev_alloc(h, (void **)&L.TERM, Rp * 4)) || (rc = dev_alloc(h, (void **)&L.qidx, E * 2 * 4)) ||
-            (rc = dev_alloc(h, (void **)&h->beff, (round_up(E, GBM) + 4) * h->nnets * L.Mp * 4))) {
-            tdmpc2_plan_destroy(h);
-            return rc;
-        }
-        L.bias_tab = h->beff;
-        if (h->split) {  // lay_cvec: z0 rows in operand form (one per plan, padded to a GEMM tile), cvec [2][rows][Mp]
-            L.cvec_rows = round_up(E, GBM);
-            if ((rc = dev_alloc(h, (void **)&L.Z0X, L.cvec_rows * L.Kin * 4)) || (rc = dev_alloc(h, (void **)&L.cvec, 2 * L.cvec_rows * L.Mp * 4))) {
-                tdmpc2_plan_destroy(h);
-                return rc;
-            }
-            if (hipMemset(L.Z0X, 0, L.cvec_rows * L.Kin * 4) != hipSuccess) {
-                tdmpc2_plan_destroy(h);
-                return fail(TDMPC2_ERR_HIP, "hipMemset(workspace) failed");
-            }
-        }
-        // second chain (reward || dynamics, Q head || Q head): buffers, stream, events
-        if (!getenv("TDMPC2_ONE_STREAM")) {
-            if ((rc = dev_alloc(h, (void **)&L.HA2, Rp * L.Mp * 4)) || (rc = dev_alloc(h, (void **)&L.HB2, Rp * L.Mp * 4)) ||
-                (rc = dev_alloc(h, (void **)&L.LG2, Rp * L.ldl * 4))) {
-                tdmpc2_plan_destroy(h);
-                return rc;
-            }
-            SideRes sr;
-            if (hipMemset(L.HA2, 0, Rp * L.Mp * 4) != hipSuccess || hipMemset(L.HB2, 0, Rp * L.Mp * 4) != hipSuccess ||
-                !side_acquire(c.device, &sr)) {
-                tdmpc2_plan_destroy(h);
-                return fail(TDMPC2_ERR_HIP, "creating the second stream of the layered path failed");
-            }
-            L.side = sr.stream; L.ev_fork = sr.ev[0]; L.ev_side = sr.ev[1]; L.ev_xread = sr.ev[2];
-        }
-        if (h->split) {  // fused NormedLinear epilogue: exchange buffer, counters, error word
-            const size_t maxct = (size_t)(std::max(c.mlp_dim, c.latent_dim) + 31) / 32;
-            L.stats_cap = Rp * ((maxct + 3) / 4) * 2;
-            L.arrive_cap = 64 * (Rp / 32);
-            L.arrive_cap *= 2;  // two chains
-            if ((rc = dev_alloc(h, (void **)&L.stats, L.stats_cap * 4)) || (rc = dev_alloc(h, (void **)&L.stats2, L.stats_cap * 4)) ||
-                (rc = dev_alloc(h, (void **)&L.arrive, L.arrive_cap * 4))) {
-                tdmpc2_plan_destroy(h);
-                return rc;
-            }
-            if (hipMemset(L.arrive, 0, L.arrive_cap * 4) != hipSuccess ||
-                hipHostMalloc((void **)&h->cl_err_host, 64, hipHostMallocMapped) != hipSuccess) {
-                tdmpc2_plan_destroy(h);
-                return fail(TDMPC2_ERR_HIP, "allocating the fused-epilogue counters / error word failed");
-            }
-            memset(h->cl_err_host, 0, 64);  // hipHostMalloc does not zero: word 0 (verdict) AND word 8 (sticky, fault_poll)
-            if (hipHostGetDevicePointer((void **)&h->cl_err_dev, h->cl_err_host, 0) != hipSuccess) {
-                tdmpc2_plan_destroy(h);
-                return fail(TDMPC2_ERR_HIP, "hipHostGetDevicePointer failed");
-            }
-            L.fuse_ln = true;
-            if (const char *fl = getenv("TDMPC2_FUSE_LN")) L.fuse_ln = atoi(fl) != 0;
-            // g_gemm_w's K-split tail: 256 KiB per (split tile, part); at most 32 tail tiles per XCD x 4 parts, or all the tiles
-            // of the handle's largest call (one workspace per chain)
-            if (const char *ks = getenv("TDMPC2_KSPLIT")) L.ksplit = std::min(2, std::max(0, atoi(ks)));
-            L.ks_tiles = (Rp % 256 == 0 && maxct >= 8) ? (Rp / 256) * ((maxct + 7) / 8) : 0;
-            if ((rc = ksws_ensure(h, L.ksplit))) {
-                tdmpc2_plan_destroy(h);
-                return rc;
-            }
-            // the few-row path (layered_mid.cuh): partial sums of a launch's two problems -- parts x tiles <= #CUs tiles of 64 x 256
-            // (128 x 256) floats each.  Only where a single plan fits the chip in one round of such tiles, and the second buffer set exists.
-            {
-                const size_t cus = (size_t)(h->num_cus > 0 ? h->num_cus : 256);
-                if (L.HA2 && ((size_t)N + 127) / 128 * ((maxct + 7) / 8) <= cus) {
-                    L.mws_cap = cus * 128 * 256;
-                    if ((rc = dev_alloc(h, (void **)&L.mws[0], L.mws_cap * 4)) || (rc = dev_alloc(h, (void **)&L.mws[1], L.mws_cap * 4))) {
-                        tdmpc2_plan_destroy(h);
-                        return rc;
-                    }
-                }
-                if (const char *fr = getenv("TDMPC2_FEWROW")) L.mid = atoi(fr) != 0;
-            }
-            // fp32 pre-activations of the NormedLinear layers whose epilogue is not fused (the fallback after a reported wait,
-            // TDMPC2_TUNE_FUSE_LN = 0, tiles the fused path does not take): one buffer per chain
-#ifdef GW_TIMING
-            if (getenv("TDMPC2_GW_TIMING")) {
-                if ((rc = dev_alloc(h, (void **)&L.gw_timing, 32 * 8)) || hipMemset(L.gw_timing, 0, 32 * 8) != hipSuccess) {
-                    tdmpc2_plan_destroy(h);
-                    return rc ? rc : fail(TDMPC2_ERR_HIP, "hipMemset failed");
-                }
-            }
-#endif
-            L.ldpre = std::max(L.Mp, (int)round_up((size_t)c.latent_dim, 32));
-            if ((rc = dev_alloc(h, (void **)&L.PRE, Rp * L.ldpre * 4)) || (L.side && (rc = dev_alloc(h, (void **)&L.PRE2, Rp * L.ldpre * 4)))) {
-                tdmpc2_plan_destroy(h);
-                return rc;
-            }
-        }
-        // stale rows of padded tiles are computed but never read back; start them finite
-        if (hipMemset(L.X, 0, Rp * L.Kin * 4) != hipSuccess || hipMemset(L.HA, 0, Rp * L.Mp * 4) != hipSuccess ||
-            hipMemset(L.HB, 0, Rp * L.Mp * 4) != hipSuccess || hipMemset(h->beff, 0, (round_up(E, GBM) + 4) * h->nnets * L.Mp * 4) != hipSuccess) {
-            tdmpc2_plan_destroy(h);
-            return fail(TDMPC2_ERR_HIP, "hipMemset(workspace) failed");
-        }
-    }
-    if (hipMemcpy(h->bins, bins.data(), bins.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        tdmpc2_plan_destroy(h);
+    if (hipMemcpy(h->bins, bins.data(), bins.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
         return fail(TDMPC2_ERR_HIP, "hipMemcpy(bins) failed");
+    const float one = 1.f;
+    if (h->one && hipMemcpy(h->one, &one, 4, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(TDMPC2_ERR_HIP, "allocating the unit output scale failed");
+    if (lo.second_chain) {
+        SideRes sr;
+        if (!side_acquire(c.device, &sr)) return fail(TDMPC2_ERR_HIP, "creating the second stream of the layered path failed");
+        L.side = sr.stream; L.ev_fork = sr.ev[0]; L.ev_side = sr.ev[1]; L.ev_xread = sr.ev[2];
     }
+    if (lo.err_line && (rc = err_line_create(h))) return rc;
     if (hipEventCreateWithFlags(&h->turn_ev, hipEventDisableTiming) != hipSuccess) {  // (StreamTurn)
         h->turn_ev = nullptr;
-        tdmpc2_plan_destroy(h);
         return fail(TDMPC2_ERR_HIP, "hipEventCreate failed");
     }
-    if (pl_set_lds()) {  // (both families: the running scale's key array)
-        tdmpc2_plan_destroy(h);
-        return TDMPC2_ERR_HIP;
-    }
-    if (!h->lay.on) {
+    if (pl_set_lds()) return TDMPC2_ERR_HIP;  // (both families: the running scale's key array)
+    if (!L.on) {
         const int ar = h->split ? 0 : 1;
         rc = fused_ops(h->Apad).set_lds(ar, c.episodic, h->lds_bytes);
         if (!rc) rc = model_ops(h->Apad).set_lds(ar, h->lds_bytes);
         if (!rc) rc = policy_loss_ops(h->Apad).set_lds(ar, h->lds_bytes);
-        if (rc) {
-            tdmpc2_plan_destroy(h);
-            return TDMPC2_ERR_HIP;
+        if (!rc && h->cl_max_clusters) rc = cluster_ops(h->Apad).set_lds(c.episodic, h->cl_lds);
+        if (rc) return TDMPC2_ERR_HIP;
+    }
+    if (L.on && h->split) {
+        L.fuse_ln = env.fuse_ln;
+        L.ksplit = env.ksplit;
+        L.mid = env.fewrow;
+        if ((rc = ksws_ensure(h, L.ksplit))) return rc;
+        if (env.gw_timing) {
+            if ((rc = dev_alloc(h, (void **)&L.gw_timing, 32 * 8))) return rc;
+            if (hipMemset(L.gw_timing, 0, 32 * 8) != hipSuccess) return fail(TDMPC2_ERR_HIP, "hipMemset failed");
         }
     }
-    // cluster path (single-plan latency): split arithmetic, sized for the calls that fit the chip in one round
-    if (!h->lay.on && h->split) {
-        const long cus = h->num_cus > 0 ? h->num_cus : 256;
-        const long per_env = (long)h->tiles * 2;                       // 32-row tiles = clusters per plan
-        long envs = std::min<long>((long)c.max_envs, cus / (per_env * CL));
-        const size_t tail = ((size_t)2 * c.horizon * c.action_dim * 4 + 15) / 16 * 16;
-        h->cl_lds = (size_t)32 * h->row_bytes + 8192 + tail + (size_t)2 * 8 * 4 * 64 * 16 + 64;
-        if (envs >= 1 && h->cl_lds <= 160 * 1024) {
-            const size_t ncl = (size_t)(envs * per_env);
-            if ((rc = dev_alloc(h, (void **)&h->cl_xbuf, ncl * CL_SLOTS * CL_TILE * 4)) ||
-                (rc = dev_alloc(h, (void **)&h->cl_zs, ncl * CL * 32 * WIDTH * 4)) ||
-                (rc = dev_alloc(h, (void **)&h->cl_flags, ncl * CL_FLAG_STRIDE * 4))) {
-                tdmpc2_plan_destroy(h);
-                return rc;
-            }
-            if (hipMemset(h->cl_flags, 0, ncl * CL_FLAG_STRIDE * 4) != hipSuccess ||
-                hipHostMalloc((void **)&h->cl_err_host, 64, hipHostMallocMapped) != hipSuccess) {
-                tdmpc2_plan_destroy(h);
-                return fail(TDMPC2_ERR_HIP, "allocating the cluster path's arrival / error words failed");
-            }
-            memset(h->cl_err_host, 0, 64);  // hipHostMalloc does not zero: word 0 (verdict) AND word 8 (sticky, fault_poll)
-            if (hipHostGetDevicePointer((void **)&h->cl_err_dev, h->cl_err_host, 0) != hipSuccess) {
-                tdmpc2_plan_destroy(h);
-                return fail(TDMPC2_ERR_HIP, "hipHostGetDevicePointer failed");
-            }
-            int rcl = 0;
-            rcl = cluster_ops(h->Apad).set_lds(c.episodic, h->cl_lds);
-            if (rcl) {
-                tdmpc2_plan_destroy(h);
-                return TDMPC2_ERR_HIP;
-            }
-            h->cl_max_clusters = (int)ncl;
-            // two clusters per tile for ONE plan (ks_rollout_cl2): needs every CU of the chip
-            if (!c.episodic && 2 * per_env * CL <= cus && c.horizon <= MAXH) {
-                const size_t n2 = (size_t)(2 * per_env);
-                if ((rc = dev_alloc(h, (void **)&h->cl2_xbuf, n2 * CL2_SLOTS_HOST * CL_TILE * 4)) ||
-                    (rc = dev_alloc(h, (void **)&h->cl2_zs, n2 * CL * 32 * WIDTH * 4)) ||
-                    (rc = dev_alloc(h, (void **)&h->cl2_flags, n2 * CL_FLAG_STRIDE * 4)) ||
-                    (rc = dev_alloc(h, (void **)&h->cl2_mail, (size_t)per_env * 32 * 2 * 4))) {
-                    tdmpc2_plan_destroy(h);
-                    return rc;
-                }
-                if (hipMemset(h->cl2_flags, 0, n2 * CL_FLAG_STRIDE * 4) != hipSuccess) {
-                    tdmpc2_plan_destroy(h);
-                    return fail(TDMPC2_ERR_HIP, "hipMemset(cl2 flags) failed");
-                }
-            }
-        }
-    }
-    if (const char *cm = getenv("TDMPC2_CLUSTER")) h->cluster_mode = atoi(cm);
+    h->cluster_mode = env.cluster;
     h->user_cluster_mode = h->cluster_mode;  // what was asked for (environment or default); set_tuning / fault recovery go through apply_modes
-    h->user_fuse_ln = h->lay.fuse_ln;
+    h->user_fuse_ln = L.fuse_ln;
 #ifdef TDMPC2_TEST_HOOKS  // libtdmpc2_plan_hooks.so (built beside the product library, loaded by the GPU tests of the fault paths only)
     if (const char *cf = getenv("TDMPC2_CLUSTER_FAULT")) h->cl_fault = atoi(cf);
 #endif
-    if (h->cl_fault) h->lay.mid = false;  // the hook mutes a workgroup of the WAITING paths: the handle runs them (the few-row path has no waits)
-#ifdef SPLIT_TIMING  // in-kernel phase timers exist in -DSPLIT_TIMING builds only (tools/ablate.sh)
-    if (getenv("TDMPC2_TIMING")) {
-        if (dev_alloc(h, (void **)&h->timing, 16 * 8) == 0) (void)hipMemset(h->timing, 0, 16 * 8);
-    }
-#endif
+    if (h->cl_fault) L.mid = false;  // the hook mutes a workgroup of the WAITING paths: the handle runs them (the few-row path has no waits)
+    // in-kernel phase timers exist in -DSPLIT_TIMING builds only (tools/ablate.sh)
+    if (env.timing && dev_alloc(h, (void **)&h->timing, 16 * 8) == 0) (void)hipMemset(h->timing, 0, 16 * 8);
+    undo.h = nullptr;
     *out = h;
     return TDMPC2_OK;
 }

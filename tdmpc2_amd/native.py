@@ -292,6 +292,30 @@ def _chk_tensor(name, t, dtype, shape, device):
     return t
 
 
+def plan_cfg(cfg, iterations: int, max_envs: int = 1, device_index: int = 0, path: int = PATH_AUTO, precision: int = PREC_AUTO,
+             log_std_min: Optional[float] = None, log_std_dif: Optional[float] = None) -> PlanCfg:
+    """struct tdmpc2_plan_cfg of a handle for `max_envs` plans of `cfg`, as NativePlanner creates it."""
+    lsmin = float(cfg.log_std_min) if log_std_min is None else float(log_std_min)
+    lsdif = float(cfg.log_std_max) - float(cfg.log_std_min) if log_std_dif is None else float(log_std_dif)
+    # cfg.num_samples may be anything (config.yaml:36); the kernels own 64- / 128-row tiles.  The handle is created with the
+    # count rounded UP to the tile and told the true one (tdmpc2_plan_cfg::num_valid_samples): the padding rows are rolled out but
+    # can never be elites.
+    n_true = int(cfg.num_samples)
+    # the family create will choose: the rule's home is plan_layout (tdmpc2_amd/csrc/plan_layout.h); repeated here only to round
+    # num_samples before create sees it (asking create instead needs an ABI call)
+    fused_ok = int(cfg.latent_dim) == 512 and int(cfg.mlp_dim) == 512 and int(path) != PATH_LAYERED
+    tile = 64 if fused_ok else 128  # rows a workgroup owns: fused family 64, layered family 128
+    npad = (n_true + tile - 1) // tile * tile
+    return PlanCfg(horizon=cfg.horizon, num_samples=npad, num_valid_samples=(n_true if npad != n_true else 0),
+                   num_elites=cfg.num_elites,
+                   num_pi_trajs=cfg.num_pi_trajs, iterations=int(iterations), action_dim=cfg.action_dim,
+                   latent_dim=cfg.latent_dim, mlp_dim=cfg.mlp_dim, task_dim=cfg.task_dim, num_bins=cfg.num_bins,
+                   num_q=cfg.num_q, simnorm_dim=cfg.simnorm_dim, vmin=cfg.vmin, vmax=cfg.vmax, min_std=cfg.min_std,
+                   max_std=cfg.max_std, temperature=cfg.temperature, log_std_min=lsmin, log_std_dif=lsdif,
+                   multitask=int(bool(cfg.multitask)), episodic=int(bool(cfg.episodic)), max_envs=int(max_envs),
+                   device=device_index, path=int(path), precision=int(precision))
+
+
 class NativePlanner:
     """Owns one `tdmpc2_plan_t` handle on one GPU.
 
@@ -313,23 +337,9 @@ class NativePlanner:
         self.device = device
         self.iterations = int(iterations)
         self.max_envs = int(max_envs)
-        lsmin = float(cfg.log_std_min) if log_std_min is None else float(log_std_min)
-        lsdif = float(cfg.log_std_max) - float(cfg.log_std_min) if log_std_dif is None else float(log_std_dif)
-        # cfg.num_samples may be anything (config.yaml:36); the kernels own 64- / 128-row tiles.  The handle is created with the
-        # count rounded UP to 128 and told the true one (tdmpc2_plan_cfg::num_valid_samples): the padding rows are rolled out but
-        # can never be elites.  self.cfg keeps the caller's count; tapes are padded and stages sliced at this boundary.
-        n_true = int(cfg.num_samples)
-        fused_ok = int(cfg.latent_dim) == 512 and int(cfg.mlp_dim) == 512 and int(path) != PATH_LAYERED
-        tile = 64 if fused_ok else 128  # rows a workgroup owns: fused family 64, layered family 128
-        self._npad = (n_true + tile - 1) // tile * tile
-        c = PlanCfg(horizon=cfg.horizon, num_samples=self._npad, num_valid_samples=(n_true if self._npad != n_true else 0),
-                    num_elites=cfg.num_elites,
-                    num_pi_trajs=cfg.num_pi_trajs, iterations=self.iterations, action_dim=cfg.action_dim,
-                    latent_dim=cfg.latent_dim, mlp_dim=cfg.mlp_dim, task_dim=cfg.task_dim, num_bins=cfg.num_bins,
-                    num_q=cfg.num_q, simnorm_dim=cfg.simnorm_dim, vmin=cfg.vmin, vmax=cfg.vmax, min_std=cfg.min_std,
-                    max_std=cfg.max_std, temperature=cfg.temperature, log_std_min=lsmin, log_std_dif=lsdif,
-                    multitask=int(bool(cfg.multitask)), episodic=int(bool(cfg.episodic)), max_envs=self.max_envs,
-                    device=device.index, path=int(path), precision=int(precision))
+        # self.cfg keeps the caller's num_samples; tapes are padded and stages sliced at the handle's (plan_cfg)
+        c = plan_cfg(cfg, self.iterations, self.max_envs, device.index, path, precision, log_std_min, log_std_dif)
+        self._npad = int(c.num_samples)
         h = C.c_void_p()
         with torch.cuda.device(device):  # the library restores the caller's device itself; this keeps torch's view in step
             self._check(self.lib.tdmpc2_plan_create(C.byref(c), C.byref(h)))

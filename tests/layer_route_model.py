@@ -1,5 +1,6 @@
 """The layered family's GEMM launches of one plan, as the host issues them -- every route from tdmpc2_amd/csrc/layer_route.h itself
-(compiled with g++ behind the C shim below), the sequence and the handle's capacities from layered_host.cuh / tdmpc2_plan.hip.
+(compiled with g++ behind the C shim below), the handle's capacities from tdmpc2_amd/csrc/plan_layout.h itself (the same shim), the
+sequence from layered_host.cuh.
 
 Used by tests/test_layer_route.py (the route table of the benched geometries) and tests/test_tile_order.py (the dispatcher model of
 the launches whose workgroups wait for each other)."""
@@ -10,7 +11,11 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 ROUTE_SHIM = r"""
+#include <cstring>
+
 #include "layer_route.h"
+#include "plan_layout.h"
+using namespace tdk;
 static LayCtx ctx_of(const long *c, const int *knob) {
     return LayCtx{c[0], (int)c[1], c[2] != 0, c[3] != 0, c[4] != 0, (size_t)c[5], (size_t)c[6], c[7] != 0, (size_t)c[8], c[9] != 0,
                   (size_t)c[10], knob};
@@ -38,12 +43,34 @@ extern "C" void mid_route_c(const long *in, const long *c, const int *knob, long
         *o++ = p.nwg;
     }
 }
+// env: one_stream, fuse_ln, ksplit, fewrow, cluster.  Returns the refusal's code (msg: its text), or 0 and the layout: sc (LAYOUT_FIELDS), then
+// per buffer its id, name, bytes and whether it starts zeroed
+extern "C" int plan_layout_c(const tdmpc2_plan_cfg *cfg, int num_cus, const int *env, char *msg, long *sc, int *ids, const char **names,
+                             long *bytes, int *zero) {
+    CreateEnv e;
+    e.one_stream = env[0] != 0; e.fuse_ln = env[1] != 0; e.ksplit = env[2]; e.fewrow = env[3] != 0; e.cluster = env[4];
+    const PlanLayout lo = plan_layout(*cfg, num_cus, e);
+    strcpy(msg, lo.msg);
+    if (lo.err) return lo.err;
+    const long v[] = {lo.path, lo.precision, lo.layered, lo.split, lo.second_chain, lo.err_line, lo.Apad, lo.tiles, lo.nnets, lo.stride,
+                      (long)lo.row_bytes, (long)lo.lds_bytes, (long)lo.cl_lds, lo.cl_max_clusters, lo.Kin, lo.Mp, lo.ldl, lo.Ppad, lo.ldpre,
+                      (long)lo.cvec_rows, (long)lo.stats_cap, (long)lo.arrive_cap, (long)lo.ks_tiles, (long)lo.mws_cap, plan_maxct(*cfg), lo.nbuf};
+    for (size_t i = 0; i < sizeof v / sizeof v[0]; ++i) sc[i] = v[i];
+    for (int i = 0; i < lo.nbuf; ++i) { ids[i] = lo.buf[i].id; names[i] = lo.buf[i].name; bytes[i] = (long)lo.buf[i].bytes; zero[i] = lo.buf[i].zero; }
+    return 0;
+}
+extern "C" long ksws_slots_c(long ks_tiles, int num_cus, int mode) { return (long)ksws_slots((size_t)ks_tiles, num_cus, mode); }
+extern "C" long ks_slot_bytes() { return (long)(KS_SLOT_FLOATS * 4); }
+extern "C" int pb_count() { return PB_COUNT; }
 extern "C" int knob_count() { return LK_COUNT; }
 extern "C" void knob_spec(int i, int *out) { out[0] = LAY_KNOBS[i].def; out[1] = LAY_KNOBS[i].lo; out[2] = LAY_KNOBS[i].hi; }
 """
 
 ROUTE_FIELDS = ("w", "nct", "rt", "sd", "epi", "nrowblk", "ncolblk", "xcd_rows", "ncol_grid", "ord_nblk", "parts", "full", "max_tail",
                 "per_xcd", "wo_nblk", "grid", "arrive", "ln_after")
+LAYOUT_FIELDS = ("path", "precision", "layered", "split", "second_chain", "err_line", "Apad", "tiles", "nnets", "stride", "row_bytes",
+                 "lds_bytes", "cl_lds", "cl_max_clusters", "Kin", "Mp", "ldl", "Ppad", "ldpre", "cvec_rows", "stats_cap", "arrive_cap",
+                 "ks_tiles", "mws_cap", "maxct", "nbuf")
 MID_FIELDS = ("ws_ok", "split_xcd", "gblk", "nrow", "mr_threads", "serial", "rblk")
 MID_PROB_FIELDS = ("nk", "ncolblk", "nrowblk", "parts", "nblk", "epi", "reset", "arrive", "nwg")
 LR_PLAIN, LR_MISH, LR_SIMNORM, LR_TWOHOT = 0, 1, 2, 3
@@ -63,7 +90,38 @@ def build(tmpdir, extra_src=""):
     lib.mid_ok_c.argtypes = [ci, ci, ci, ci, ci, ci, cl, ci, cl]
     lib.mid_route_c.argtypes = [pl, pl, pi, pl]
     lib.knob_spec.argtypes = [ci, pi]
+    lib.plan_layout_c.argtypes = [ctypes.c_void_p, ci, pi, ctypes.c_char_p, pl, pi, ctypes.POINTER(ctypes.c_char_p), pl, pi]
+    lib.ksws_slots_c.argtypes = [cl, ci, ci]
+    lib.ksws_slots_c.restype = lib.ks_slot_bytes.restype = cl
     return lib
+
+
+class Refused(Exception):
+    """plan_layout's refusal: args = (code, message)"""
+
+
+def plan_layout(lib, plan_cfg, num_cus=CUS, one_stream=False, fuse_ln=True, ksplit=2, fewrow=True, cluster=2):
+    """plan_layout (tdmpc2_amd/csrc/plan_layout.h) of a struct tdmpc2_plan_cfg (tdmpc2_amd.native.PlanCfg): the scalars by name
+    (LAYOUT_FIELDS) and "bufs": {name: (bytes, starts zeroed)}; Refused(code, message) where create refuses the configuration."""
+    n = lib.pb_count()
+    env = (ctypes.c_int * 5)(int(one_stream), int(fuse_ln), ksplit, int(fewrow), cluster)
+    msg = ctypes.create_string_buffer(512)
+    sc, ids, names = (ctypes.c_long * len(LAYOUT_FIELDS))(), (ctypes.c_int * n)(), (ctypes.c_char_p * n)()
+    nbytes, zero = (ctypes.c_long * n)(), (ctypes.c_int * n)()
+    rc = lib.plan_layout_c(ctypes.byref(plan_cfg), num_cus, env, msg, sc, ids, names, nbytes, zero)
+    if rc:
+        raise Refused(rc, msg.value.decode())
+    lo = dict(zip(LAYOUT_FIELDS, sc))
+    lo["bufs"] = {names[i].decode(): (nbytes[i], bool(zero[i])) for i in range(lo["nbuf"])}
+    assert len(lo["bufs"]) == lo["nbuf"] == len(set(ids[:lo["nbuf"]]))  # every entry its own name and handle field
+    return lo
+
+
+def layout_bytes(lib, lo, num_cus=CUS, ksplit=2):
+    """Device bytes of a handle with this layout whose K-split mode is (or has been raised to) `ksplit`: the table plus the K-split
+    workspaces, one per chain (ksws_ensure)."""
+    slots = lib.ksws_slots_c(lo["ks_tiles"], num_cus, ksplit)
+    return sum(b for b, _ in lo["bufs"].values()) + slots * lib.ks_slot_bytes() * (2 if lo["second_chain"] else 1)
 
 
 def knob_defaults(lib):
@@ -80,26 +138,20 @@ def _ru(x, m):
 
 
 class Handle:
-    """What a layered, split-arithmetic handle created for E plans of `cfg` holds (tdmpc2_plan.hip: create, ksws_ensure), with the
+    """What a layered, split-arithmetic handle created for E plans of `cfg` holds (plan_layout.h: plan_layout, ksws_slots), with the
     K-split mode set to `ksplit` after creation (tdmpc2_plan_set_tuning) and the arrival counters of the stage it is in."""
 
     def __init__(self, lib, cfg, E, ksplit=2, cus=CUS):
         self.lib, self.cfg, self.E, self.ksplit, self.cus = lib, cfg, E, ksplit, cus
-        L, M, A, N = cfg.latent_dim, cfg.mlp_dim, cfg.action_dim, cfg.num_samples
-        self.Kin, self.Mp = _ru(L + A, 32), M
-        self.Ppad = _ru(max(cfg.num_pi_trajs, 1), 32)
-        Rp = _ru(E * N, 128)
-        self.maxct = (max(M, L) + 31) // 32
-        self.stats_cap = Rp * ((self.maxct + 3) // 4) * 2
-        self.arrive_cap = 64 * (Rp // 32) * 2
-        ks_tiles = (Rp // 256) * ((self.maxct + 7) // 8) if Rp % 256 == 0 and self.maxct >= 8 else 0
+        from tdmpc2_amd import native
 
-        def slots(mode):
-            cap = 8 * ((cus // 16 + 3) // 4 * 4) * 4 if mode == 2 else 8 * 32 * 4
-            return min(cap, ks_tiles * 4) if ks_tiles and mode else 0
-        self.ksws_slots = max(slots(2), slots(ksplit))  # created in mode 2, grown (never shrunk) by the mode set afterwards
-        self.mws = (N + 127) // 128 * ((self.maxct + 7) // 8) <= cus
-        self.mws_cap = cus * 128 * 256
+        lo = plan_layout(lib, native.plan_cfg(cfg, cfg.iterations, E), cus)  # created with the default switches (K-split mode 2)
+        assert lo["layered"] and lo["split"] and lo["second_chain"]
+        for k in ("Kin", "Mp", "Ppad", "maxct", "stats_cap", "arrive_cap", "mws_cap"):
+            setattr(self, k, lo[k])
+        # grown (never shrunk) by the mode set afterwards
+        self.ksws_slots = max(lib.ksws_slots_c(lo["ks_tiles"], cus, 2), lib.ksws_slots_c(lo["ks_tiles"], cus, ksplit))
+        self.mws = "mws[0]" in lo["bufs"]
         self.knob = (ctypes.c_int * lib.knob_count())(*knob_defaults(lib))
         self.arrive_off, self.pending = 0, False
 
