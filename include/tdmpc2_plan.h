@@ -19,6 +19,7 @@
  *   tdmpc2_plan_run_obs       <- TDMPC2._plan including encode()        tdmpc2/tdmpc2.py:152-206
  *   tdmpc2_plan_bind_pixel_encoder <- the pixel encoder's parameters    tdmpc2/common/layers.py:136-150
  *   tdmpc2_plan_encode_pix    <- WorldModel.encode (rgb observations)   tdmpc2/common/layers.py:36-71,136-150
+ *   tdmpc2_plan_encode_pix_batch <- the same on the frame stacks of a training batch (TDMPC2._update, tdmpc2.py:259-267)
  *   tdmpc2_plan_run_pix       <- TDMPC2._plan including encode(), rgb   tdmpc2/tdmpc2.py:152-206
  *   tdmpc2_plan_bind_policy   <- the policy prior's parameters (_pi)    tdmpc2/common/world_model.py:32
  *   tdmpc2_plan_pi            <- WorldModel.pi                          tdmpc2/common/world_model.py:144-184
@@ -258,6 +259,20 @@ int tdmpc2_plan_encode_pix(tdmpc2_plan_t *h, int n_envs, const void *obs, int ob
 int tdmpc2_plan_run_pix(tdmpc2_plan_t *h, int n_envs, const void *obs, int obs_dtype, int in_channels, const int32_t *shift,
                         const float *disc_pow, float *prev_mean, const uint8_t *t0, int eval_mode, const tdmpc2_noise *tape,
                         uint64_t seed, float *action, void *stream);
+
+/* Pixel encoder, batch route (additions to ABI 14; the version number stays 14): the same network on TRAINING batches -- the
+ * (H + 1) B frame stacks of TDMPC2._update -- as exact-fp32 MFMA implicit GEMMs (one fmaf chain per output element, like the
+ * planning routes).  Reads the weights tdmpc2_plan_bind_pixel_encoder bound (binding again after a reservation keeps working).
+ * Single-task handles only.
+ * pix_batch_reserve: workspace of the batch route for `chunk_images` images per pass; may be called again with a larger value
+ * (grows, never shrinks); needs a bound pixel encoder; allocates -- encode_pix_batch never does.  Not part of create:
+ * device_bytes of a handle that never reserves is unchanged. */
+int tdmpc2_plan_pix_batch_reserve(tdmpc2_plan_t *h, int chunk_images, void *stream);
+/* obs [n, Cin, 64, 64] uint8 / float32, shift int32 [n, 2] (as encode_pix) -> z_out [n, 16 C]; any n >= 1 (not bounded by
+ * max_envs): passes of the reserved chunk, four launches each, ordered by the stream.  No host synchronisation.
+ * TDMPC2_ERR_STATE without a bound encoder or a reservation. */
+int tdmpc2_plan_encode_pix_batch(tdmpc2_plan_t *h, int n_images, const void *obs, int obs_dtype, int in_channels,
+                                 const int32_t *shift, float *z_out, void *stream);
 
 /* Policy prior (ABI 11): WorldModel.pi (tdmpc2/common/world_model.py:144-184, common/math.py:12-29) and TDMPC2.act's branch
  * without planning (tdmpc2/tdmpc2.py:114-120), plain fp32.  bind_policy takes _pi.{layer}: layer 0 [M, L + T] and 1 [M, M]

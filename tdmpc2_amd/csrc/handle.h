@@ -175,6 +175,10 @@ struct tdmpc2_plan {
         int C = 0, cin = 0;
         void *tab = nullptr;  // PixTap [7][64]: ShiftAug's resampling table (pixel_route.h)
         float *ws = nullptr;  // [max_envs][pix_ws_floats(C)] layer outputs of the spread route
+        // batch route (tdmpc2_plan_pix_batch_reserve / encode_pix_batch; pixel_batch_route.h): [bchunk][pix_ws_floats(C)], grown by reserve
+        float *bws = nullptr;
+        size_t bws_cap = 0;   // floats
+        int bchunk = 0;       // images per pass (0: nothing reserved)
     } pix;
     // policy prior (optional: bound with tdmpc2_plan_bind_policy; policy_kernels.cuh, policy_route.h)
     struct Pol {

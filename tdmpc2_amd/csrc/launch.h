@@ -2,6 +2,7 @@
 // in exactly one translation unit; everything else reaches it through these functions / tables.
 #pragma once
 #include "handle.h"
+#include "pixel_batch_route.h"
 #include "policy_route.h"
 
 // ---- policy prior (k_policy.hip: policy_kernels.cuh, routes in policy_route.h)
@@ -37,6 +38,18 @@ struct PolGemvParams {
 struct PolHeadParams {
     const float *y;  // [n, 2A] output-layer pre-activations
     PolHeadArgs head;
+};
+
+// ---- pixel encoder, batch route (k_pixel_batch.hip: pixel_batch_kernels.cuh, decisions in pixel_batch_route.h)
+struct PixbParams {
+    const float *wp[PIX_LAYERS];    // [cin][k][k][C] re-packed Conv2d weights (the planning routes' copy)
+    const float *bias[PIX_LAYERS];  // [C]
+    const void *obs;                // this pass's images: [n, cin, 64, 64] uint8 or fp32
+    int cin, C, n;
+    const int32_t *shift;           // [n, 2] (dx, dy), clamped to [0, 6] in the kernel
+    const PixTap *tab;              // [PIX_SHIFTS][PIX_IN]
+    float *ws;                      // [chunk][pix_ws_floats(C)] outputs of layers 0..2
+    float *z;                       // [n, 16 C]
 };
 
 namespace tdk {
@@ -127,6 +140,10 @@ int pl_launch_term_stats(const TerminationStatsParams &p, hipStream_t st);
 // ---- grouped weight refresh (k_refresh.hip: refresh_kernels.cuh, launch list in refresh_route.h)
 #include "refresh_params.h"
 int refresh_launch(int op /* RO_* */, const RfParams &p, hipStream_t st);
+
+// ---- pixel encoder, batch route (k_pixel_batch.hip)
+int pixb_set_lds(size_t bytes);  // layer 0's dynamic LDS limit (at reserve)
+int pixb_launch(int layer, bool obs_u8, const PixbParams &p, const PixGrid &g, hipStream_t st);
 
 // ---- policy prior (k_policy.hip)
 int pol_set_lds();  // the GEMV instantiations' dynamic LDS limit (once per handle, at bind)

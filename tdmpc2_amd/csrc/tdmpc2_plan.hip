@@ -2586,4 +2586,60 @@ int tdmpc2_plan_refit(tdmpc2_plan_t *h, int n_envs, float *value, const float *a
     return TDMPC2_OK;
 }
 
+// ================================================================ pixel encoder, batch route (k_pixel_batch.hip, pixel_batch_route.h)
+// Training batches of frame stacks: any number of images, in passes over a workspace that tdmpc2_plan_pix_batch_reserve sized.
+// The weights, biases and ShiftAug table are the ones tdmpc2_plan_bind_pixel_encoder keeps for the planning routes.
+namespace {
+int check_pixb_handle(tdmpc2_plan *h) {
+    if (h->cfg.multitask) return fail(TDMPC2_ERR_UNSUPPORTED, "the pixel encoder is single-task only (multitask handle)");
+    for (int l = 0; l < PIX_LAYERS; ++l)
+        if (!h->pix.bound[l]) return fail(TDMPC2_ERR_STATE, "no pixel encoder bound (layer %d; tdmpc2_plan_bind_pixel_encoder)", l);
+    return 0;
+}
+}  // namespace
+
+int tdmpc2_plan_pix_batch_reserve(tdmpc2_plan_t *h, int chunk_images, void *stream) {
+    if (!h) return fail(TDMPC2_ERR_INVALID, "null handle");
+    if (chunk_images < 1) return fail(TDMPC2_ERR_INVALID, "chunk_images %d < 1", chunk_images);
+    int rc = check_pixb_handle(h);
+    if (rc) return rc;
+    ENTER_ON(h, stream);
+    tdmpc2_plan::Pix &P = h->pix;
+    if (chunk_images <= P.bchunk) return TDMPC2_OK;  // grows, never shrinks
+    if (!P.bchunk && (rc = tdk::pixb_set_lds(pixb_lds(0, PIX_MAX_C, PIX_MAX_CIN)))) return rc;
+    if ((rc = grow_ws(h, &P.bws, &P.bws_cap, (size_t)chunk_images * pix_ws_floats(P.C), (hipStream_t)stream))) return rc;
+    P.bchunk = chunk_images;
+    return TDMPC2_OK;
+}
+
+int tdmpc2_plan_encode_pix_batch(tdmpc2_plan_t *h, int n_images, const void *obs, int obs_dtype, int in_channels,
+                                 const int32_t *shift, float *z_out, void *stream) {
+    if (!h || !obs || !shift || !z_out) return fail(TDMPC2_ERR_INVALID, "null argument");
+    if (n_images < 1) return fail(TDMPC2_ERR_INVALID, "n_images %d < 1", n_images);
+    if (obs_dtype != 0 && obs_dtype != 1) return fail(TDMPC2_ERR_INVALID, "obs_dtype %d (0 = uint8, 1 = float32)", obs_dtype);
+    if (in_channels < 1 || in_channels > PIX_MAX_CIN)
+        return fail(TDMPC2_ERR_INVALID, "pixel encoder: %d input channels outside [1, %d]", in_channels, PIX_MAX_CIN);
+    int rc = check_pixb_handle(h);
+    if (rc) return rc;
+    const tdmpc2_plan::Pix &P = h->pix;
+    if (in_channels != P.cin)
+        return fail(TDMPC2_ERR_INVALID, "pixel encoder: the observation has %d channels, layer 0 was bound with %d", in_channels, P.cin);
+    if (!P.bchunk) return fail(TDMPC2_ERR_STATE, "no batch workspace reserved (tdmpc2_plan_pix_batch_reserve)");
+    ENTER_ON(h, stream);
+    PixbParams p{};
+    for (int l = 0; l < PIX_LAYERS; ++l) { p.wp[l] = P.wp[l]; p.bias[l] = P.bias[l]; }
+    p.cin = P.cin; p.C = P.C; p.tab = static_cast<const PixTap *>(P.tab); p.ws = P.bws;
+    const size_t img_bytes = (size_t)P.cin * PIX_IN * PIX_IN * (obs_dtype == 0 ? 1 : 4);
+    for (int i = 0; i < pixb_chunks(n_images, P.bchunk); ++i) {
+        const int e0 = pixb_chunk_begin(i, P.bchunk);
+        p.n = pixb_chunk_count(n_images, P.bchunk, i);
+        p.obs = static_cast<const char *>(obs) + (size_t)e0 * img_bytes;
+        p.shift = shift + 2 * (size_t)e0;
+        p.z = z_out + (size_t)e0 * 16 * P.C;
+        for (int l = 0; l < PIX_LAYERS; ++l)
+            if ((rc = tdk::pixb_launch(l, obs_dtype == 0, p, pixb_grid(l, p.n, P.C, P.cin), (hipStream_t)stream))) return rc;
+    }
+    return TDMPC2_OK;
+}
+
 }  // extern "C"

@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "tdmpc2_plan_model_rollout", "tdmpc2_plan_model_rollout_mt", "tdmpc2_plan_model_losses", "tdmpc2_plan_model_losses_mt",
     "tdmpc2_plan_policy_loss", "tdmpc2_plan_policy_loss_mt", "tdmpc2_plan_running_scale", "tdmpc2_plan_termination_stats",
     "tdmpc2_plan_refresh_weights", "tdmpc2_plan_soft_update_target",
+    "tdmpc2_plan_pix_batch_reserve", "tdmpc2_plan_encode_pix_batch",
 ]
 
 NET_DYNAMICS, NET_REWARD, NET_PI, NET_Q, NET_TERMINATION, NET_TARGET_Q = range(6)
@@ -191,6 +192,10 @@ def _open(path):
     lib.tdmpc2_plan_bind_pixel_encoder.restype = i32
     lib.tdmpc2_plan_encode_pix.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
     lib.tdmpc2_plan_encode_pix.restype = i32
+    lib.tdmpc2_plan_pix_batch_reserve.argtypes = [vp, i32, vp]
+    lib.tdmpc2_plan_pix_batch_reserve.restype = i32
+    lib.tdmpc2_plan_encode_pix_batch.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
+    lib.tdmpc2_plan_encode_pix_batch.restype = i32
     lib.tdmpc2_plan_run_pix.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, C.POINTER(Noise), u64, vp, vp]
     lib.tdmpc2_plan_run_pix.restype = i32
     lib.tdmpc2_plan_bind_policy.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, vp]
@@ -354,6 +359,7 @@ class NativePlanner:
         self.encoder_layers = 0
         self.obs_dim = None
         self.policy_bound = False
+        self.pix_batch_chunk = 0  # images per pass that reserve_pix_batch has sized the batch route's workspace for (0: nothing reserved)
 
     # ------------------------------------------------------------------ plumbing
     def _check(self, rc: int):
@@ -605,6 +611,30 @@ class NativePlanner:
         with torch.cuda.device(self.device):
             self._check(self.lib.tdmpc2_plan_encode_pix(self._h, E, _ptr(obs), dt, self.pix_channels, _ptr(shift), _ptr(z),
                                                         self._stream()))
+        return z
+
+    def reserve_pix_batch(self, chunk_images: int):
+        """Workspace of `encode_pix_batch` for `chunk_images` images per pass (grows, never shrinks; needs a bound pixel encoder).
+        The only call of the batch route that allocates."""
+        chunk_images = int(chunk_images)
+        if chunk_images < 1:
+            raise ValueError(f"chunk_images: expected >= 1, got {chunk_images}")
+        with torch.cuda.device(self.device):
+            self._check(self.lib.tdmpc2_plan_pix_batch_reserve(self._h, chunk_images, self._stream()))
+        self.pix_batch_chunk = max(self.pix_batch_chunk, chunk_images)
+
+    def encode_pix_batch(self, obs, shift, out: Optional[torch.Tensor] = None):
+        """WorldModel.encode on the frame stacks of a training batch: obs [n, Cin, 64, 64] (uint8 or fp32 pixel levels), shift
+        int32 [n, 2] (`draw_shift`) -> z [n, L], for any n >= 1 (not bounded by max_envs): passes of the chunk that
+        `reserve_pix_batch` sized, on the MFMA batch route."""
+        n, dt = self._pix_inputs(obs, shift)
+        if n < 1:
+            raise ValueError("obs: expected at least one image")
+        z = out if out is not None else torch.empty(n, self.cfg.latent_dim, device=self.device, dtype=torch.float32)
+        _chk_tensor("z", z, torch.float32, (n, self.cfg.latent_dim), self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.tdmpc2_plan_encode_pix_batch(self._h, n, _ptr(obs), dt, self.pix_channels, _ptr(shift), _ptr(z),
+                                                              self._stream()))
         return z
 
     def plan_pix(self, obs, shift, disc_pow, prev_mean, t0, eval_mode=False, tape: Optional[Dict[str, torch.Tensor]] = None,

@@ -53,6 +53,10 @@ class TDMPC2(torch.nn.Module):
         # True: rgb observations are encoded inside the library too (tdmpc2_plan_run_pix); off by default -- the PyTorch-ROCm
         # conv module encodes them and the planner is handed the latent
         self.native_pixel_encoder = False
+        # images per pass of the library's batch route for rgb training batches (model_losses / update_info with
+        # native_pixel_encoder): the workspace the agent reserves on first use (NativePlanner.reserve_pix_batch).  Raised later, the
+        # next call grows the workspace; lowered later, the reservation stays (the library never shrinks it) and so do the passes
+        self.pixel_batch_images = 256
         self._pix_shift = None      # ShiftAug's shifts of the last native pixel plan (a re-planned step reuses them)
         # True: act() with cfg.mpc == False (the policy prior, tdmpc2.py:114-120) runs inside the library too (tdmpc2_plan_act_pi /
         # act_pi_pix / pi); off by default -- the PyTorch-ROCm modules encode and evaluate _pi
@@ -455,7 +459,8 @@ class TDMPC2(torch.nn.Module):
     def model_losses(self, obs, action, reward, terminated=None, task=None, pi_eps=None, qidx=None, want=("zs",)):
         """The forward half of `_update` (reference tdmpc2.py:259-304) with its argument shapes: obs [H+1, B, *], action
         [H, B, A], reward / terminated [H, B, 1], task [B].  encode(obs[0]), encode(obs[1:]) (state observations in the library;
-        pixel observations through the PyTorch-ROCm modules), `_td_target`, then the rollout and the losses in one library call.
+        pixel observations through the PyTorch-ROCm modules or, with `native_pixel_encoder`, the library's batch route in one
+        call), `_td_target`, then the rollout and the losses in one library call.
         Returns the reference's loss keys plus td_targets [H, B, 1] and zs [H+1, B, L]."""
         cfg = self.cfg
         obs = obs.to(self.device)
@@ -469,6 +474,8 @@ class TDMPC2(torch.nn.Module):
                 t = torch.as_tensor(task, device=self.device).long()
                 emb = self.model._task_emb(t.repeat(H + 1)).to(torch.float32).contiguous()
             z_all = self.planner().encode(flat, emb).reshape(H + 1, B, cfg.latent_dim)
+        elif self._native_pix():
+            z_all = self._encode_pix_batch(obs, H, B)
         else:
             t = None if task is None else torch.as_tensor(task, device=self.device)
             z_all = torch.stack([self.model.encode(obs[i], t) for i in range(H + 1)])
@@ -477,6 +484,20 @@ class TDMPC2(torch.nn.Module):
         res = self.model_losses_latent(z0, next_z, action, reward, td, terminated, task, want=want)
         res["td_targets"] = td
         return res
+
+    def _encode_pix_batch(self, obs, H, B):
+        """encode(obs[i]) for i = 0 .. H in one library call (tdmpc2_plan_encode_pix_batch): ShiftAug's shifts are drawn on the host
+        framework's generator once per time step, in the order and with the calls of the module branch."""
+        planner = self.planner()
+        if planner.__dict__.get("pix_channels") is None:  # flag set after the handle was made
+            self._bind_pixel_encoder()
+        if planner.pix_batch_chunk < self.pixel_batch_images:  # first use, or the attribute was raised since
+            planner.reserve_pix_batch(self.pixel_batch_images)
+        if obs.dtype not in (torch.uint8, torch.float32):
+            obs = obs.to(torch.float32)
+        flat = obs.reshape((H + 1) * B, *obs.shape[2:]).contiguous()
+        shift = torch.cat([planner.draw_shift(B, self.device) for _ in range(H + 1)])
+        return planner.encode_pix_batch(flat, shift).reshape(H + 1, B, self.cfg.latent_dim)
 
     # ------------------------------------------------------------------ update_pi's forward and the info dict of _update
     @torch.no_grad()
