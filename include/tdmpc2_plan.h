@@ -34,6 +34,7 @@
  *   tdmpc2_plan_export_packed / import_packed <- TDMPC2.save / load of the planner's weights  tdmpc2/tdmpc2.py:72-95
  *   tdmpc2_plan_export_noise  <- the six RNG draw sites of one plan    tdmpc2/tdmpc2.py:176,204, tdmpc2/common/world_model.py:156,212,
  *                                (what torch.manual_seed pins there)   tdmpc2/common/math.py:90
+ *   tdmpc2_buffer_create / add / load / sample <- Buffer (torchrl slice sampler)               tdmpc2/common/buffer.py:13-115
  *
  * Conventions
  *   - plain C types only; every tensor is a DEVICE pointer to fp32 (or int32 /
@@ -667,6 +668,77 @@ int tdmpc2_plan_fault_info(tdmpc2_plan_t *h, tdmpc2_fault_info *info);
  * launches measured, and rewinds the buffer. */
 int tdmpc2_plan_set_profiling(tdmpc2_plan_t *h, int max_launches);
 int tdmpc2_plan_profile_read(tdmpc2_plan_t *h, float *rollout_ms_total, int *rollout_launches);
+
+/* Replay buffer (additions to ABI 14; the version number stays 14): the reference's Buffer (tdmpc2/common/buffer.py:13-115), a
+ * torchrl ReplayBuffer with SliceSampler(num_slices = batch_size, traj_key = 'episode', strict_length = True), restated as an
+ * episode ring on the device.  A handle of its own: it needs no planner and shares nothing with one.
+ *   Storage   `capacity` steps; per step up to 8 FIELDS (obs, action, reward, terminated, task, ...) of row_bytes opaque bytes each
+ *             (fp32 state rows, uint8 [9, 64, 64] frame stacks, an int64 task id): the library copies bytes and never interprets
+ *             them.  Device memory only, one allocation made by create; there is no host-resident storage.
+ *   Ring      a step's LOGICAL index is the count of steps written before it (64-bit); its physical row is logical % capacity.
+ *             Writing evicts the oldest logical steps; an episode that loses its front stays a shorter trajectory (as in a torchrl
+ *             storage whose cursor has passed it).
+ *   Table     S = slice_len (= horizon + 1).  An episode is ELIGIBLE while it has at least S live steps; the eligible ones are kept
+ *             as {first_logical, len} in a device-side ring of capacity / S + 1 entries, appended at the tail, shrunk or popped at
+ *             the head.  Shorter episodes occupy storage and count in num_eps but are never sampled.
+ *   Sampling  slice b of a call takes ONE Philox4x32-10 draw r, counter (b, site 8, 0, call), key = seed:
+ *             episode e = (u64(r.x) * eligible) >> 32 of the table (uniform over eligible episodes), start s = (u64(r.y) *
+ *             (len_e - S + 1)) >> 32 (uniform over the starts that fit).  This is what torchrl documents for a strict-length slice
+ *             sampler; torchrl itself was not run against it.
+ *   Outputs   time-major, as Buffer._prepare_batch returns them (buffer.py:93-110): a field that delivers steps
+ *             [step_first, step_first + step_count) of the slice writes [step_count, batch, row_bytes] bytes.
+ * The call counter and the table's head / count live on the device: a tdmpc2_buffer_sample captured in a hipGraph draws fresh
+ * slices at every replay and sees episodes added between replays.  sample is two launches (draw, grouped gather over all
+ * fields), allocates nothing and never synchronises the host.  A handle is not re-entrant. */
+typedef struct tdmpc2_buffer tdmpc2_buffer_t;
+#define TDMPC2_BUFFER_MAX_FIELDS 8
+typedef struct tdmpc2_buffer_field {
+    uint32_t row_bytes;                /* bytes per step, > 0 */
+    int32_t step_first, step_count;    /* the steps of a slice this field delivers: obs 0, S; action / reward 1, S - 1; task 0, 1 */
+} tdmpc2_buffer_field;
+typedef struct tdmpc2_buffer_cfg {
+    uint64_t capacity;                 /* steps; >= slice_len */
+    int32_t slice_len;                 /* S = horizon + 1 >= 2 */
+    int32_t device;                    /* HIP device ordinal */
+    int32_t n_fields;                  /* 1 .. 8 */
+    int32_t max_batch;                 /* slices per sample call the workspace is reserved for; 0 = 4096 */
+    tdmpc2_buffer_field field[TDMPC2_BUFFER_MAX_FIELDS];
+} tdmpc2_buffer_cfg;
+typedef struct tdmpc2_buffer_info {
+    uint64_t num_eps;                  /* episodes ever written (Buffer.num_eps, buffer.py:33-36) */
+    uint64_t live_steps;               /* min(steps ever written, capacity) */
+    uint64_t cursor;                   /* steps ever written: the next step's logical index */
+    uint32_t eligible;                 /* entries in the table */
+    uint32_t next_call;                /* the device's call counter: the `call` of the next sample */
+} tdmpc2_buffer_info;
+/* Buffer.__init__ + _init (buffer.py:13-67).  create validates, sizes and builds the host side only; like the reference's lazy
+ * storage, the device memory -- storage, table, state words and the draw workspace, ONE allocation -- is made by the first add /
+ * load (keep that call outside a hipGraph capture).  TDMPC2_ERR_INVALID (the device is never touched): NULL cfg / out,
+ * slice_len < 2, capacity < slice_len, n_fields outside [1, 8], a field with row_bytes == 0 or steps outside the slice,
+ * max_batch < 0.  A failed allocation (in add / load): TDMPC2_ERR_HIP, nothing is left allocated and the handle is unchanged
+ * (there is no host fallback, unlike buffer.py:61-63).  The host keeps a mirror of the table: 16 bytes per capacity / S. */
+int tdmpc2_buffer_create(const tdmpc2_buffer_cfg *cfg, tdmpc2_buffer_t **out);
+void tdmpc2_buffer_destroy(tdmpc2_buffer_t *b);
+/* Buffer.add (buffer.py:84-91): ONE episode of `steps` steps.  fields[f]: DEVICE pointer to [steps, row_bytes of field f].  Per
+ * field at most two copies around the physical wrap, then one tiny kernel that takes the new table / state values by value:
+ * everything is ordered by `stream`.  Host cost O(table entries touched).  TDMPC2_ERR_INVALID: NULL handle / fields / a NULL
+ * field pointer, steps < 1, an episode longer than capacity. */
+int tdmpc2_buffer_add(tdmpc2_buffer_t *b, uint32_t steps, const void *const *fields, void *stream);
+/* Buffer.load (buffer.py:69-82): n_episodes episodes of `steps` steps each, fields[f] [n_episodes, steps, row_bytes]; the state
+ * it leaves (table, samples) is that of n_episodes add calls.  The table entries are filled arithmetically in one launch; steps
+ * that the same load would evict are not copied.  Refusals as add (n_episodes < 1 too). */
+int tdmpc2_buffer_load(tdmpc2_buffer_t *b, uint64_t n_episodes, uint32_t steps, const void *const *fields, void *stream);
+/* Buffer.sample + _prepare_batch (buffer.py:93-115): `batch` slices.  outs[f]: DEVICE pointer to [step_count of f, batch,
+ * row_bytes of f], or NULL (field not wanted); index_out: DEVICE int64 [batch], the logical index of step 0 of every slice, or
+ * NULL.  Accesses are 16 bytes wide where row_bytes % 16 == 0 and outs[f] is 16-byte aligned, 4 bytes where both allow that, else
+ * single bytes.  TDMPC2_ERR_INVALID: NULL handle / outs, batch outside [1, max_batch]; TDMPC2_ERR_STATE: no eligible episode (by
+ * the host's count).  A captured replay that meets an empty table on the device reads nothing, leaves the outputs untouched and
+ * writes -1 to index_out. */
+int tdmpc2_buffer_sample(tdmpc2_buffer_t *b, int32_t batch, void *const *outs, int64_t *index_out, uint64_t seed, void *stream);
+/* Buffer.num_eps and the ring's state (buffer.py:28-36).  next_call is read from the device: the call synchronises `stream`. */
+int tdmpc2_buffer_stats(tdmpc2_buffer_t *b, tdmpc2_buffer_info *info, void *stream);
+/* The call counter of the NEXT sample (the reproducibility handle torch.manual_seed gives the reference's sampler), stream-ordered. */
+int tdmpc2_buffer_set_call_counter(tdmpc2_buffer_t *b, uint32_t next_call, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 """MI355X-native TD-MPC2 planner: drop-in `TDMPC2.act()/plan()` over hand-written HIP kernels."""
 from .config import Config, named_config, parse_cfg, planner_iterations  # noqa: F401
 
-__all__ = ["Config", "named_config", "parse_cfg", "planner_iterations", "TDMPC2", "WorldModel", "NativePlanner"]
+__all__ = ["Config", "named_config", "parse_cfg", "planner_iterations", "TDMPC2", "WorldModel", "NativePlanner", "Buffer"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require torch/HIP
@@ -14,4 +14,7 @@ def __getattr__(name):  # lazy: importing the package must not require torch/HIP
     if name == "NativePlanner":
         from .native import NativePlanner
         return NativePlanner
+    if name == "Buffer":
+        from .buffer import Buffer
+        return Buffer
     raise AttributeError(name)

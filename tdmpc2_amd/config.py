@@ -84,6 +84,10 @@ class Config:
     action_dims: Optional[List[int]] = None
     episode_lengths: Optional[List[int]] = None
     bin_size: float = 0.2
+    # replay buffer (config.yaml: steps, batch_size, buffer_size; common/buffer.py:16,18)
+    steps: int = 10_000_000
+    batch_size: int = 256
+    buffer_size: int = 1_000_000
 
     def replace(self, **kw) -> "Config":
         return dataclasses.replace(self, **kw)

@@ -13,8 +13,9 @@
 #   k_policy_loss.hip          generic unit: running scale, policy-loss tail, termination statistics
 #   k_refresh.hip              grouped weight refresh + target-Q soft update (refresh_weights / soft_update_target)
 #   k_pixel_batch.hip          pixel encoder, batch route: MFMA implicit-GEMM convolutions (encode_pix_batch)
+#   k_buffer.hip               replay buffer: episode ring, slice draws, grouped gather, and its own C ABI (tdmpc2_buffer_*)
 # Objects are cached under build/ and rebuilt when a source they include is newer (make-style), so an experiment on one
-# family recompiles one file.  TDMPC2_EXTRA_FLAGS (all units), TDMPC2_FLAGS_<unit> (one unit: main, fused, cluster, layered, policy, model, ploss, refresh, pixbatch),
+# family recompiles one file.  TDMPC2_EXTRA_FLAGS (all units), TDMPC2_FLAGS_<unit> (one unit: main, fused, cluster, layered, policy, model, ploss, refresh, pixbatch, buffer),
 # TDMPC2_ONLY_APAD=48 (experiment builds: the fused / cluster units of one padding only), TDMPC2_OUT, TDMPC2_BUILD_DIR, JOBS.
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
@@ -40,6 +41,7 @@ UNITS+=("model|k_model.hip|${TDMPC2_FLAGS_model:-}")
 UNITS+=("ploss|k_policy_loss.hip|${TDMPC2_FLAGS_ploss:-}")
 UNITS+=("refresh|k_refresh.hip|${TDMPC2_FLAGS_refresh:-}")
 UNITS+=("pixbatch|k_pixel_batch.hip|${TDMPC2_FLAGS_pixbatch:-}")
+UNITS+=("buffer|k_buffer.hip|${TDMPC2_FLAGS_buffer:-}")
 for ap in ${APADS}; do
     UNITS+=("fused${ap}|k_fused.hip|-DTU_APAD=${ap} ${TDMPC2_FLAGS_fused:-}")
     UNITS+=("cluster${ap}|k_cluster.hip|-DTU_APAD=${ap} ${TDMPC2_FLAGS_cluster:-}")

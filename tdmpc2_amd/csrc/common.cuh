@@ -263,7 +263,8 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
     }
     return c;
 }
-enum { SITE_PITRAJ = 1, SITE_SAMPLE = 2, SITE_PI = 3, SITE_QIDX = 4, SITE_GUMBEL = 5, SITE_FINAL = 6, SITE_POLICY = 7 };
+enum { SITE_PITRAJ = 1, SITE_SAMPLE = 2, SITE_PI = 3, SITE_QIDX = 4, SITE_GUMBEL = 5, SITE_FINAL = 6, SITE_POLICY = 7,
+       SITE_BUFFER = 8 };  // the replay buffer's slice draws (buffer_kernels.cuh): counter (slice, site, 0, call)
 
 __device__ __forceinline__ uint4 rng_raw(unsigned long long seed, unsigned call, int site, int iter, int env,
                                          unsigned idx) {

@@ -36,6 +36,8 @@ ABI_SYMBOLS = [
     "tdmpc2_plan_policy_loss", "tdmpc2_plan_policy_loss_mt", "tdmpc2_plan_running_scale", "tdmpc2_plan_termination_stats",
     "tdmpc2_plan_refresh_weights", "tdmpc2_plan_soft_update_target",
     "tdmpc2_plan_pix_batch_reserve", "tdmpc2_plan_encode_pix_batch",
+    "tdmpc2_buffer_create", "tdmpc2_buffer_destroy", "tdmpc2_buffer_add", "tdmpc2_buffer_load", "tdmpc2_buffer_sample",
+    "tdmpc2_buffer_stats", "tdmpc2_buffer_set_call_counter",
 ]
 
 NET_DYNAMICS, NET_REWARD, NET_PI, NET_Q, NET_TERMINATION, NET_TARGET_Q = range(6)
@@ -120,6 +122,23 @@ class PolicyOut(C.Structure):
 
 POLICY_ROUTE_AUTO, POLICY_ROUTE_ROW, POLICY_ROUTE_SPREAD = range(3)  # TDMPC2_TUNE_POLICY_ROUTE values
 TUNE_POLICY_ROUTE = 9
+
+
+BUFFER_MAX_FIELDS = 8
+
+
+class BufferField(C.Structure):  # struct tdmpc2_buffer_field
+    _fields_ = [("row_bytes", C.c_uint32), ("step_first", C.c_int32), ("step_count", C.c_int32)]
+
+
+class BufferCfg(C.Structure):  # struct tdmpc2_buffer_cfg
+    _fields_ = [("capacity", C.c_uint64), ("slice_len", C.c_int32), ("device", C.c_int32), ("n_fields", C.c_int32),
+                ("max_batch", C.c_int32), ("field", BufferField * BUFFER_MAX_FIELDS)]
+
+
+class BufferInfo(C.Structure):  # struct tdmpc2_buffer_info
+    _fields_ = [("num_eps", C.c_uint64), ("live_steps", C.c_uint64), ("cursor", C.c_uint64), ("eligible", C.c_uint32),
+                ("next_call", C.c_uint32)]
 
 
 class Debug(C.Structure):
@@ -268,6 +287,20 @@ def _open(path):
     lib.tdmpc2_plan_set_profiling.restype = i32
     lib.tdmpc2_plan_profile_read.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
     lib.tdmpc2_plan_profile_read.restype = i32
+    lib.tdmpc2_buffer_create.argtypes = [C.POINTER(BufferCfg), C.POINTER(vp)]
+    lib.tdmpc2_buffer_create.restype = i32
+    lib.tdmpc2_buffer_destroy.argtypes = [vp]
+    lib.tdmpc2_buffer_destroy.restype = None
+    lib.tdmpc2_buffer_add.argtypes = [vp, C.c_uint32, C.POINTER(vp), vp]
+    lib.tdmpc2_buffer_add.restype = i32
+    lib.tdmpc2_buffer_load.argtypes = [vp, u64, C.c_uint32, C.POINTER(vp), vp]
+    lib.tdmpc2_buffer_load.restype = i32
+    lib.tdmpc2_buffer_sample.argtypes = [vp, C.c_int32, C.POINTER(vp), vp, u64, vp]
+    lib.tdmpc2_buffer_sample.restype = i32
+    lib.tdmpc2_buffer_stats.argtypes = [vp, C.POINTER(BufferInfo), vp]
+    lib.tdmpc2_buffer_stats.restype = i32
+    lib.tdmpc2_buffer_set_call_counter.argtypes = [vp, C.c_uint32, vp]
+    lib.tdmpc2_buffer_set_call_counter.restype = i32
     if lib.tdmpc2_plan_abi_version() != ABI_VERSION:
         raise NativeError(f"ABI version mismatch: library {lib.tdmpc2_plan_abi_version()}, binding {ABI_VERSION}")
     return lib
@@ -1220,3 +1253,124 @@ class NativePlanner:
         ms, n = C.c_float(), C.c_int()
         self._check(self.lib.tdmpc2_plan_profile_read(self._h, C.byref(ms), C.byref(n)))
         return float(ms.value), int(n.value)
+
+
+def buffer_cfg(capacity: int, slice_len: int, fields, device_index: int = 0, max_batch: int = 0) -> BufferCfg:
+    """struct tdmpc2_buffer_cfg; fields: (row_bytes, step_first, step_count) per field."""
+    c = BufferCfg(capacity=int(capacity), slice_len=int(slice_len), device=int(device_index), n_fields=len(fields),
+                  max_batch=int(max_batch))
+    for i, (rb, s0, sc) in enumerate(fields[:BUFFER_MAX_FIELDS]):
+        c.field[i] = BufferField(int(rb), int(s0), int(sc))
+    return c
+
+
+class NativeBuffer:
+    """Owns one `tdmpc2_buffer_t`: an episode ring of opaque byte rows on one GPU with the reference Buffer's slice sampling
+    (tdmpc2/common/buffer.py:13-115).  fields: (row_bytes, step_first, step_count) per field; tensors passed to add / load are
+    [T, ...] / [N, T, ...] with row_bytes bytes per step, outputs of sample are [step_count, batch, row_bytes] bytes."""
+
+    def __init__(self, capacity: int, slice_len: int, fields, device: torch.device, max_batch: int = 0):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise NativeError(f"the replay buffer keeps its storage on an MI355X only (device {device}); there is no host storage")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.lib = load_library()
+        self.device = device
+        self.fields = [tuple(int(v) for v in f) for f in fields]
+        self.capacity, self.slice_len = int(capacity), int(slice_len)
+        h = C.c_void_p()
+        self._h = C.c_void_p()
+        self._check(self.lib.tdmpc2_buffer_create(C.byref(buffer_cfg(capacity, slice_len, self.fields, device.index, max_batch)),
+                                                  C.byref(h)))
+        self._h = h
+
+    def _check(self, rc: int):
+        if rc != 0:
+            raise NativeError(f"tdmpc2_buffer error {rc}: {self.lib.tdmpc2_last_error().decode()}")
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.lib.tdmpc2_buffer_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _rows(self, tensors, lead):
+        if len(tensors) != len(self.fields):
+            raise ValueError(f"expected {len(self.fields)} field tensors, got {len(tensors)}")
+        n = 1
+        for d in lead:
+            n *= int(d)
+        ptrs = (C.c_void_p * len(self.fields))()
+        keep = []
+        for i, (t, (rb, _, _)) in enumerate(zip(tensors, self.fields)):
+            if t.device != self.device:
+                raise ValueError(f"field {i}: expected device {self.device}, got {t.device}")
+            if tuple(t.shape[:len(lead)]) != tuple(lead) or t.numel() * t.element_size() != n * rb:
+                raise ValueError(f"field {i}: expected {tuple(lead)} steps of {rb} bytes, got {tuple(t.shape)} {t.dtype}")
+            t = t.contiguous()
+            keep.append(t)
+            ptrs[i] = t.data_ptr()
+        return ptrs, keep
+
+    def add(self, tensors):
+        """One episode: tensors[f] is [T, ...]."""
+        T = int(tensors[0].shape[0])
+        ptrs, keep = self._rows(tensors, (T,))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.tdmpc2_buffer_add(self._h, T, ptrs, self._stream()))
+        for t in keep:  # the copies are stream-ordered: the caching allocator must not hand the sources out before they ran
+            t.record_stream(torch.cuda.current_stream(self.device))
+
+    def load(self, tensors):
+        """N episodes of equal length: tensors[f] is [N, T, ...]."""
+        N, T = int(tensors[0].shape[0]), int(tensors[0].shape[1])
+        ptrs, keep = self._rows(tensors, (N, T))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.tdmpc2_buffer_load(self._h, N, T, ptrs, self._stream()))
+        for t in keep:
+            t.record_stream(torch.cuda.current_stream(self.device))
+
+    def sample(self, outs, seed: int = 0, index_out: Optional[torch.Tensor] = None):
+        """outs[f]: a contiguous tensor of step_count x batch x row_bytes bytes on the device, or None (field not wanted)."""
+        batch = None
+        ptrs = (C.c_void_p * len(self.fields))()
+        for i, (t, (rb, _, sc)) in enumerate(zip(outs, self.fields)):
+            if t is None:
+                continue
+            if t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"output {i}: must be contiguous on {self.device}")
+            nb = t.numel() * t.element_size()
+            if nb % (rb * sc):
+                raise ValueError(f"output {i}: {nb} bytes is not [{sc}, batch, {rb} bytes]")
+            if batch is None:
+                batch = nb // (rb * sc)
+            if nb != batch * rb * sc:
+                raise ValueError(f"output {i}: expected [{sc}, {batch}, {rb} bytes], got {tuple(t.shape)} {t.dtype}")
+            ptrs[i] = t.data_ptr()
+        if index_out is not None:
+            _chk_tensor("index_out", index_out, torch.int64, (index_out.shape[0],), self.device)
+            batch = int(index_out.shape[0]) if batch is None else batch
+            if int(index_out.shape[0]) != batch:
+                raise ValueError(f"index_out: expected [{batch}], got {tuple(index_out.shape)}")
+        with torch.cuda.device(self.device):
+            self._check(self.lib.tdmpc2_buffer_sample(self._h, int(batch or 0), ptrs, _ptr(index_out), int(seed) & (2 ** 64 - 1),
+                                                      self._stream()))
+
+    def stats(self) -> dict:
+        info = BufferInfo()
+        with torch.cuda.device(self.device):
+            self._check(self.lib.tdmpc2_buffer_stats(self._h, C.byref(info), self._stream()))
+        return {k: int(getattr(info, k)) for k, _ in BufferInfo._fields_}
+
+    def set_call_counter(self, value: int):
+        with torch.cuda.device(self.device):
+            self._check(self.lib.tdmpc2_buffer_set_call_counter(self._h, int(value) & 0xFFFFFFFF, self._stream()))

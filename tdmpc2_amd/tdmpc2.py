@@ -539,3 +539,11 @@ class TDMPC2(torch.nn.Module):
             info[k] = pl[k]
         info["pi_scale"] = pl["pi_scale"].mean()
         return info
+
+    @torch.no_grad()
+    def update_info_sampled(self, buffer, pi_eps=None, qidx=None):
+        """`update_info` on a batch drawn from `buffer` (a tdmpc2_amd.Buffer): what the forward of `TDMPC2.update(buffer)` does with
+        `buffer.sample()` (reference tdmpc2.py:334-346).  The batch comes out of the library's replay buffer time-major and on
+        this device, so nothing runs between the gather and the first encoder launch."""
+        obs, action, reward, terminated, task = buffer.sample()
+        return self.update_info(obs, action, reward, terminated, task, pi_eps=pi_eps, qidx=qidx)
