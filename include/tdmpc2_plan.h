@@ -183,7 +183,10 @@ int tdmpc2_plan_precision(const tdmpc2_plan_t *h);
  * ("_Qs.params.<layer>.<name>", tdmpc2/common/layers.py:167-199).  The first
  * layer's input columns are ordered [z | task_emb | action]
  * (world_model.py:118-120).  The library re-packs into its own MFMA fragment
- * layout; the source buffers may be freed after the stream reaches this call. */
+ * layout; the source buffers may be freed after the stream reaches this call.
+ * One job (this layer, every ensemble member) for the packer that
+ * tdmpc2_plan_refresh_weights runs over a whole table: the same kernels, at
+ * most 4 launches (csrc/refresh_route.h). */
 int tdmpc2_plan_bind_weights(tdmpc2_plan_t *h, int net, int layer, const float *W, const float *b,
                              const float *ln_g, const float *ln_b, int out_features, int in_features,
                              void *stream);
@@ -468,7 +471,7 @@ int tdmpc2_plan_termination_stats(tdmpc2_plan_t *h, int n, const float *term_log
 
 /* Weight refresh (ABI 14): the whole model re-packed from the trainer's own parameter tensors in a constant, small number of
  * launches -- what a training loop needs after every optimiser step (TDMPC2._update, tdmpc2/tdmpc2.py:259-316, changes every
- * parameter; the per-layer binds above cost about ten small launches per ensemble member and layer).
+ * parameter; the per-layer binds above run the same packer but cost up to four launches per layer and call).
  *
  * tdmpc2_weight_table: device pointers, fp32, in the checkpoint's layout -- per net and layer exactly the W, b, ln_g, ln_b that
  * tdmpc2_plan_bind_weights takes (the Q nets stacked over num_q; ln_g / ln_b NULL where the layer has no LayerNorm), and the
@@ -487,7 +490,7 @@ typedef struct tdmpc2_weight_table {
     int32_t enc_out[6], enc_in[6];   /* nn.Linear out_features / in_features of the encoder's layers */
 } tdmpc2_weight_table;
 /* Produces, for every net the table names, exactly what the sequence of tdmpc2_plan_bind_weights / tdmpc2_plan_bind_encoder
- * calls produces (tdmpc2_plan_export_packed is byte-identical): operand slabs, per-layer scale records, padded biases,
+ * calls produces (the same kernels over a larger job table; tdmpc2_plan_export_packed is byte-identical): operand slabs, per-layer scale records, padded biases,
  * LayerNorm vectors, task-embedding columns, the transposed encoder; if the policy prior's fp32 copy is bound
  * (tdmpc2_plan_bind_policy) and TDMPC2_NET_PI is named, that copy as well.  Both kernel families, both arithmetics.  At most 4
  * launches on a SPLIT_F16 handle (reset of the maxima, scan, scales, pack of everything), 1 on an FP32 handle, whatever num_q

@@ -2,7 +2,7 @@
 # Build the planner's C-ABI shared library for gfx950 (cross-compiles without a GPU).
 # One translation unit per kernel family (and, for the fused 512-wide family, per action padding), compiled in parallel and
 # linked into ONE libtdmpc2_plan.so:
-#   tdmpc2_plan.hip            C ABI, handle (its sizes: plan_layout.h), bind / pack kernels, refit, encoder, host side of the fused family
+#   tdmpc2_plan.hip            C ABI, handle (its sizes: plan_layout.h), job tables of the weight packer, refit, encoder, host side of the fused family
 #   k_fused.hip   x {16,32,48,64}   ks_setup / ks_pitraj / ks_rollout / ks_value
 #   k_cluster.hip x {16,32,48,64}   ks_rollout_cl
 #   k_layered.hip              layered GEMMs + row kernels + their host orchestration
@@ -11,7 +11,7 @@
 #   k_model.hip                generic unit (no TU_APAD): the loss row kernels of both families
 #   k_policy_loss.hip x {16,32,48,64}   ks_value_ent (update_pi's forward per row, fused family)
 #   k_policy_loss.hip          generic unit: running scale, policy-loss tail, termination statistics
-#   k_refresh.hip              grouped weight refresh + target-Q soft update (refresh_weights / soft_update_target)
+#   k_refresh.hip              the weight packer (every bind, refresh_weights) + target-Q soft update
 #   k_pixel_batch.hip          pixel encoder, batch route: MFMA implicit-GEMM convolutions (encode_pix_batch)
 #   k_buffer.hip               replay buffer: episode ring, slice draws, grouped gather, and its own C ABI (tdmpc2_buffer_*)
 # Objects are cached under build/ and rebuilt when a source they include is newer (make-style), so an experiment on one

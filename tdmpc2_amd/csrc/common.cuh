@@ -35,7 +35,7 @@ constexpr int RW_THREADS = 256;   // row kernels: 4 rows (wavefronts) per workgr
 
 
 // Scale of bounded operands (SimNorm latents in [0, 1], actions in [-1, 1]) and the LARGEST scale of a hidden activation.
-// A hidden layer's own scale is chosen at bind time from its LayerNorm affine parameters (k_ascale: the largest power
+// A hidden layer's own scale is chosen at bind time from its LayerNorm affine parameters (k_rf_scales: the largest power
 // of two <= 2^5 that keeps |Mish(LayerNorm(.))| * scale below the f16 maximum for ANY input), so that a checkpoint with a
 // huge LayerNorm gain cannot overflow the hi piece into Inf -> NaN -> nan_to_num(0).  The consuming layer's output
 // scale (LayerS::oscale) carries the matching 2^-(kw + log2 scale_in).
@@ -676,7 +676,7 @@ struct TaskBiasParams {
 struct LayerScal {
     float wscale;          // 2^kw: applied to the weights when they are packed
     float oscale;          // 2^-(kw + log2 of the INPUT's operand scale): applied to the fp32 accumulator
-    unsigned int maxbits;  // max |W| as bits (k_absmax)
+    unsigned int maxbits;  // max over the finite |W| as bits (k_rf_scan)
     int kw;
     float ascale;          // 2^ka: operand scale of this layer's OUTPUT (hidden layers; <= ACT_SCALE)
     int ka;

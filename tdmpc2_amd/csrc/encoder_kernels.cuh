@@ -204,12 +204,3 @@ __global__ __launch_bounds__(ENC_THREADS) void k_enc_norm(EncNormParams p) {
         }
     }
 }
-
-// nn.Linear weight [out][in] -> [in][out]
-__global__ void k_transpose(const float *__restrict__ w, float *__restrict__ wt, int out, int in) {
-    const size_t n = (size_t)out * in;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int k = (int)(i / out), f = (int)(i % out);
-        wt[i] = w[(size_t)f * in + k];
-    }
-}

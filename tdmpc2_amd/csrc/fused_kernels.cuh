@@ -9,7 +9,7 @@
 // runs at up to 16/3 of the exact-fp32 kernels' roof while the error against an fp64 evaluation of the same network
 // stays in the fp32 round-off class (measured: tests/test_gpu_planner.py::test_error_attribution_against_fp64; CPU emulation: oracle/split_probe.py).
 // Operands are pre-scaled by powers of two so that the lo pieces stay in the f16 normal range: activations by 2^5,
-// each weight matrix by 2^kw with max|W| 2^kw in [2^13, 2^14) (k_wscale); the fp32 accumulator is multiplied back by
+// each weight matrix by 2^kw with max|W| 2^kw in [2^13, 2^14) (k_rf_scales); the fp32 accumulator is multiplied back by
 // the exact 2^-(kw+5) in the epilogue.
 //
 // Structure (reference: TDMPC2._plan / _estimate_value, tdmpc2/tdmpc2.py:122-206; WorldModel.next / reward / pi / Q,

@@ -1,5 +1,6 @@
-// Translation unit of the grouped weight refresh (tdmpc2_plan_refresh_weights / tdmpc2_plan_soft_update_target): the kernels of
-// refresh_kernels.cuh behind refresh_launch of launch.h.  The host side (table checks, job table, the C ABI) is in tdmpc2_plan.hip.
+// Translation unit of the weight packer (tdmpc2_plan_bind_weights / bind_encoder / bind_policy / refresh_weights /
+// soft_update_target): the kernels of refresh_kernels.cuh behind refresh_launch of launch.h.  The host side (job checks, job
+// table, the C ABI) is in tdmpc2_plan.hip.
 #include "launch.h"
 
 namespace {

@@ -137,7 +137,7 @@ int pl_launch_scale(const RunningScaleParams &p, hipStream_t st);
 int pl_launch_tail(const PolicyLossTailParams &p, hipStream_t st);
 int pl_launch_term_stats(const TerminationStatsParams &p, hipStream_t st);
 
-// ---- grouped weight refresh (k_refresh.hip: refresh_kernels.cuh, launch list in refresh_route.h)
+// ---- the weight packer: binds, grouped refresh, soft update (k_refresh.hip: refresh_kernels.cuh, launch list in refresh_route.h)
 #include "refresh_params.h"
 int refresh_launch(int op /* RO_* */, const RfParams &p, hipStream_t st);
 

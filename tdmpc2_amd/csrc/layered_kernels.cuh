@@ -44,7 +44,7 @@ struct GemmParams {
     const float *A;     // [Rp, lda] fp32 row-major, Rp a multiple of GBM
     int lda;
     int K;              // contraction length, multiple of GBK (weights zero-padded)
-    const float *wp;    // packed [CT][K/8][64][4] (k_pack_weight), + sel * w_sel_stride for ensembles
+    const float *wp;    // packed [CT][K/8][64][4] (rf_pack_tile, refresh_kernels.cuh), + sel * w_sel_stride for ensembles
     long w_sel_stride;
     int CT;             // output column tiles of 32
     int ncolblk;        // ceil(CT / 4)

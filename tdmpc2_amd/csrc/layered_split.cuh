@@ -25,7 +25,7 @@ struct GemmSParams {
     int KBa, a_kb0;     // blocks per row of A; the first block contracted (a k-range: the action columns of X)
     int K;              // contraction length, multiple of GBK
     int kb0, kbs;       // a k-range of the packed matrix: first k16-block and blocks per column tile (0: K / 16 = the whole matrix)
-    const _Float16 *wp; // split-packed [CT][K/16][2][64][8] (k_pack_split), + sel * w_sel_stride (in halfs)
+    const _Float16 *wp; // split-packed [CT][K/16][2][64][8] (rf_pack_tile, refresh_kernels.cuh), + sel * w_sel_stride (in halfs)
     long w_sel_stride;
     const float *oscale; // device scalar(s): 2^-(kw + 5), + sel * osc_sel_stride
     long osc_sel_stride;
@@ -486,7 +486,7 @@ __global__ __launch_bounds__(RW_THREADS) void l_ln_act_s(LnActParams p) {
     }
     const float var = group_sum<64>(ss) / (float)p.width;
     const float rstd = 1.0f / sqrtf(var + LN_EPS);
-    // operand scale of this layer's output: chosen at bind time for Mish layers (k_ascale), fixed for SimNorm outputs
+    // operand scale of this layer's output: chosen at bind time for Mish layers (k_rf_scales), fixed for SimNorm outputs
     const float oscl = ACT == 0 ? p.ascale[(size_t)sel * p.asc_sel_stride] : ACT_SCALE;
 #pragma unroll
     for (int q = 0; q < 16; ++q) {

@@ -1,9 +1,11 @@
-// Grouped weight refresh (tdmpc2_plan_refresh_weights / tdmpc2_plan_soft_update_target): what the per-(net, layer, head)
-// launches of tdmpc2_plan_bind_weights / bind_encoder / bind_policy produce, in at most four launches over a job table
-// (RfParams, refresh_params.h; the launch list is refresh_route.h).  Every stored byte is the one the bind kernels of
-// bind_kernels.cuh / tdmpc2_plan.hip store: the same expressions on the same inputs, spread differently over threads.
-// Included by k_refresh.hip inside its anonymous namespace.  No inline assembly, no waits between workgroups; the only atomic
-// is the integer atomicMax on the bits of a non-negative float (order independent), as in k_absmax.
+// The weight packer: caller's fp32 tensors -> the handle's packed storage, in at most four launches over a job table (RfParams,
+// refresh_params.h; the launch list is refresh_route.h).  Every entry point that stores weights runs these kernels and no
+// others: tdmpc2_plan_refresh_weights / tdmpc2_plan_soft_update_target with a table of jobs, tdmpc2_plan_bind_weights /
+// bind_encoder / bind_policy with one job (one layer, every ensemble member).  This file is therefore the definition of the
+// scale rule, the source-column map, the fragment layouts and the transposed copies; tests/golden/packed_digests.json pins
+// the bytes.  Included by k_refresh.hip inside its anonymous namespace.  No inline assembly, no waits between workgroups; the
+// only atomic is the integer atomicMax on the bits of a non-negative float (order preserving on the uint pattern, order
+// independent).
 #pragma once
 
 typedef _Float16 rf_half8 __attribute__((ext_vector_type(8)));
@@ -20,7 +22,7 @@ __global__ __launch_bounds__(RF_THREADS) void k_rf_reset(RfParams p) {
     for (int item = threadIdx.x; item < RF_NETS * MAXQ * 3; item += RF_THREADS) {
         const int net = item / (MAXQ * 3), hd = (item / 3) % MAXQ, l = item % 3;
         const RfNet &N = p.net[net];
-        if (!N.on || !N.scal || hd >= N.heads) continue;
+        if (!(N.mask >> l & 1) || !N.scal || hd >= N.heads) continue;
         LayerScal *s = N.scal + hd * 3 + l;
         s->maxbits = 0u;
         if (N.l[l].has_ln) {
@@ -36,6 +38,7 @@ __device__ __forceinline__ float rf_lerp(float t, float o, float w) {
     const float d = o - t;
     return w < 0.5f ? t + w * d : o - d * (1.f - w);
 }
+// max over the FINITE |v|: NaN and Inf entries do not take part in a scale
 __device__ __forceinline__ float rf_absmax(float m, float v) {
     const float a = fabsf(v);
     return (a == a && a < INFINITY) ? fmaxf(m, a) : m;
@@ -84,44 +87,47 @@ __global__ __launch_bounds__(RF_THREADS) void k_rf_scan(RfParams p) {
     }
 }
 
-// ---------------------------------------------------------------- RO_SCALES: k_wscale, k_ascale, k_net_scales per (net, head)
+// ---------------------------------------------------------------- RO_SCALES
+// One thread per (net, head).  Named layers get their exponents from the maxima of RO_SCAN:
+//   kw such that max|W| 2^kw in [2^13, 2^14); wscale = 2^kw multiplies the matrix before its hi / lo split.
+//   ka, the output scale of a LayerNorm + Mish layer of `width` features: |LayerNorm(x)_i| <= sqrt(width - 1) for any x, so
+//   |Mish(g x + b)| <= sqrt(width - 1) max|g| + max|b| =: B.  ka = the largest exponent <= 5 with B 2^ka < 2^15 (half of the
+//   f16 maximum: rounding of the hi piece cannot reach Inf).  Trained checkpoints (g ~ 1) keep ka = 5.
+// Then oscale of ALL three layers from the stored kw / ka, so that a job naming one layer leaves its neighbours' exponents
+// alone and still corrects the next layer's oscale: layer 0 reads [z | a] (scale 2^5), layer l > 0 reads layer l - 1's output.
 __global__ __launch_bounds__(RF_THREADS) void k_rf_scales(RfParams p) {
     for (int item = threadIdx.x; item < RF_NETS * MAXQ; item += RF_THREADS) {
         const int net = item / MAXQ, hd = item % MAXQ;
         const RfNet &N = p.net[net];
-        if (!N.on || !N.scal || hd >= N.heads) continue;
+        if (!N.mask || !N.scal || hd >= N.heads) continue;
         LayerScal *s3 = N.scal + hd * 3;
-        int kws[3], kas[3];
         for (int l = 0; l < 3; ++l) {
+            if (!(N.mask >> l & 1)) continue;
             LayerScal *s = s3 + l;
-            // kw such that max|W| 2^kw in [2^13, 2^14)
             const float m = __uint_as_float(s->maxbits);
             int ex = 0;
-            if (m > 0.f) frexpf(m, &ex);
+            if (m > 0.f) frexpf(m, &ex);  // m = f 2^ex, f in [0.5, 1)
             int kw = 14 - ex;
             kw = kw > 40 ? 40 : (kw < -40 ? -40 : kw);
             s->kw = kw;
             s->wscale = ldexpf(1.f, kw);
-            // ka: the largest exponent <= 5 with (sqrt(width - 1) max|g| + max|b|) 2^ka < 2^15 (LayerNorm + Mish layers)
             int ka = ACT_SCALE_LOG2;
             if (N.l[l].has_ln && N.l[l].mish) {
                 const int width = N.l[l].out;
                 const float bound = sqrtf((float)(width > 1 ? width - 1 : 1)) * __uint_as_float(s->gmax) + __uint_as_float(s->bmax);
                 if (bound > 0.f) {
                     int eb = 0;
-                    frexpf(bound, &eb);
+                    frexpf(bound, &eb);  // bound < 2^eb
                     ka = 15 - eb < ka ? 15 - eb : ka;
                 }
                 ka = ka < -24 ? -24 : ka;
             }
             s->ka = ka;
             s->ascale = ldexpf(1.f, ka);
-            kws[l] = kw;
-            kas[l] = ka;
         }
         for (int l = 0; l < 3; ++l) {
-            const int kin = l == 0 ? ACT_SCALE_LOG2 : kas[l - 1];
-            s3[l].oscale = ldexpf(1.f, -(kws[l] + kin));
+            const int kin = l == 0 ? ACT_SCALE_LOG2 : s3[l - 1].ka;
+            s3[l].oscale = ldexpf(1.f, -(s3[l].kw + kin));
         }
     }
 }
@@ -130,7 +136,11 @@ __global__ __launch_bounds__(RF_THREADS) void k_rf_scales(RfParams p) {
 constexpr int RF_LDT = RF_TILE_K + 1;  // LDS row stride of the 32 x RF_TILE_K tile (odd: the fragment reads walk rows conflict-free)
 
 // 32 rows x RF_TILE_K packed columns of one matrix: source rows read coalesced into LDS (scaled for the split arithmetic), then
-// written in MFMA fragment order, 16 bytes per (k block, lane) and plane.  Layouts: k_pack_split / k_pack_weight.
+// written in MFMA fragment order, 16 bytes per (k block, lane) and plane:
+//   split  dst[ct][kb][plane][lane][e] = W[row = ct*32 + (lane & 31)][k = kb*16 + 8 (lane >> 5) + e] * wscale, hi / lo f16 planes
+//   fp32   dst[ct][kb][lane][r]        = W[row = ct*32 + (lane & 31)][k = kb*8 + 4 (lane >> 5) + r]
+// The packed k axis is [z columns (nz) | action columns (na, zero padded)], the source columns are [z (nz) | task_emb (nt) |
+// action (na)] (tdmpc2/common/world_model.py:118-120); rows beyond `out` are zero.
 __device__ __forceinline__ void rf_pack_tile(const RfLayer &L, const float *W, char *dst, int ct, int kc, int split, float sc, float *tile) {
     const int tid = threadIdx.x;
     const int kp = L.KB * (split ? 16 : 8);
@@ -181,7 +191,7 @@ __device__ __forceinline__ void rf_pack_tile(const RfLayer &L, const float *W, c
     }
 }
 
-// nn.Linear [out][in] -> [in][out], one 32 x 32 tile (k_transpose's result), + the vectors by the first workgroup
+// nn.Linear [out][in] -> [in][out], one 32 x 32 tile, + the vectors by the first workgroup
 __device__ __forceinline__ void rf_transpose_tile(const RfTrans &T, int local, float *tile) {
     const int tid = threadIdx.x;
     const int tiles_k = (T.in + 31) / 32;
@@ -237,7 +247,7 @@ __global__ __launch_bounds__(RF_THREADS) void k_rf_pack(RfParams p) {
                 L.bd[hd * gsz + i] = L.beta[(size_t)hd * L.out + i];
             }
         }
-    } else {  // task-embedding columns of 32 rows: wemb[row][c] = W[row][nz + c] (k_copy_cols)
+    } else {  // task-embedding columns of 32 rows: wemb[row][c] = W[row][nz + c]
         const int ct = r - n_w - 1;
         float *e = L.wemb + (size_t)hd * L.out * L.nt;
         for (int i = tid; i < 32 * L.nt; i += RF_THREADS) {

@@ -1,4 +1,4 @@
-// Kernel arguments of the grouped weight refresh (refresh_kernels.cuh; routes in refresh_route.h).  Included by launch.h inside
+// Kernel arguments of the weight packer (refresh_kernels.cuh; routes in refresh_route.h).  Included by launch.h inside
 // namespace tdk.  ONE record, passed by value to every launch of a call: the caller's pointers reach the kernels as kernel
 // arguments (no host-to-device copy is enqueued; a captured call replays on the same tensors).
 #pragma once
@@ -16,7 +16,7 @@ struct RfLayer {
 struct RfNet {
     RfLayer l[3];
     LayerScal *scal;  // [heads][3] (split) or null
-    int heads, on;
+    int heads, mask;  // bit l: layer l is named (0: the net is left as it is).  Absent layers are empty workgroup ranges
 };
 // nn.Linear [out][in] -> [in][out] plus its vectors (state encoder, policy prior's fp32 copy)
 struct RfTrans {

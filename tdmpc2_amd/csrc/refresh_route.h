@@ -1,13 +1,14 @@
-// Which operations a tdmpc2_plan_refresh_weights / tdmpc2_plan_soft_update_target call enqueues, as a pure function of what the
-// table names and of the handle's arithmetic.  Compilable on the host, no HIP types: tests/test_refresh_route.py builds it with
-// the host compiler.  The host side (tdmpc2_plan.hip) walks the list; the kernels are in refresh_kernels.cuh.
+// Which operations a call that stores weights enqueues (tdmpc2_plan_refresh_weights / soft_update_target with a table,
+// tdmpc2_plan_bind_weights / bind_encoder / bind_policy with one layer), as a pure function of what the jobs name and of the
+// handle's arithmetic.  Compilable on the host, no HIP types: tests/test_refresh_route.py builds it with the host compiler.
+// The host side (tdmpc2_plan.hip) walks the list; the kernels are in refresh_kernels.cuh.
 //
-// A refresh is at most REFRESH_MAX_OPS = 4 launches, whatever the model: every launch is GROUPED over a job table (one job per
+// A call is at most REFRESH_MAX_OPS = 4 launches, whatever the model: every launch is GROUPED over a job table (one job per
 // (net, layer), all ensemble members inside it), so the count depends on neither num_q nor the number of nets or layers.
 //   RO_RESET   max|W| / max|g| / max|b| words of every named net back to zero                      (split arithmetic)
 //   RO_SCAN    max over the finite |W|, |ln_g|, |ln_b| of every matrix (integer atomicMax on the float bits: order independent);
 //              a soft update lerps the target tensors in place in this launch and scans what it wrote   (split, or any lerp)
-//   RO_SCALES  kw / wscale / ka / ascale / oscale of every (net, head), the arithmetic of k_wscale, k_ascale, k_net_scales   (split)
+//   RO_SCALES  kw / wscale / ka / ascale of the named layers, oscale of every layer of their (net, head): k_rf_scales        (split)
 //   RO_PACK    operand slabs, padded biases, LayerNorm vectors, task-embedding columns, the transposed encoder and the policy
 //              prior's fp32 copy
 // The dependency max -> scale -> pack crosses launch boundaries: no workgroup waits for another, no float atomics.
@@ -27,11 +28,12 @@ enum { RF_SCAN_MAX_BLOCKS = 512 };  // ... up to this many per matrix, then the 
 
 struct RefreshIn {
     int split;          // 1: f16x2 split arithmetic (scales exist), 0: exact fp32
-    unsigned nets;      // bit n: TDMPC2_NET_n is named by the table (all three layers)
+    unsigned nets;      // bit n: TDMPC2_NET_n is named (a table names all three layers, a per-layer bind one)
     int enc_layers;     // state-encoder layers named (0: none)
     int policy_copy;    // 1: the policy prior's fp32 copy is bound and TDMPC2_NET_PI is named
     int lerp;           // 1: soft update (the named net is the target ensemble, lerped in place first)
     int num_q, episodic;  // part of the input on purpose: the answer must not depend on them
+    int policy_alone;   // 1: a layer of the policy prior's fp32 copy on its own, whatever `nets` says (tdmpc2_plan_bind_policy)
 };
 struct RefreshRoute {
     int nops;
@@ -45,8 +47,8 @@ inline RefreshRoute refresh_route(const RefreshIn &in) {
     const unsigned nets = in.nets & ((1u << RF_NETS) - 1u);
     r.nets = nets;
     r.enc_layers = in.enc_layers > 0 ? in.enc_layers : 0;
-    r.policy_copy = (in.policy_copy && (nets & (1u << 2))) ? 1 : 0;
-    if (!nets && !r.enc_layers) return r;  // an empty table: nothing to do
+    r.policy_copy = ((in.policy_copy && (nets & (1u << 2))) || in.policy_alone) ? 1 : 0;
+    if (!nets && !r.enc_layers && !in.policy_alone) return r;  // an empty table: nothing to do
     if (in.split && nets) {
         r.op[r.nops++] = RO_RESET;
         r.op[r.nops++] = RO_SCAN;

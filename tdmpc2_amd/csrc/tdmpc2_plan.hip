@@ -7,7 +7,7 @@
 //   NormedLinear / SimNorm                 tdmpc2/common/layers.py:74-118
 //   two_hot_inv / symexp / log_std / gumbel_softmax_sample   tdmpc2/common/math.py
 //
-// This file: the C ABI, the handle, weight packing, the elite-refit kernel shared by every path, and the host side of
+// This file: the C ABI, the handle, the weight packer's job tables, the elite-refit kernel shared by every path, and the host side of
 // the fused family.  Kernels:
 //   fused_kernels.cuh    fused 512-wide family (ks_setup / ks_pitraj / ks_rollout): one persistent workgroup keeps 32 or
 //                        64 sample rows of one plan in LDS for a whole CEM iteration; templated on the arithmetic
@@ -19,8 +19,8 @@
 //                        layer-at-a-time family for every other model size and for episodic planning
 //   encoder_kernels.cuh  WorldModel.encode for state observations (world_model.py:103-112)
 // The policy prior's kernels (WorldModel.pi, act() with mpc = False) are in k_policy.hip; its host side is here.
-// Weights are re-packed once (bind) into MFMA fragment order so that a wave's global_load_dwordx4 reads 1 KiB
-// contiguous; one small workgroup per plan does nan_to_num + top-k + score + mean/std refit (+ the final Gumbel pick)
+// Weights are re-packed (bind / refresh: refresh_kernels.cuh) into MFMA fragment order so that a wave's global_load_dwordx4
+// reads 1 KiB contiguous; one small workgroup per plan does nan_to_num + top-k + score + mean/std refit (+ the final Gumbel pick)
 // between rollout launches (k_refit below).  DESIGN.md has the full account.
 #include <cstdarg>
 #include <cstring>
@@ -45,42 +45,20 @@ int tdk::launch_refit(const RefitParams &fp, int E, int N, size_t lds, hipStream
 }
 namespace {
 
-// ================================================================ weight packing kernels
-// dst[ct][kb][lane][r] = W[row = ct*32 + (lane&31)][k = kb*8 + 4*(lane>>5) + r]; the packed k axis is
-// [z columns (nz) | action columns (na, zero padded to a multiple of 8)], source columns are
-// [z (nz) | task_emb (nt) | action (na)] (tdmpc2/common/world_model.py:118-120).
-__global__ void k_pack_weight(const float *W, int out, int in, int nz, int nt, int na, int CT, int KB, float *dst) {
-    const size_t total = (size_t)CT * KB * 256;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        const int r = idx & 3, lane = (idx >> 2) & 63;
-        const size_t blk = idx >> 8;
-        const int kb = blk % KB, ct = blk / KB;
-        const int row = ct * 32 + (lane & 31);
-        const int k = kb * 8 + 4 * (lane >> 5) + r;
-        float v = 0.f;
-        if (row < out) {
-            int src = -1;
-            if (k < nz) src = k;
-            else if (k - nz < na) src = nz + nt + (k - nz);
-            if (src >= 0 && src < in) v = W[(size_t)row * in + src];
-        }
-        dst[idx] = v;
+// beff_tab[task][net][WIDTH] = b + W[:, L:L+T] . task_emb[task] for the policy and the Q heads (online or target):
+// the per-task effective first-layer biases ks_value indexes per row.  grid = n_tasks, block = WIDTH threads.
+__global__ void ks_task_bias(TaskBiasParams p) {
+    const int task = blockIdx.x, f = threadIdx.x;
+    const float *emb = p.task_emb + (size_t)task * p.T;
+    for (int net = 0; net < p.nnets; ++net) {
+        if (!p.wemb[net]) continue;
+        const float *w = p.wemb[net] + (size_t)f * p.T;
+        float sacc = 0.f;
+        for (int k = 0; k < p.T; ++k) sacc = fmaf(w[k], emb[k], sacc);
+        p.beff_tab[((size_t)task * p.nnets + net) * WIDTH + f] = p.bias[net][f] + sacc;
     }
-}
-__global__ void k_copy_cols(const float *W, int out, int in, int col0, int ncols, float *dst) {
-    const size_t total = (size_t)out * ncols;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        const int c = idx % ncols;
-        const size_t r = idx / ncols;
-        dst[idx] = W[r * in + col0 + c];
-    }
-}
-__global__ void k_copy_pad(const float *src, int n, int npad, float *dst) {
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < npad; idx += gridDim.x * blockDim.x)
-        dst[idx] = idx < n ? src[idx] : 0.f;
 }
 
-#include "bind_kernels.cuh"
 #include "encoder_kernels.cuh"
 #include "pixel_kernels.cuh"
 
@@ -1031,61 +1009,7 @@ int ensure_layer_alloc(tdmpc2_plan *h, int net, int layer, const LayerShape &sh)
     }
     return 0;
 }
-}  // namespace
 
-int tdmpc2_plan_bind_weights(tdmpc2_plan_t *h, int net, int layer, const float *W, const float *b, const float *ln_g,
-                             const float *ln_b, int out_features, int in_features, void *stream) {
-    if (!h || !W || !b) return fail(TDMPC2_ERR_INVALID, "null argument");
-    if (layer < 0 || layer > 2) return fail(TDMPC2_ERR_INVALID, "layer %d outside [0, 2]", layer);
-    if (net < TDMPC2_NET_DYNAMICS || net > TDMPC2_NET_TARGET_Q) return fail(TDMPC2_ERR_INVALID, "unknown net %d", net);
-    const tdmpc2_plan_cfg &c = h->cfg;
-    if (net == TDMPC2_NET_TERMINATION && !c.episodic)
-        return fail(TDMPC2_ERR_INVALID, "termination head bound on a non-episodic planner");
-    ENTER_ON(h, stream);
-    hipStream_t st = (hipStream_t)stream;
-    const LayerShape sh = layer_shape(h, net, layer);
-    if (in_features != sh.in || out_features != sh.out)
-        return fail(TDMPC2_ERR_INVALID, "net %d layer %d: got [%d, %d], expected [%d, %d]", net, layer, out_features,
-                    in_features, sh.out, sh.in);
-    if (sh.has_ln && (!ln_g || !ln_b)) return fail(TDMPC2_ERR_INVALID, "net %d layer %d needs LayerNorm parameters", net, layer);
-    int rc = ensure_layer_alloc(h, net, layer, sh);
-    if (rc) return rc;
-    for (int hd = 0; hd < sh.heads; ++hd) {
-        HostNet *N = net_of(h, net, hd);
-        HostLayer &L = N->l[layer];
-        const float *Wh = W + (size_t)hd * out_features * in_features;
-        if (h->split) {
-            HIP_TRY(hipMemsetAsync(&L.scal->maxbits, 0, 4, st));
-            hipLaunchKernelGGL(k_absmax, dim3(256), dim3(256), 0, st, Wh, (size_t)out_features * in_features, &L.scal->maxbits);
-            hipLaunchKernelGGL(k_wscale, dim3(1), dim3(1), 0, st, L.scal);
-            hipLaunchKernelGGL(k_pack_split, dim3(512), dim3(256), 0, st, Wh, out_features, in_features, sh.nz, sh.nt, sh.na, sh.CT,
-                               sh.KB, &L.scal->wscale, L.wps);
-            if (sh.has_ln) {
-                HIP_TRY(hipMemsetAsync(&L.scal->gmax, 0, 8, st));
-                hipLaunchKernelGGL(k_absmax, dim3(4), dim3(256), 0, st, ln_g + (size_t)hd * out_features, (size_t)out_features, &L.scal->gmax);
-                hipLaunchKernelGGL(k_absmax, dim3(4), dim3(256), 0, st, ln_b + (size_t)hd * out_features, (size_t)out_features, &L.scal->bmax);
-            }
-            hipLaunchKernelGGL(k_ascale, dim3(1), dim3(1), 0, st, L.scal, out_features, sh.has_ln && sh.mish ? 1 : 0);
-            hipLaunchKernelGGL(k_net_scales, dim3(1), dim3(1), 0, st, N->scal);
-        } else {
-            hipLaunchKernelGGL(k_pack_weight, dim3(512), dim3(256), 0, st, Wh, out_features, in_features, sh.nz, sh.nt, sh.na, sh.CT,
-                               sh.KB, L.wp);
-        }
-        hipLaunchKernelGGL(k_copy_pad, dim3(1), dim3(256), 0, st, b + (size_t)hd * out_features, out_features, sh.CT * 32, L.bias);
-        if (sh.has_ln) {
-            const int gb = (out_features + 255) / 256;
-            hipLaunchKernelGGL(k_copy_pad, dim3(gb), dim3(256), 0, st, ln_g + (size_t)hd * out_features, out_features, out_features, L.g);
-            hipLaunchKernelGGL(k_copy_pad, dim3(gb), dim3(256), 0, st, ln_b + (size_t)hd * out_features, out_features, out_features, L.b);
-        }
-        if (sh.nt > 0)
-            hipLaunchKernelGGL(k_copy_cols, dim3(64), dim3(256), 0, st, Wh, out_features, in_features, sh.nz, sh.nt, L.wemb);
-        HIP_TRY(hipGetLastError());
-        L.bound = true;
-    }
-    return TDMPC2_OK;
-}
-
-namespace {
 int ensure_enc_alloc(tdmpc2_plan *h, int layer, int in_features, int out_features) {
     const tdmpc2_plan_cfg &c = h->cfg;
     tdmpc2_plan::Enc &L = h->enc[layer];
@@ -1109,35 +1033,141 @@ int ensure_enc_alloc(tdmpc2_plan *h, int layer, int in_features, int out_feature
     }
     return 0;
 }
+
+// ================================================================ the weight packer's host side (k_refresh.hip: refresh_kernels.cuh, refresh_route.h)
+// Every entry point that stores weights describes JOBS -- one per (net, layer) with every ensemble member inside it, one per
+// transposed copy (a state-encoder layer, a layer of the policy prior's fp32 copy) -- and hands them to run_jobs.  The entry
+// points differ only in how they collect jobs: the per-layer binds describe one, the table calls walk their table.  Each kind
+// of job has ONE function that checks it, allocates its first-time storage and appends it; everything that can refuse,
+// refuses before anything is enqueued.
+struct RfJobs {
+    RfParams p{};
+    unsigned nets = 0;          // nets with a named layer
+    unsigned enc = 0, pol = 0;  // state-encoder / policy-copy layers among p.tr
+    int nenc = 0;               // the encoder depth its layers were checked against
+    explicit RfJobs(const tdmpc2_plan *h) {
+        p.split = h->split ? 1 : 0;
+        p.lerp_net = -1;
+    }
+};
+
+// one nn.Linear of a net (+ its LayerNorm), every ensemble member: `e` in the checkpoint's layout, stacked over heads
+int add_net_layer(tdmpc2_plan *h, RfJobs &j, int net, int l, const tdmpc2_weight_entry &e) {
+    if (net == TDMPC2_NET_TERMINATION && !h->cfg.episodic)
+        return fail(TDMPC2_ERR_INVALID, "termination head bound on a non-episodic planner");
+    const LayerShape sh = layer_shape(h, net, l);
+    if (!e.W || !e.b) return fail(TDMPC2_ERR_INVALID, "net %d is named but layer %d lacks its weight or bias", net, l);
+    if (sh.has_ln && (!e.ln_g || !e.ln_b)) return fail(TDMPC2_ERR_INVALID, "net %d layer %d needs LayerNorm parameters", net, l);
+    if (int rc = ensure_layer_alloc(h, net, l, sh)) return rc;
+    const HostLayer &L0 = net_of(h, net, 0)->l[l];
+    RfNet &N = j.p.net[net];
+    RfLayer &J = N.l[l];
+    J.W = e.W; J.b = e.b; J.g = sh.has_ln ? e.ln_g : nullptr; J.beta = sh.has_ln ? e.ln_b : nullptr;
+    J.wdst = h->split ? reinterpret_cast<float *>(L0.wps) : L0.wp;
+    J.bias = L0.bias; J.gd = L0.g; J.bd = L0.b; J.wemb = L0.wemb;
+    J.out = sh.out; J.in = sh.in; J.nz = sh.nz; J.nt = sh.nt; J.na = sh.na; J.CT = sh.CT; J.KB = sh.KB;
+    J.has_ln = sh.has_ln ? 1 : 0; J.mish = sh.mish ? 1 : 0;
+    J.scan_nbw = rf_scan_wblocks((long)sh.out * sh.in);
+    N.heads = sh.heads;
+    N.scal = h->split ? net_of(h, net, 0)->scal : nullptr;
+    N.mask |= 1 << l;
+    j.nets |= 1u << net;
+    return 0;
+}
+
+// layer `l` of a state encoder of `nenc` layers
+int add_enc_layer(tdmpc2_plan *h, RfJobs &j, int l, int nenc, const tdmpc2_weight_entry &e, int out_features, int in_features) {
+    const tdmpc2_plan_cfg &c = h->cfg;
+    if (nenc < 1 || nenc > ENC_MAX_LAYERS) return fail(TDMPC2_ERR_INVALID, "encoder depth %d outside [1, %d]", nenc, ENC_MAX_LAYERS);
+    if (l < 0 || l >= nenc) return fail(TDMPC2_ERR_INVALID, "encoder layer %d outside [0, %d)", l, nenc);
+    if (!e.W || !e.b || !e.ln_g || !e.ln_b) return fail(TDMPC2_ERR_INVALID, "encoder layer %d: null tensor", l);
+    if (out_features < 1 || out_features > ENC_THREADS * ENC_MAX_PER_THREAD || in_features < 1)
+        return fail(TDMPC2_ERR_UNSUPPORTED, "encoder layer %d: width %d outside [1, %d]", l, out_features, ENC_THREADS * ENC_MAX_PER_THREAD);
+    if (l == nenc - 1 && out_features != c.latent_dim)
+        return fail(TDMPC2_ERR_INVALID, "the last encoder layer has %d outputs, latent_dim is %d", out_features, c.latent_dim);
+    if (l == nenc - 1 && (c.latent_dim % c.simnorm_dim || (c.simnorm_dim & (c.simnorm_dim - 1)) || c.simnorm_dim > 64))
+        return fail(TDMPC2_ERR_UNSUPPORTED, "SimNorm groups of %d over %d latents", c.simnorm_dim, c.latent_dim);
+    if (h->enc_layers && h->enc_layers != nenc) return fail(TDMPC2_ERR_STATE, "encoder depth changed from %d to %d", h->enc_layers, nenc);
+    if (int rc = ensure_enc_alloc(h, l, in_features, out_features)) return rc;  // refuses a re-bind with another shape
+    const tdmpc2_plan::Enc &E = h->enc[l];
+    j.p.tr[j.p.ntrans++] = RfTrans{e.W, e.b, e.ln_g, e.ln_b, E.wt, E.bias, E.g, E.b, E.out, E.in};
+    j.enc |= 1u << l;
+    j.nenc = nenc;
+    return 0;
+}
+
+// layer `l` of the policy prior's fp32 copy; its buffers exist (tdmpc2_plan_bind_policy) and `e` has passed that call's checks
+// or add_net_layer(TDMPC2_NET_PI)'s, which ask the same of it
+void add_pol_layer(tdmpc2_plan *h, RfJobs &j, int l, const tdmpc2_weight_entry &e) {
+    const bool ln = l < 2;
+    const tdmpc2_plan_cfg &c = h->cfg;
+    const tdmpc2_plan::Pol &P = h->pol;
+    j.p.tr[j.p.ntrans++] = RfTrans{e.W, e.b, ln ? e.ln_g : nullptr, ln ? e.ln_b : nullptr, P.wt[l], P.bias[l], ln ? P.g[l] : nullptr,
+                                   ln ? P.b[l] : nullptr, l == 2 ? 2 * c.action_dim : c.mlp_dim, l == 0 ? c.latent_dim + c.task_dim : c.mlp_dim};
+    j.pol |= 1u << l;
+}
+
+// The launches refresh_route lists over the jobs' workgroup ranges, then the bound flags of exactly the jobs that ran.
+int run_jobs(tdmpc2_plan *h, RfJobs &j, hipStream_t st) {
+    RfParams &p = j.p;
+    const bool pi = j.nets >> TDMPC2_NET_PI & 1;
+    const RefreshRoute route = refresh_route(RefreshIn{p.split, j.nets, __builtin_popcount(j.enc), j.pol && pi, p.lerp_net >= 0,
+                                                       h->cfg.num_q, h->cfg.episodic, j.pol && !pi});
+    long sb = 0, pb = 0;
+    for (int net = 0; net < RF_NETS; ++net)
+        for (int l = 0; l < 3; ++l) {
+            const RfNet &N = p.net[net];
+            const RfLayer &J = N.l[l];
+            p.scan_blk0[net * 3 + l] = (int)sb;
+            p.pack_blk0[net * 3 + l] = (int)pb;
+            if (!(N.mask >> l & 1)) continue;
+            sb += (long)N.heads * (J.scan_nbw + 1);
+            pb += (long)N.heads * rf_pack_blocks(J.CT, J.KB * (p.split ? 16 : 8), J.nt);
+        }
+    p.scan_blk0[3 * RF_NETS] = (int)sb;
+    for (int t = 0; t < RF_MAX_TRANS; ++t) {
+        p.pack_blk0[3 * RF_NETS + t] = (int)pb;
+        if (t < p.ntrans) pb += rf_transpose_blocks(p.tr[t].out, p.tr[t].in);
+    }
+    p.pack_blk0[RF_SEGS] = (int)pb;
+    if (pb > 0x7fffffffL || sb > 0x7fffffffL) return fail(TDMPC2_ERR_UNSUPPORTED, "weight refresh: %ld workgroups", pb);
+    for (int i = 0; i < route.nops; ++i)
+        if (int rc = tdk::refresh_launch(route.op[i], p, st)) return rc;
+    for (int net = 0; net < RF_NETS; ++net)
+        for (int l = 0; l < 3; ++l)
+            if (p.net[net].mask >> l & 1)
+                for (int hd = 0; hd < p.net[net].heads; ++hd) net_of(h, net, hd)->l[l].bound = true;
+    for (int l = 0; l < ENC_MAX_LAYERS; ++l)
+        if (j.enc >> l & 1) h->enc[l].bound = true;
+    if (j.enc) h->enc_layers = j.nenc;
+    for (int l = 0; l < 3; ++l)
+        if (j.pol >> l & 1) h->pol.bound[l] = true;
+    return TDMPC2_OK;
+}
 }  // namespace
+
+int tdmpc2_plan_bind_weights(tdmpc2_plan_t *h, int net, int layer, const float *W, const float *b, const float *ln_g,
+                             const float *ln_b, int out_features, int in_features, void *stream) {
+    if (!h || !W || !b) return fail(TDMPC2_ERR_INVALID, "null argument");
+    if (layer < 0 || layer > 2) return fail(TDMPC2_ERR_INVALID, "layer %d outside [0, 2]", layer);
+    if (net < TDMPC2_NET_DYNAMICS || net > TDMPC2_NET_TARGET_Q) return fail(TDMPC2_ERR_INVALID, "unknown net %d", net);
+    ENTER_ON(h, stream);
+    const LayerShape sh = layer_shape(h, net, layer);  // the caller states the shape: it must be the handle's
+    if (in_features != sh.in || out_features != sh.out)
+        return fail(TDMPC2_ERR_INVALID, "net %d layer %d: got [%d, %d], expected [%d, %d]", net, layer, out_features,
+                    in_features, sh.out, sh.in);
+    RfJobs j(h);
+    if (int rc = add_net_layer(h, j, net, layer, tdmpc2_weight_entry{W, b, ln_g, ln_b})) return rc;
+    return run_jobs(h, j, (hipStream_t)stream);
+}
 
 int tdmpc2_plan_bind_encoder(tdmpc2_plan_t *h, int layer, int n_layers, const float *W, const float *b, const float *ln_g,
                              const float *ln_b, int out_features, int in_features, void *stream) {
     if (!h || !W || !b || !ln_g || !ln_b) return fail(TDMPC2_ERR_INVALID, "null argument");
-    if (n_layers < 1 || n_layers > ENC_MAX_LAYERS) return fail(TDMPC2_ERR_INVALID, "encoder depth %d outside [1, %d]", n_layers, ENC_MAX_LAYERS);
-    if (layer < 0 || layer >= n_layers) return fail(TDMPC2_ERR_INVALID, "encoder layer %d outside [0, %d)", layer, n_layers);
-    if (out_features < 1 || out_features > ENC_THREADS * ENC_MAX_PER_THREAD || in_features < 1)
-        return fail(TDMPC2_ERR_UNSUPPORTED, "encoder layer %d: width %d outside [1, %d]", layer, out_features, ENC_THREADS * ENC_MAX_PER_THREAD);
-    const tdmpc2_plan_cfg &c = h->cfg;
-    if (layer == n_layers - 1 && out_features != c.latent_dim)
-        return fail(TDMPC2_ERR_INVALID, "the last encoder layer has %d outputs, latent_dim is %d", out_features, c.latent_dim);
-    if (layer == n_layers - 1 && (c.latent_dim % c.simnorm_dim || (c.simnorm_dim & (c.simnorm_dim - 1)) || c.simnorm_dim > 64))
-        return fail(TDMPC2_ERR_UNSUPPORTED, "SimNorm groups of %d over %d latents", c.simnorm_dim, c.latent_dim);
-    if (h->enc_layers && h->enc_layers != n_layers) return fail(TDMPC2_ERR_STATE, "encoder depth changed from %d to %d", h->enc_layers, n_layers);
     ENTER_ON(h, stream);
-    int rc = ensure_enc_alloc(h, layer, in_features, out_features);
-    if (rc) return rc;
-    tdmpc2_plan::Enc &L = h->enc[layer];
-    hipStream_t st = (hipStream_t)stream;
-    const size_t n = (size_t)in_features * out_features;
-    hipLaunchKernelGGL(k_transpose, dim3((unsigned)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, st, W, L.wt, out_features, in_features);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(L.bias, b, (size_t)out_features * 4, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(L.g, ln_g, (size_t)out_features * 4, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(L.b, ln_b, (size_t)out_features * 4, hipMemcpyDeviceToDevice, st));
-    L.bound = true;
-    h->enc_layers = n_layers;
-    return TDMPC2_OK;
+    RfJobs j(h);
+    if (int rc = add_enc_layer(h, j, layer, n_layers, tdmpc2_weight_entry{W, b, ln_g, ln_b}, out_features, in_features)) return rc;
+    return run_jobs(h, j, (hipStream_t)stream);
 }
 
 namespace {
@@ -1321,7 +1351,6 @@ int tdmpc2_plan_bind_policy(tdmpc2_plan_t *h, int layer, const float *W, const f
         return fail(TDMPC2_ERR_UNSUPPORTED, "policy prior: widths %d / %d beyond %d", in0, M, POL_MAX_WIDTH);
     ENTER_ON(h, stream);
     tdmpc2_plan::Pol &P = h->pol;
-    hipStream_t st = (hipStream_t)stream;
     int rc;
     if (!P.x) {  // every buffer of the policy prior, once: pi / act_pi never allocate
         for (int l = 0; l < 3; ++l) {
@@ -1336,167 +1365,55 @@ int tdmpc2_plan_bind_policy(tdmpc2_plan_t *h, int layer, const float *W, const f
         if ((rc = tdk::pol_set_lds())) return rc;
         if ((rc = dev_alloc(h, (void **)&P.x, pol_ws_x_floats(c.max_envs, M) * 4))) return rc;  // last: marks the set complete
     }
-    const size_t n = (size_t)in_features * out_features;
-    hipLaunchKernelGGL(k_transpose, dim3((unsigned)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, st, W, P.wt[layer], out_features, in_features);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(P.bias[layer], b, (size_t)out_features * 4, hipMemcpyDeviceToDevice, st));
-    if (layer < 2) {
-        HIP_TRY(hipMemcpyAsync(P.g[layer], ln_g, (size_t)out_features * 4, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(P.b[layer], ln_b, (size_t)out_features * 4, hipMemcpyDeviceToDevice, st));
-    }
-    P.bound[layer] = true;
-    return TDMPC2_OK;
+    RfJobs j(h);
+    add_pol_layer(h, j, layer, tdmpc2_weight_entry{W, b, ln_g, ln_b});
+    return run_jobs(h, j, (hipStream_t)stream);
 }
 
-// ================================================================ grouped weight refresh (k_refresh.hip: refresh_kernels.cuh, refresh_route.h)
-namespace {
-// One job per (net, layer) the table names (every ensemble member inside it), the encoder's and the policy copy's transposes,
-// and the workgroup ranges of the scan and pack launches.  Everything that can refuse, refuses before anything is enqueued;
-// first-time storage is allocated here.  `targets`: soft update -- the sources of TDMPC2_NET_TARGET_Q are the caller's target
-// tensors and `tab` names the online ensemble they move towards.
-int refresh_build(tdmpc2_plan *h, const tdmpc2_weight_table *tab, float *const targets[3][4], float tau, RfParams &p, RefreshRoute &route) {
-    const tdmpc2_plan_cfg &c = h->cfg;
-    p = RfParams{};
-    p.split = h->split ? 1 : 0;
-    p.lerp_net = -1;
-    unsigned nets = 0;
-    for (int net = TDMPC2_NET_DYNAMICS; net <= TDMPC2_NET_TARGET_Q; ++net) {
-        tdmpc2_weight_entry src[3];
-        if (targets) {
-            if (net != TDMPC2_NET_TARGET_Q) continue;
-            for (int l = 0; l < 3; ++l) {
-                src[l] = tdmpc2_weight_entry{targets[l][0], targets[l][1], targets[l][2], targets[l][3]};
-                const tdmpc2_weight_entry &on = tab->net[TDMPC2_NET_Q][l];
-                const bool ln = layer_shape(h, net, l).has_ln;
-                if (!on.W || !on.b || (ln && (!on.ln_g || !on.ln_b)))
-                    return fail(TDMPC2_ERR_INVALID, "soft update: the table lacks the online Q ensemble (layer %d)", l);
-                if (!src[l].W || !src[l].b || (ln && (!src[l].ln_g || !src[l].ln_b)))
-                    return fail(TDMPC2_ERR_INVALID, "soft update: null target tensor (layer %d)", l);
-                p.online[l][0] = on.W; p.online[l][1] = on.b; p.online[l][2] = ln ? on.ln_g : nullptr; p.online[l][3] = ln ? on.ln_b : nullptr;
-            }
-            p.lerp_net = net;
-            p.tau = tau;
-        } else {
-            int named = 0;
-            for (int l = 0; l < 3; ++l) {
-                src[l] = tab->net[net][l];
-                named += (src[l].W != nullptr) + (src[l].b != nullptr) + (src[l].ln_g != nullptr) + (src[l].ln_b != nullptr);
-            }
-            if (!named) continue;  // left as it is
-            if (net == TDMPC2_NET_TERMINATION && !c.episodic)
-                return fail(TDMPC2_ERR_INVALID, "termination head in the table of a non-episodic planner");
-            for (int l = 0; l < 3; ++l) {
-                if (!src[l].W || !src[l].b) return fail(TDMPC2_ERR_INVALID, "net %d is named but layer %d lacks its weight or bias", net, l);
-                if (layer_shape(h, net, l).has_ln && (!src[l].ln_g || !src[l].ln_b))
-                    return fail(TDMPC2_ERR_INVALID, "net %d layer %d needs LayerNorm parameters", net, l);
-            }
-        }
-        RfNet &N = p.net[net];
-        for (int l = 0; l < 3; ++l) {
-            const LayerShape sh = layer_shape(h, net, l);
-            if (int rc = ensure_layer_alloc(h, net, l, sh)) return rc;
-            const HostLayer &L0 = net_of(h, net, 0)->l[l];
-            RfLayer &J = N.l[l];
-            J.W = src[l].W; J.b = src[l].b; J.g = sh.has_ln ? src[l].ln_g : nullptr; J.beta = sh.has_ln ? src[l].ln_b : nullptr;
-            J.wdst = h->split ? reinterpret_cast<float *>(L0.wps) : L0.wp;
-            J.bias = L0.bias; J.gd = L0.g; J.bd = L0.b; J.wemb = L0.wemb;
-            J.out = sh.out; J.in = sh.in; J.nz = sh.nz; J.nt = sh.nt; J.na = sh.na; J.CT = sh.CT; J.KB = sh.KB;
-            J.has_ln = sh.has_ln ? 1 : 0; J.mish = sh.mish ? 1 : 0;
-            J.scan_nbw = rf_scan_wblocks((long)sh.out * sh.in);
-            N.heads = sh.heads;
-        }
-        N.scal = h->split ? net_of(h, net, 0)->scal : nullptr;
-        N.on = 1;
-        nets |= 1u << net;
-    }
-    // the state encoder: bind_encoder's rules
-    const int nenc = targets ? 0 : tab->enc_layers;
-    if (nenc < 0 || nenc > ENC_MAX_LAYERS) return fail(TDMPC2_ERR_INVALID, "encoder depth %d outside [0, %d]", nenc, ENC_MAX_LAYERS);
-    if (nenc && h->enc_layers && h->enc_layers != nenc) return fail(TDMPC2_ERR_STATE, "encoder depth changed from %d to %d", h->enc_layers, nenc);
-    for (int l = 0; l < nenc; ++l) {
-        const tdmpc2_weight_entry &e = tab->enc[l];
-        const int of = tab->enc_out[l], inf = tab->enc_in[l];
-        if (!e.W || !e.b || !e.ln_g || !e.ln_b) return fail(TDMPC2_ERR_INVALID, "encoder layer %d: null tensor", l);
-        if (of < 1 || of > ENC_THREADS * ENC_MAX_PER_THREAD || inf < 1)
-            return fail(TDMPC2_ERR_UNSUPPORTED, "encoder layer %d: width %d outside [1, %d]", l, of, ENC_THREADS * ENC_MAX_PER_THREAD);
-        if (l == nenc - 1 && of != c.latent_dim)
-            return fail(TDMPC2_ERR_INVALID, "the last encoder layer has %d outputs, latent_dim is %d", of, c.latent_dim);
-        if (l == nenc - 1 && (c.latent_dim % c.simnorm_dim || (c.simnorm_dim & (c.simnorm_dim - 1)) || c.simnorm_dim > 64))
-            return fail(TDMPC2_ERR_UNSUPPORTED, "SimNorm groups of %d over %d latents", c.simnorm_dim, c.latent_dim);
-        if (h->enc[l].wt && (h->enc[l].in != inf || h->enc[l].out != of))
-            return fail(TDMPC2_ERR_STATE, "encoder layer %d refreshed with a different shape", l);
-    }
-    for (int l = 0; l < nenc; ++l) {
-        if (int rc = ensure_enc_alloc(h, l, tab->enc_in[l], tab->enc_out[l])) return rc;
-        const tdmpc2_plan::Enc &E = h->enc[l];
-        const tdmpc2_weight_entry &e = tab->enc[l];
-        p.tr[p.ntrans++] = RfTrans{e.W, e.b, e.ln_g, e.ln_b, E.wt, E.bias, E.g, E.b, E.out, E.in};
-    }
-    // the policy prior's fp32 copy, when its buffers exist
-    const bool pol = !targets && h->pol.x && (nets & (1u << TDMPC2_NET_PI));
-    if (pol)
-        for (int l = 0; l < 3; ++l) {
-            const RfLayer &J = p.net[TDMPC2_NET_PI].l[l];
-            const tdmpc2_plan::Pol &P = h->pol;
-            p.tr[p.ntrans++] = RfTrans{J.W, J.b, l < 2 ? J.g : nullptr, l < 2 ? J.beta : nullptr, P.wt[l], P.bias[l],
-                                       l < 2 ? P.g[l] : nullptr, l < 2 ? P.b[l] : nullptr, J.out, J.in};
-        }
-    route = refresh_route(RefreshIn{p.split, nets, nenc, pol ? 1 : 0, targets ? 1 : 0, c.num_q, c.episodic});
-    // workgroup ranges
-    long sb = 0, pb = 0;
-    for (int net = 0; net < RF_NETS; ++net)
-        for (int l = 0; l < 3; ++l) {
-            const RfNet &N = p.net[net];
-            const RfLayer &J = N.l[l];
-            p.scan_blk0[net * 3 + l] = (int)sb;
-            p.pack_blk0[net * 3 + l] = (int)pb;
-            if (!N.on) continue;
-            sb += (long)N.heads * (J.scan_nbw + 1);
-            pb += (long)N.heads * rf_pack_blocks(J.CT, J.KB * (p.split ? 16 : 8), J.nt);
-        }
-    p.scan_blk0[3 * RF_NETS] = (int)sb;
-    for (int t = 0; t < RF_MAX_TRANS; ++t) {
-        p.pack_blk0[3 * RF_NETS + t] = (int)pb;
-        if (t < p.ntrans) pb += rf_transpose_blocks(p.tr[t].out, p.tr[t].in);
-    }
-    p.pack_blk0[RF_SEGS] = (int)pb;
-    if (pb > 0x7fffffffL || sb > 0x7fffffffL) return fail(TDMPC2_ERR_UNSUPPORTED, "weight refresh: %ld workgroups", pb);
-    return 0;
-}
-
-int refresh_run(tdmpc2_plan *h, const RfParams &p, const RefreshRoute &route, int nenc, hipStream_t st) {
-    for (int i = 0; i < route.nops; ++i)
-        if (int rc = tdk::refresh_launch(route.op[i], p, st)) return rc;
-    for (int net = 0; net < RF_NETS; ++net)
-        if (p.net[net].on)
-            for (int hd = 0; hd < p.net[net].heads; ++hd)
-                for (int l = 0; l < 3; ++l) net_of(h, net, hd)->l[l].bound = true;
-    for (int l = 0; l < nenc; ++l) h->enc[l].bound = true;
-    if (nenc) h->enc_layers = nenc;
-    if (route.policy_copy)
-        for (int l = 0; l < 3; ++l) h->pol.bound[l] = true;
-    return TDMPC2_OK;
-}
-}  // namespace
-
+// ================================================================ weight tables: the packer's jobs, collected from a table
+// Every net the table names (all three layers of it), the state encoder, and the policy prior's fp32 copy when its buffers
+// exist and TDMPC2_NET_PI is named.
 int tdmpc2_plan_refresh_weights(tdmpc2_plan_t *h, const tdmpc2_weight_table *tab, void *stream) {
     if (!h || !tab) return fail(TDMPC2_ERR_INVALID, "null argument");
     ENTER_ON(h, stream);
-    RfParams p;
-    RefreshRoute route;
-    if (int rc = refresh_build(h, tab, nullptr, 0.f, p, route)) return rc;
-    return refresh_run(h, p, route, tab->enc_layers, (hipStream_t)stream);
+    RfJobs j(h);
+    for (int net = TDMPC2_NET_DYNAMICS; net <= TDMPC2_NET_TARGET_Q; ++net) {
+        int named = 0;
+        for (const tdmpc2_weight_entry &e : tab->net[net]) named += (e.W != nullptr) + (e.b != nullptr) + (e.ln_g != nullptr) + (e.ln_b != nullptr);
+        if (!named) continue;  // left as it is
+        for (int l = 0; l < 3; ++l)
+            if (int rc = add_net_layer(h, j, net, l, tab->net[net][l])) return rc;
+    }
+    if (tab->enc_layers < 0) return fail(TDMPC2_ERR_INVALID, "encoder depth %d outside [0, %d]", tab->enc_layers, ENC_MAX_LAYERS);
+    for (int l = 0; l < tab->enc_layers; ++l)
+        if (int rc = add_enc_layer(h, j, l, tab->enc_layers, tab->enc[l], tab->enc_out[l], tab->enc_in[l])) return rc;
+    if (h->pol.x && (j.nets >> TDMPC2_NET_PI & 1))
+        for (int l = 0; l < 3; ++l) add_pol_layer(h, j, l, tab->net[TDMPC2_NET_PI][l]);
+    return run_jobs(h, j, (hipStream_t)stream);
 }
 
+// The jobs of TDMPC2_NET_TARGET_Q with the caller's target tensors as sources; RO_SCAN lerps them towards the online ensemble
+// `online` names before it scans them.
 int tdmpc2_plan_soft_update_target(tdmpc2_plan_t *h, const tdmpc2_weight_table *online, float *const target[3][4], float tau,
                                    void *stream) {
     if (!h || !online || !target) return fail(TDMPC2_ERR_INVALID, "null argument");
     if (!(tau >= 0.f && tau <= 1.f)) return fail(TDMPC2_ERR_INVALID, "soft update: tau %g outside [0, 1]", (double)tau);
     ENTER_ON(h, stream);
-    RfParams p;
-    RefreshRoute route;
-    if (int rc = refresh_build(h, online, target, tau, p, route)) return rc;
-    return refresh_run(h, p, route, 0, (hipStream_t)stream);
+    RfJobs j(h);
+    for (int l = 0; l < 3; ++l) {
+        const tdmpc2_weight_entry src{target[l][0], target[l][1], target[l][2], target[l][3]};
+        const tdmpc2_weight_entry &on = online->net[TDMPC2_NET_Q][l];
+        const bool ln = layer_shape(h, TDMPC2_NET_TARGET_Q, l).has_ln;
+        if (!on.W || !on.b || (ln && (!on.ln_g || !on.ln_b)))
+            return fail(TDMPC2_ERR_INVALID, "soft update: the table lacks the online Q ensemble (layer %d)", l);
+        if (!src.W || !src.b || (ln && (!src.ln_g || !src.ln_b)))
+            return fail(TDMPC2_ERR_INVALID, "soft update: null target tensor (layer %d)", l);
+        if (int rc = add_net_layer(h, j, TDMPC2_NET_TARGET_Q, l, src)) return rc;
+        j.p.online[l][0] = on.W; j.p.online[l][1] = on.b; j.p.online[l][2] = ln ? on.ln_g : nullptr; j.p.online[l][3] = ln ? on.ln_b : nullptr;
+    }
+    j.p.lerp_net = TDMPC2_NET_TARGET_Q;
+    j.p.tau = tau;
+    return run_jobs(h, j, (hipStream_t)stream);
 }
 
 namespace {

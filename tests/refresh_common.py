@@ -1,5 +1,6 @@
 """Shared by the weight-refresh tests (tests/test_gpu_refresh.py, tests/test_refresh_golden.py) and tools/make_soft_update_golden.py:
-the seeded inputs of the soft-update fixture, the gate of a lerped element, and a reader of the packed blob's segment table."""
+the seeded inputs of the soft-update fixture, the gate of a lerped element, a reader of the packed blob's segment table, and
+the weight sets and per-owner digests of the packed-bytes fixture (tools/make_packed_digests.py)."""
 import hashlib
 import struct
 
@@ -98,3 +99,77 @@ def blob_segments(blob, cfg, split, has_target=True, enc_layers=2):
         out.append((o, blob[pos:pos + n]))
         pos += n
     return out
+
+
+# ---------------------------------------------------------------- weight sets of the blob tests and of packed_digests.json
+# (case, path, precision): fused split / fp32 (heads of 101 and 2 A columns, action padding), fused multitask (wemb), layered
+# episodic (GBK row padding, termination net), layered fp32 multitask
+CASES = [("c1", 1, 2), ("c1", 1, 1), ("mt5", 1, 2), ("small_ep", 2, 2), ("small_mt", 2, 1)]
+IDS = ["c1-split", "c1-fp32", "mt5", "small_ep", "small_mt"]
+EDGE_VARIANTS = ("zero_last", "ln_gain", "kw_clamps", "nonfinite")
+PACKED_DIGESTS = "packed_digests.json"
+
+
+def device_sd(c, device):
+    """The case's checkpoint as contiguous fp32 device tensors: what a trainer holds (and a refresh reads in place)."""
+    import torch
+
+    return {k: torch.as_tensor(np.asarray(v)).to(device, torch.float32).contiguous() for k, v in c["sd"].items()
+            if k.startswith(("_dynamics.", "_reward.", "_pi.", "_Qs.params.", "_termination.", "_target_Qs_params.", "_encoder.state."))}
+
+
+def perturb(sd, seed, scale=0.02):
+    import torch
+
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    for k in sorted(sd):
+        sd[k].add_((scale * torch.randn(sd[k].shape, generator=g)).to(sd[k].device))
+
+
+def edge_weights(sd, variant):
+    import torch
+
+    with torch.no_grad():
+        if variant == "zero_last":       # maxbits = 0: what a fresh model's zero-initialised heads give
+            sd["_reward.2.weight"].zero_()
+            sd["_Qs.params.2.weight"].zero_()
+            sd["_target_Qs_params.2.weight"].zero_()
+        elif variant == "ln_gain":       # ka leaves 5
+            sd["_dynamics.0.ln.weight"][3] = 1e3
+            sd["_Qs.params.1.ln.weight"][1, 7] = -1e3
+            sd["_pi.1.ln.bias"][2] = 4e4
+        elif variant == "kw_clamps":     # kw near and beyond its clamps
+            sd["_pi.1.weight"][5, 9] = 3e4
+            sd["_reward.1.weight"].fill_(1e-30)
+            sd["_Qs.params.0.weight"][1, 2, 3] = 1e20
+            sd["_dynamics.2.weight"].mul_(1e-30)
+        elif variant == "nonfinite":     # the scan of max|W| skips them
+            sd["_dynamics.1.weight"][4, 4] = float("nan")
+            sd["_reward.0.weight"][0, 1] = float("inf")
+            sd["_Qs.params.1.weight"][2, 1, 1] = float("-inf")
+            sd["_pi.0.ln.weight"][0] = float("nan")
+
+
+def packed_inputs(c, device):
+    """(label, state dict) of the six weight sets the packed-bytes fixture records: the case's own, a seeded perturbation of
+    them, and the four edge variants."""
+    yield "plain", device_sd(c, device)
+    sd = device_sd(c, device)
+    perturb(sd, 1)
+    yield "perturbed", sd
+    for variant in EDGE_VARIANTS:
+        sd = device_sd(c, device)
+        edge_weights(sd, variant)
+        yield variant, sd
+
+
+def sd_digest(sd):
+    return digest({k: v.detach().cpu().numpy() for k, v in sd.items()})
+
+
+def owner_digests(blob, cfg, split):
+    """{owner: SHA-256 over that owner's segments, in the blob's order}."""
+    hs = {}
+    for o, seg in blob_segments(blob, cfg, split):
+        hs.setdefault(o, hashlib.sha256()).update(seg)
+    return {o: h.hexdigest() for o, h in hs.items()}

@@ -8,8 +8,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIM = r"""
 #include "refresh_route.h"
 // out: nops, op[4], nets, enc_layers, policy_copy, REFRESH_MAX_OPS
-extern "C" void route(int split, unsigned nets, int enc_layers, int policy_copy, int lerp, int num_q, int episodic, int *out) {
-    const RefreshRoute r = refresh_route(RefreshIn{split, nets, enc_layers, policy_copy, lerp, num_q, episodic});
+extern "C" void route(int split, unsigned nets, int enc_layers, int policy_copy, int lerp, int num_q, int episodic, int policy_alone,
+                      int *out) {
+    const RefreshRoute r = refresh_route(RefreshIn{split, nets, enc_layers, policy_copy, lerp, num_q, episodic, policy_alone});
     out[0] = r.nops;
     for (int i = 0; i < REFRESH_MAX_OPS; ++i) out[1 + i] = i < r.nops ? r.op[i] : -1;
     out[5] = (int)r.nets; out[6] = r.enc_layers; out[7] = r.policy_copy; out[8] = REFRESH_MAX_OPS;
@@ -34,7 +35,7 @@ def build(tmpdir):
     return lib
 
 
-def route(lib, split, nets, enc_layers=0, policy_copy=0, lerp=0, num_q=5, episodic=0):
+def route(lib, split, nets, enc_layers=0, policy_copy=0, lerp=0, num_q=5, episodic=0, policy_alone=0):
     out = (ctypes.c_int * 9)()
-    lib.route(int(split), nets, enc_layers, int(policy_copy), int(lerp), num_q, int(episodic), out)
+    lib.route(int(split), nets, enc_layers, int(policy_copy), int(lerp), num_q, int(episodic), int(policy_alone), out)
     return {"ops": list(out[1:1 + out[0]]), "nets": out[5], "enc_layers": out[6], "policy_copy": out[7], "max_ops": out[8]}

@@ -98,7 +98,7 @@ def test_split_arithmetic_on_heavy_tailed_weights(name, path):
 @pytest.mark.parametrize("name,path", [("c1", 1), ("small", 2)])
 def test_huge_layernorm_gain_does_not_saturate(name, path):
     """gamma = 300 on the hidden layers: |Mish(LayerNorm)| reaches ~6e3, 32x that overflows f16 (65504).  The bind-time
-    activation scale (k_ascale) lowers the operand scale of exactly those layers; values stay finite and fp32-accurate."""
+    activation scale (k_rf_scales) lowers the operand scale of exactly those layers; values stay finite and fp32-accurate."""
     from tdmpc2_amd import synth
     from tdmpc2_amd.config import named_config
 

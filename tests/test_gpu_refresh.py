@@ -1,9 +1,13 @@
 """-m gpu: the weight refresh in one call and the target-Q soft update (ABI 14).  tdmpc2_plan_refresh_weights must reproduce the
 per-layer binds, so the criterion has no tolerance: byte identity of tdmpc2_plan_export_packed (slabs, scale records, biases,
-LayerNorm vectors, task-embedding columns, encoder); the policy prior's fp32 copy is compared through tdmpc2_plan_pi.  The
+LayerNorm vectors, task-embedding columns, encoder); the policy prior's fp32 copy is compared through tdmpc2_plan_pi.  Both
+are job tables over ONE packer, so the bytes themselves are pinned to recorded digests (tests/golden/packed_digests.json) and
+the one-layer jobs of the per-layer binds are tested where a layer mask can go wrong.  The
 soft update's lerp is gated per element against fp64, |out - ref64| <= 2^-23 (|t| + |o|) (tests/refresh_common.py), and its
 pack against a handle freshly bound from the lerped tensors."""
+import json
 import os
+import struct
 
 import numpy as np
 import pytest
@@ -14,10 +18,7 @@ from tests.gpu_common import dev
 
 pytestmark = pytest.mark.gpu
 
-# (case, path, precision): fused split / fp32 (heads of 101 and 2 A columns, action padding), fused multitask (wemb), layered
-# episodic (GBK row padding, termination net), layered fp32 multitask
-CASES = [("c1", 1, 2), ("c1", 1, 1), ("mt5", 1, 2), ("small_ep", 2, 2), ("small_mt", 2, 1)]
-IDS = ["c1-split", "c1-fp32", "mt5", "small_ep", "small_mt"]
+CASES, IDS = rc.CASES, rc.IDS
 _cases = {}
 
 
@@ -30,9 +31,7 @@ def _case(name):
 
 
 def _sd(c):
-    """The case's checkpoint as contiguous fp32 device tensors: what a trainer holds (and a refresh reads in place)."""
-    return {k: torch.as_tensor(np.asarray(v)).to(dev(), torch.float32).contiguous() for k, v in c["sd"].items()
-            if k.startswith(("_dynamics.", "_reward.", "_pi.", "_Qs.params.", "_termination.", "_target_Qs_params.", "_encoder.state."))}
+    return rc.device_sd(c, dev())
 
 
 def _planner(c, path, prec):
@@ -48,10 +47,7 @@ def _bind(pl, sd):
         pl.bind_policy(sd)
 
 
-def _perturb(sd, seed, scale=0.02):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    for k in sorted(sd):
-        sd[k].add_((scale * torch.randn(sd[k].shape, generator=g)).to(sd[k].device))
+_perturb, _edge_weights = rc.perturb, rc.edge_weights
 
 
 def _diff_owners(a, b, cfg, split):
@@ -79,28 +75,6 @@ def _td(pl, c, sd):
 
 
 # ---------------------------------------------------------------- 1. blob identity
-def _edge_weights(sd, variant):
-    with torch.no_grad():
-        if variant == "zero_last":       # maxbits = 0: what a fresh model's zero-initialised heads give
-            sd["_reward.2.weight"].zero_()
-            sd["_Qs.params.2.weight"].zero_()
-            sd["_target_Qs_params.2.weight"].zero_()
-        elif variant == "ln_gain":       # ka leaves 5
-            sd["_dynamics.0.ln.weight"][3] = 1e3
-            sd["_Qs.params.1.ln.weight"][1, 7] = -1e3
-            sd["_pi.1.ln.bias"][2] = 4e4
-        elif variant == "kw_clamps":     # kw near and beyond its clamps
-            sd["_pi.1.weight"][5, 9] = 3e4
-            sd["_reward.1.weight"].fill_(1e-30)
-            sd["_Qs.params.0.weight"][1, 2, 3] = 1e20
-            sd["_dynamics.2.weight"].mul_(1e-30)
-        elif variant == "nonfinite":     # k_absmax skips them
-            sd["_dynamics.1.weight"][4, 4] = float("nan")
-            sd["_reward.0.weight"][0, 1] = float("inf")
-            sd["_Qs.params.1.weight"][2, 1, 1] = float("-inf")
-            sd["_pi.0.ln.weight"][0] = float("nan")
-
-
 @pytest.mark.parametrize("name,path,prec", CASES, ids=IDS)
 def test_refresh_reproduces_the_binds_byte_for_byte(name, path, prec):
     c = _case(name)
@@ -125,6 +99,160 @@ def test_refresh_reproduces_the_binds_byte_for_byte(name, path, prec):
         assert a == B.export_packed(), variant
     A.close()
     B.close()
+
+
+# ---------------------------------------------------------------- 1b. the bytes themselves, pinned
+@pytest.mark.parametrize("name,path,prec", CASES, ids=IDS)
+def test_packed_bytes_match_the_recorded_digests(name, path, prec, request):
+    """tests/golden/packed_digests.json (tools/make_packed_digests.py) holds, per weight set and segment owner, the SHA-256 of
+    what the commit named in the file packed.  Both ways of filling a handle must still produce exactly those bytes."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", rc.PACKED_DIGESTS)) as f:
+        rec = json.load(f)["rows"][request.node.callspec.id]
+    c = _case(name)
+    A, B = _planner(c, path, prec), _planner(c, path, prec)
+    seen = []
+    for label, sd in rc.packed_inputs(c, dev()):
+        assert rc.sd_digest(sd) == rec[label]["input"], f"{label}: the INPUT tensors differ from the recorded ones, not the packer"
+        A.bind_state_dict(sd)
+        A.bind_encoder(sd)
+        B.refresh_state_dict(sd)
+        for way, pl in (("binds", A), ("refresh", B)):
+            got = rc.owner_digests(pl.export_packed(), c["cfg"], prec == 2)
+            assert got == rec[label]["owners"], (label, way, sorted(o for o in got if got[o] != rec[label]["owners"].get(o)))
+        seen.append(label)
+    assert sorted(seen) == sorted(rec) and len(seen) == 2 + len(rc.EDGE_VARIANTS)
+    A.close()
+    B.close()
+
+
+# ---------------------------------------------------------------- 1c. one-layer jobs: where the layer mask can go wrong
+ONE_LAYER = dict(argnames="name,path,prec", argvalues=[CASES[0], CASES[3]], ids=[IDS[0], IDS[3]])
+FIELDS = ("weight", "bias", "ln.weight", "ln.bias")
+
+
+def _bind_layer(pl, sd, net, layer):
+    """tdmpc2_plan_bind_weights itself: one (net, layer), every ensemble member."""
+    from tdmpc2_amd import native
+
+    t = [sd.get(f"{native.NET_PREFIX[net]}.{layer}.{n}") for n in FIELDS]
+    pl._check(pl.lib.tdmpc2_plan_bind_weights(pl._h, net, layer, *(native._ptr(x) for x in t), int(t[0].shape[-2]), int(t[0].shape[-1]),
+                                              pl._stream()))
+
+
+def _scales(blob, cfg, owner):
+    """[head][layer] -> dict of the LayerScal record (the last segment of every ensemble member of a split handle)."""
+    segs = [x for o, x in rc.blob_segments(blob, cfg, True) if o == owner]
+    heads = int(cfg.num_q) if owner in ("q", "target_q") else 1
+    per = len(segs) // heads
+    names = ("wscale", "oscale", "maxbits", "kw", "ascale", "ka", "gmax", "bmax")
+    return [[dict(zip(names, struct.unpack_from("<ffIifiII", segs[hd * per + per - 1], 32 * l))) for l in range(3)] for hd in range(heads)]
+
+
+def _layer1_variant(c):
+    """The ln_gain and kw_clamps weight sets in one, with edits of the same kinds on the layer-1 tensors this test re-binds
+    (those two sets leave `_dynamics.1.*` alone): kw AND ka of layer 1 move in both nets."""
+    v = _sd(c)
+    _edge_weights(v, "ln_gain")
+    _edge_weights(v, "kw_clamps")
+    with torch.no_grad():
+        v["_dynamics.1.ln.weight"][3] = 1e3
+        v["_dynamics.1.weight"][5, 9] = 3e4
+        v["_Qs.params.1.weight"][1, 2, 3] = 1e20
+    return v
+
+
+@pytest.mark.parametrize(**ONE_LAYER)
+def test_rebinding_one_layer_leaves_its_neighbours(name, path, prec):
+    from tdmpc2_amd import native
+
+    c = _case(name)
+    cfg, sd, v = c["cfg"], _sd(c), _layer1_variant(c)
+    A = _planner(c, path, prec)
+    _bind(A, sd)
+    before = A.export_packed()
+    mixed = {k: (v[k] if k.startswith(("_dynamics.1.", "_Qs.params.1.")) else t) for k, t in sd.items()}
+    _bind_layer(A, mixed, native.NET_DYNAMICS, 1)
+    _bind_layer(A, mixed, native.NET_Q, 1)
+    after = A.export_packed()
+    F = _planner(c, path, prec)
+    _bind(F, mixed)
+    assert after == F.export_packed()
+    assert _diff_owners(before, after, cfg, True) == {"dynamics", "q"}
+    for owner, hd in (("dynamics", 0), ("q", 1)):  # the member whose tensors were edited
+        s0, s1 = _scales(before, cfg, owner)[hd], _scales(after, cfg, owner)[hd]
+        assert (s1[0]["kw"], s1[2]["kw"]) == (s0[0]["kw"], s0[2]["kw"]) and s1[0] == s0[0]
+        assert s1[1]["kw"] != s0[1]["kw"] and s1[1]["ka"] != s0[1]["ka"]
+        assert s1[2]["oscale"] == 2.0 ** -(s1[2]["kw"] + s1[1]["ka"]) != s0[2]["oscale"]
+    A.close()
+    F.close()
+
+
+@pytest.mark.parametrize(**ONE_LAYER)
+def test_layer_order_of_the_binds_does_not_matter(name, path, prec):
+    from tdmpc2_amd import native
+
+    c = _case(name)
+    sd = _sd(c)
+    _edge_weights(sd, "ln_gain")  # scales that differ between the layers
+    A, R = _planner(c, path, prec), _planner(c, path, prec)
+    _bind(A, sd)
+    for net, prefix in native.NET_PREFIX.items():
+        if f"{prefix}.0.weight" in sd:
+            for layer in (2, 1, 0):
+                _bind_layer(R, sd, net, layer)
+    R.bind_encoder(sd)
+    assert R.export_packed() == A.export_packed()
+    A.close()
+    R.close()
+
+
+@pytest.mark.parametrize(**ONE_LAYER)
+def test_rebinding_one_encoder_layer_touches_the_encoder_only(name, path, prec):
+    from tdmpc2_amd import native
+
+    c = _case(name)
+    cfg, sd = c["cfg"], _sd(c)
+    A = _planner(c, path, prec)
+    _bind(A, sd)
+    before = A.export_packed()
+    mixed = dict(sd)
+    for n in FIELDS:
+        mixed[f"_encoder.state.0.{n}"] = sd[f"_encoder.state.0.{n}"] * 1.5 + 0.25
+    t = [mixed[f"_encoder.state.0.{n}"] for n in FIELDS]
+    A._check(A.lib.tdmpc2_plan_bind_encoder(A._h, 0, A.encoder_layers, *(native._ptr(x) for x in t), int(t[0].shape[0]), int(t[0].shape[1]),
+                                            A._stream()))
+    after = A.export_packed()
+    assert _diff_owners(before, after, cfg, True) == {"encoder"}
+    F = _planner(c, path, prec)
+    _bind(F, mixed)
+    assert after == F.export_packed()
+    A.close()
+    F.close()
+
+
+@pytest.mark.parametrize(**ONE_LAYER)
+def test_policy_bind_alone_moves_the_copy_only(name, path, prec):
+    c = _case(name)
+    cfg, sd = c["cfg"], _sd(c)
+    A, F = _planner(c, path, prec), _planner(c, path, prec)
+    _bind(A, sd)  # `_pi` is packed here ...
+    A.bind_policy(sd)
+    blob = A.export_packed()
+    z = torch.as_tensor(c["z0"]).to(dev())
+    eps = torch.randn(z.shape[0], cfg.action_dim, generator=torch.Generator().manual_seed(2)).to(dev())
+    before = A.pi(z, eps=eps)[0].clone()
+    new = _sd(c)
+    _perturb(new, 3, scale=0.05)
+    A.bind_policy(new)  # ... and only the prior's fp32 copy follows the new tensors
+    assert A.export_packed() == blob
+    _bind(F, new)
+    F.bind_policy(new)
+    (aa, ia), (af, i_f) = A.pi(z, eps=eps), F.pi(z, eps=eps)
+    assert torch.equal(aa, af) and not torch.equal(aa, before)
+    for k in ("mean", "log_std", "entropy", "scaled_entropy"):
+        assert torch.equal(ia[k], i_f[k]), k
+    A.close()
+    F.close()
 
 
 # ---------------------------------------------------------------- 2. the policy prior's fp32 copy

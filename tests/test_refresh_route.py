@@ -42,6 +42,21 @@ def test_soft_update_costs_a_one_net_refresh(lib):
     assert m.route(lib, 0, m.TQ, lerp=1)["ops"] == [m.SCAN, m.PACK]           # exact fp32: the scan launch only lerps
 
 
+def test_one_layer_binds(lib):
+    """tdmpc2_plan_bind_weights names one net (one layer of it): it routes as a one-net table does.  tdmpc2_plan_bind_encoder is
+    the encoder alone.  tdmpc2_plan_bind_policy is a policy-copy transpose with no net named: one pack launch, whatever the
+    arithmetic, and the copy is touched although TDMPC2_NET_PI is not in `nets`."""
+    for net in (m.DYN, m.REW, m.PI, m.TERM, m.Q, m.TQ):
+        assert m.route(lib, 1, net)["ops"] == [m.RESET, m.SCAN, m.SCALES, m.PACK]
+        assert m.route(lib, 0, net)["ops"] == [m.PACK]
+    for split, nq, ep in itertools.product((1, 0), (2, 5, 8), (0, 1)):
+        r = m.route(lib, split, 0, policy_alone=1, num_q=nq, episodic=ep)
+        assert r["ops"] == [m.PACK] and (r["nets"], r["enc_layers"], r["policy_copy"]) == (0, 0, 1)
+        assert m.route(lib, split, 0, enc_layers=1, num_q=nq, episodic=ep)["ops"] == [m.PACK]
+    assert m.route(lib, 1, 0, policy_copy=1)["ops"] == []                      # the table's flag alone still names nothing
+    assert m.route(lib, 1, m.Q, policy_copy=1, policy_alone=0)["policy_copy"] == 0
+
+
 def test_grids(lib):
     assert [lib.scan_wblocks(n) for n in (0, 1, 4096, 4097, 512 * 4096, 10 ** 9)] == [1, 1, 1, 2, 512, 512]
     assert lib.pack_blocks(16, 528, 0) == 16 * 5 + 1 and lib.pack_blocks(16, 512, 64) == 16 * 4 + 1 + 16
