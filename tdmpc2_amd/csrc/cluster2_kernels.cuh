@@ -42,7 +42,7 @@ __device__ __forceinline__ void cl2_wait_peer(const CT &c, ClState &x, const uns
 }
 
 template <int APAD>
-__global__ __launch_bounds__(NTHREADS, 2) void ks_rollout_cl2(RolloutParamsT<NetS> p) {
+__global__ __launch_bounds__(NTHREADS, 2) void ks_rollout_cl2(RolloutParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ int s_is_last, s_dead, s_fast;
     typedef CtxT<APAD, 1, 8, 0> CT;

@@ -431,7 +431,7 @@ __device__ __forceinline__ float cl_head_term(const CT &c, ClState &x, const Lay
 }
 
 template <int APAD, int EP>
-__global__ __launch_bounds__(NTHREADS, 2) void ks_rollout_cl(RolloutParamsT<NetS> p) {
+__global__ __launch_bounds__(NTHREADS, 2) void ks_rollout_cl(RolloutParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ int s_is_last, s_dead, s_fast;
     typedef CtxT<APAD, 1, 8, 0> CT;

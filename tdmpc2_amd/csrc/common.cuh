@@ -15,6 +15,7 @@
 #include "../../include/tdmpc2_plan.h"
 #include "layer_route.h"  // GBM and the other tile constants the layered family's routes share with its kernels
 #include "plan_layout.h"  // ROWS, WIDTH, MAXQ, MAXH, GBK, BE_*, CL* : the constants the handle's buffers are sized with
+#include "fused_route.h"  // the fused family's launch routes; refit_lds_bytes / refit_threads (both families)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -55,7 +56,7 @@ struct NetS {
     LayerS l[3];
 };
 
-// ---------------------------------------------------------------- kernel parameter blocks (NET = NetS, fused_kernels.cuh)
+// ---------------------------------------------------------------- kernel parameter blocks (fused_kernels.cuh)
 // elite select + refit (tdmpc2/tdmpc2.py:184-206): refit_plan() below
 // A bounded inter-workgroup wait gave up.  The handle's host-mapped line: word 0 = "the call in flight is invalid" -- read by the
 // call's own last kernel (refit_plan's final pick, l_value_head), cleared IN STREAM ORDER at the start of the next call, never by
@@ -134,14 +135,13 @@ struct RefitParams {
     float *dbg_std; long dbg_std_es;
 };
 
-template <class NET>
-struct RolloutParamsT {
+struct RolloutParams {
     int E, N, H, A, Apad, P, stride, tiles, nq, num_bins, multitask, given_actions, iter, iters_total;
     int tile_off;  // first row tile of the range this launch covers (tiles = tiles in the range)
     int nnets;  // vectors per plan in `beff`
     float log_std_min, log_std_dif;
-    NET dyn, rew, pi, term;
-    NET q[MAXQ];
+    NetS dyn, rew, pi, term;
+    NetS q[MAXQ];
     const float *bins;
     const float *z0;        // [E,L]
     const float *beff;      // [E,nnets,WIDTH] effective first-layer biases (multitask) or null
@@ -184,12 +184,11 @@ struct RolloutParamsT {
 };
 
 // pi + two Q heads on a batch of latent rows (fused_kernels.cuh: ks_value)
-template <class NET>
-struct ValueParamsT {
+struct ValueParams {
     int rows, A, Apad, nq, num_bins, reduce_min;
     float log_std_min, log_std_dif, discount;
-    NET pi;
-    NET q[MAXQ];
+    NetS pi;
+    NetS q[MAXQ];
     const float *bins;
     const float *z;        // [rows, L]
     const float *pi_eps;   // [rows, A] or null (Philox)
@@ -208,8 +207,7 @@ struct ValueParamsT {
 };
 
 // ks_value_ent: the same rows with the policy head's entropy terms (tdmpc2_plan_policy_loss)
-template <class NET>
-struct ValueEntParamsT : ValueParamsT<NET> {
+struct ValueEntParams : ValueParams {
     float *entropy, *scaled_entropy;  // [rows] each
     int task_mod;                     // multitask: task of row r = task_ids[r % task_mod] (rows = [steps + 1, B], task_ids [B])
 };
@@ -297,12 +295,11 @@ __device__ __forceinline__ void rng_normal2(unsigned long long seed, unsigned ca
 // per-plan setup: (1) effective first-layer biases b + W[:, L:L+T] . task_emb (multitask); (2) cvec = z0-part (+ bias) of
 // the reward / dynamics first layers (all rows share z0 at t = 0, tdmpc2/tdmpc2.py:163); (3) mean / std initialisation
 // and warm start (tdmpc2.py:164-167)
-template <class NET>
-struct SetupParamsT {
+struct SetupParams {
     int E, H, A, T, multitask, nq, nnets, stride;
     float max_std;
-    NET dyn, rew, pi;
-    NET q[MAXQ];
+    NetS dyn, rew, pi;
+    NetS q[MAXQ];
     const float *wemb[3 + MAXQ];  // [out=WIDTH][T] task-embedding columns of each first layer
     const float *z0, *task_emb, *prev_mean;
     const unsigned char *t0;
@@ -316,11 +313,10 @@ struct SetupParamsT {
 };
 
 // policy-prior trajectories (tdmpc2/tdmpc2.py:154-160): rows < P of one tile per plan
-template <class NET>
-struct PiTrajParamsT {
+struct PiTrajParams {
     int E, N, H, A, Apad, P, stride, multitask, nnets;
     float log_std_min, log_std_dif;
-    NET dyn, pi;
+    NetS dyn, pi;
     const float *z0, *beff, *act_mask;
     const float *pi_traj_eps;  // [E,H,P,A] or null
     unsigned long long seed;
@@ -331,17 +327,7 @@ struct PiTrajParamsT {
 };
 
 // ================================================================ kernel: elite select + refit (struct RefitParams: above)
-// dynamic LDS of the refit; `stage` out: whether the K x H x A elite actions fit next to the rest (they are then gathered
-// by the whole workgroup in one round of loads instead of 2 K dependent global loads per (t, a) thread: 35 -> 12 us)
-inline size_t refit_lds_bytes(int N, int K, int H, int A, int *stage, size_t budget = 48 * 1024) {
-    size_t M = 64;
-    while (M < (size_t)N) M <<= 1;  // sort keys: 8 bytes per padded sample
-    const size_t base = (2 * M + 3 * (size_t)K + 4 * H * A + 48) * 4 + 64;
-    const size_t elite = (size_t)K * H * A * 4;
-    *stage = base + elite <= budget;
-    return *stage ? base + elite : base;
-}
-
+// (its dynamic LDS and workgroup size: refit_lds_bytes / refit_threads of fused_route.h)
 
 // block-wide sum / max over `n` floats in LDS: strided thread-local partials, wavefront shuffle reduction, one LDS slot per
 // wave, every thread reads the slots back (fixed order -> deterministic, the same value in every thread)
@@ -654,14 +640,6 @@ __device__ __forceinline__ void refit_plan(const RefitParams &p, int e, float *s
         p.prev_mean[(size_t)e * p.H * p.A + idx] = smean[idx];  // _prev_mean.copy_(mean) (tdmpc2.py:205)
     RT_MARK(6)
 }
-
-// threads of a k_refit workgroup: the sort width (one key per thread)
-inline int refit_threads(int N) {
-    int M = 64;
-    while (M < N) M <<= 1;
-    return M;
-}
-
 
 // beff_tab[task][net][WIDTH] = b + W[:, L:L+T] . task_emb[task] for the policy and the Q heads (online or target):
 // the per-task effective first-layer biases ks_value indexes per row.  grid = n_tasks, block = WIDTH threads.

@@ -990,7 +990,7 @@ __device__ __forceinline__ void dump_tile_s(const CT &c, float *trace, int nslot
 
 // ================================================================ kernel: per-plan setup
 template <int APAD, int AR>
-__global__ __launch_bounds__(NTHREADS, 2) void ks_setup(SetupParamsT<NetS> p) {
+__global__ __launch_bounds__(NTHREADS, 2) void ks_setup(SetupParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int e = blockIdx.x, tid = threadIdx.x;
     typedef CtxT<APAD, 2, 8, AR> CT;  // 64 rows, 8 waves
@@ -1046,7 +1046,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void ks_setup(SetupParamsT<NetS> p) {
 // ================================================================ kernel: policy-prior trajectories
 // ST = 1 (one 32-row tile) when num_pi_trajs <= 32 -- the reference's 24 -- else 2.
 template <int APAD, int ST, int AR>
-__global__ __launch_bounds__(NTHREADS, 2) void ks_pitraj(PiTrajParamsT<NetS> p) {
+__global__ __launch_bounds__(NTHREADS, 2) void ks_pitraj(PiTrajParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int e = blockIdx.x, tid = threadIdx.x;
     typedef CtxT<APAD, ST, 8, AR> CT;
@@ -1140,7 +1140,7 @@ __device__ __forceinline__ void first_layers_s(const CT &c, const LayerS &la, co
 // (Registers: the 8-wave instantiations fill the 256-VGPR budget of two waves per SIMD -- 65 spilled, none inside a k-loop or
 // an epilogue; dropping the second launch-bounds argument changes nothing: tools/kmeta.py, profiles/README.md r4w.)
 template <int APAD, int ST, int NW, int AR, int EP, int TR = 0>
-__global__ __launch_bounds__(64 * NW, 2) void ks_rollout(RolloutParamsT<NetS> p) {
+__global__ __launch_bounds__(64 * NW, 2) void ks_rollout(RolloutParams p) {
     constexpr bool TRACE = TR || EP;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ int s_is_last;
@@ -1380,7 +1380,7 @@ __global__ __launch_bounds__(64 * NW, 2) void ks_rollout(RolloutParamsT<NetS> p)
 // batches carry one task per row (world_model.py:95-97): the first-layer biases b + W[:, L:L+T] . task_emb come from a
 // per-task table (`beff_tab`, built by ks_task_bias) indexed with the row's task, and so do the action mask and discount.
 template <int APAD, int AR>
-__global__ __launch_bounds__(NTHREADS, 2) void ks_value(ValueParamsT<NetS> p) {
+__global__ __launch_bounds__(NTHREADS, 2) void ks_value(ValueParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x;
     typedef CtxT<APAD, 2, 8, AR> CT;

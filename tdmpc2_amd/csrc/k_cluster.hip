@@ -13,11 +13,11 @@ namespace {
 
 constexpr int AP = TU_APAD;
 
-void rollout_cl_(int ep, const RolloutParamsT<NetS> &p, int grid, size_t lds, hipStream_t st) {
+void rollout_cl_(int ep, const RolloutParams &p, int grid, size_t lds, hipStream_t st) {
     if (ep) hipLaunchKernelGGL((ks_rollout_cl<AP, 1>), dim3(grid), dim3(NTHREADS), lds, st, p);
     else hipLaunchKernelGGL((ks_rollout_cl<AP, 0>), dim3(grid), dim3(NTHREADS), lds, st, p);
 }
-void rollout_cl2_(const RolloutParamsT<NetS> &p, int grid, size_t lds, hipStream_t st) {
+void rollout_cl2_(const RolloutParams &p, int grid, size_t lds, hipStream_t st) {
     hipLaunchKernelGGL((ks_rollout_cl2<AP>), dim3(grid), dim3(NTHREADS), lds, st, p);
 }
 int set_lds_(int episodic, size_t b) {

@@ -12,11 +12,11 @@ namespace {
 
 constexpr int AP = TU_APAD;
 
-void setup_(int ar, const SetupParamsT<NetS> &p, int E, size_t lds, hipStream_t st) {
+void setup_(int ar, const SetupParams &p, int E, size_t lds, hipStream_t st) {
     if (ar) hipLaunchKernelGGL((ks_setup<AP, 1>), dim3(E), dim3(NTHREADS), lds, st, p);
     else hipLaunchKernelGGL((ks_setup<AP, 0>), dim3(E), dim3(NTHREADS), lds, st, p);
 }
-void pitraj_(int ar, int nst, const PiTrajParamsT<NetS> &p, int E, size_t lds, hipStream_t st) {
+void pitraj_(int ar, int nst, const PiTrajParams &p, int E, size_t lds, hipStream_t st) {
     if (nst == 1) {
         if (ar) hipLaunchKernelGGL((ks_pitraj<AP, 1, 1>), dim3(E), dim3(NTHREADS), lds, st, p);
         else hipLaunchKernelGGL((ks_pitraj<AP, 1, 0>), dim3(E), dim3(NTHREADS), lds, st, p);
@@ -26,7 +26,7 @@ void pitraj_(int ar, int nst, const PiTrajParamsT<NetS> &p, int E, size_t lds, h
     }
 }
 template <int AR>
-void rollout_ar(int nst, int ep, int tracing, const RolloutParamsT<NetS> &p, int grid, size_t lds, hipStream_t st) {
+void rollout_ar(int nst, int ep, int tracing, const RolloutParams &p, int grid, size_t lds, hipStream_t st) {
     if (nst == 2) {
         if (ep) hipLaunchKernelGGL((ks_rollout<AP, 2, 8, AR, 1>), dim3(grid), dim3(NTHREADS), lds, st, p);
         else if (tracing) hipLaunchKernelGGL((ks_rollout<AP, 2, 8, AR, 0, 1>), dim3(grid), dim3(NTHREADS), lds, st, p);
@@ -36,11 +36,11 @@ void rollout_ar(int nst, int ep, int tracing, const RolloutParamsT<NetS> &p, int
         else hipLaunchKernelGGL((ks_rollout<AP, 1, 8, AR, 0>), dim3(grid), dim3(NTHREADS), lds, st, p);
     }
 }
-void rollout_(int ar, int nst, int ep, int tracing, const RolloutParamsT<NetS> &p, int grid, size_t lds, hipStream_t st) {
+void rollout_(int ar, int nst, int ep, int tracing, const RolloutParams &p, int grid, size_t lds, hipStream_t st) {
     if (ar) rollout_ar<1>(nst, ep, tracing, p, grid, lds, st);
     else rollout_ar<0>(nst, ep, tracing, p, grid, lds, st);
 }
-void value_(int ar, const ValueParamsT<NetS> &p, int grid, size_t lds, hipStream_t st) {
+void value_(int ar, const ValueParams &p, int grid, size_t lds, hipStream_t st) {
     if (ar) hipLaunchKernelGGL((ks_value<AP, 1>), dim3(grid), dim3(NTHREADS), lds, st, p);
     else hipLaunchKernelGGL((ks_value<AP, 0>), dim3(grid), dim3(NTHREADS), lds, st, p);
 }

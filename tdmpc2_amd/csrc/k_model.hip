@@ -13,11 +13,11 @@ namespace {
 
 constexpr int AP = TU_APAD;
 
-void dyn_(int ar, const ModelParamsT<NetS> &p, int gx, size_t lds, hipStream_t st) {
+void dyn_(int ar, const ModelParams &p, int gx, size_t lds, hipStream_t st) {
     if (ar) hipLaunchKernelGGL((ks_value_roll<AP, 1>), dim3(gx), dim3(NTHREADS), lds, st, p);
     else hipLaunchKernelGGL((ks_value_roll<AP, 0>), dim3(gx), dim3(NTHREADS), lds, st, p);
 }
-void chain_(int ar, const ModelParamsT<NetS> &p, int gx, int gy, int gz, size_t lds, hipStream_t st) {
+void chain_(int ar, const ModelParams &p, int gx, int gy, int gz, size_t lds, hipStream_t st) {
     if (ar) hipLaunchKernelGGL((ks_value_chain<AP, 1>), dim3(gx, gy, gz), dim3(NTHREADS), lds, st, p);
     else hipLaunchKernelGGL((ks_value_chain<AP, 0>), dim3(gx, gy, gz), dim3(NTHREADS), lds, st, p);
 }

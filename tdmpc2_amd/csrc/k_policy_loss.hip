@@ -11,7 +11,7 @@ namespace {
 
 constexpr int AP = TU_APAD;
 
-void value_ent_(int ar, const ValueEntParamsT<NetS> &p, int grid, size_t lds, hipStream_t st) {
+void value_ent_(int ar, const ValueEntParams &p, int grid, size_t lds, hipStream_t st) {
     if (ar) hipLaunchKernelGGL((ks_value_ent<AP, 1>), dim3(grid), dim3(NTHREADS), lds, st, p);
     else hipLaunchKernelGGL((ks_value_ent<AP, 0>), dim3(grid), dim3(NTHREADS), lds, st, p);
 }

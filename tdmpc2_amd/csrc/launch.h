@@ -59,18 +59,18 @@ namespace tdk {
 // ---- fused 512-wide family: one table per action padding (k_fused.hip, compiled once per -DTU_APAD=16|32|48|64).
 // ar: 0 = f16x2 split, 1 = exact fp32 MFMA; nst: 32-row sample tiles per workgroup (1 | 2).
 struct FusedOps {
-    void (*setup)(int ar, const SetupParamsT<NetS> &p, int E, size_t lds, hipStream_t st);
-    void (*pitraj)(int ar, int nst, const PiTrajParamsT<NetS> &p, int E, size_t lds, hipStream_t st);
-    void (*rollout)(int ar, int nst, int ep, int tracing, const RolloutParamsT<NetS> &p, int grid, size_t lds, hipStream_t st);
-    void (*value)(int ar, const ValueParamsT<NetS> &p, int grid, size_t lds, hipStream_t st);
+    void (*setup)(int ar, const SetupParams &p, int E, size_t lds, hipStream_t st);
+    void (*pitraj)(int ar, int nst, const PiTrajParams &p, int E, size_t lds, hipStream_t st);
+    void (*rollout)(int ar, int nst, int ep, int tracing, const RolloutParams &p, int grid, size_t lds, hipStream_t st);
+    void (*value)(int ar, const ValueParams &p, int grid, size_t lds, hipStream_t st);
     int (*set_lds)(int ar, int episodic, size_t lds_bytes);  // hipFuncAttributeMaxDynamicSharedMemorySize of every instantiation
 };
 // ---- cluster path of the fused family (k_cluster.hip, per action padding; split arithmetic only)
 struct ClusterOps {
-    void (*rollout_cl)(int ep, const RolloutParamsT<NetS> &p, int grid, size_t lds, hipStream_t st);
+    void (*rollout_cl)(int ep, const RolloutParams &p, int grid, size_t lds, hipStream_t st);
     int (*set_lds)(int episodic, size_t lds_bytes);
     // two clusters per 32-row tile (reward chain beside the dynamics chain): single non-episodic plans, every launch (launch 0 with the policy-prior fold)
-    void (*rollout_cl2)(const RolloutParamsT<NetS> &p, int grid, size_t lds, hipStream_t st);
+    void (*rollout_cl2)(const RolloutParams &p, int grid, size_t lds, hipStream_t st);
 };
 // (accessor functions, not global tables: hipcc would emit a constant-initialised table on the device side as well)
 const FusedOps &fused_ops_ap16(); const FusedOps &fused_ops_ap32(); const FusedOps &fused_ops_ap48(); const FusedOps &fused_ops_ap64();
@@ -84,6 +84,36 @@ inline int set_lds(K kernel, size_t bytes) {
 
 // ---- elite selection + refit, one workgroup per plan (k_refit, tdmpc2_plan.hip)
 int launch_refit(const RefitParams &fp, int E, int N, size_t lds, hipStream_t st);
+// The refit of CEM iteration `it` of a plan (both families, whole and sharded plans).  err: the handle's error word where the
+// plan ran kernels with bounded waits (the final pick then returns NaN and keeps prev_mean), else null.
+inline void fill_refit(const tdmpc2_plan *h, RefitParams &fp, int E, int it, int eval_mode, float *value, const float *act_mask,
+                       const tdmpc2_noise *tape, uint64_t seed, unsigned call, float *prev_mean, float *action,
+                       const tdmpc2_debug *dbg, int stage, const unsigned int *err) {
+    const tdmpc2_plan_cfg &c = h->cfg;
+    const int H = c.horizon, N = c.num_samples, A = c.action_dim, K = c.num_elites, I = c.iterations;
+    fp = RefitParams{};
+    fp.Nvalid = c.num_valid_samples; fp.E = E; fp.N = N; fp.H = H; fp.A = A; fp.K = K; fp.iter = it; fp.last = (it == I - 1); fp.eval_mode = eval_mode; fp.stage = stage;
+    fp.temperature = c.temperature; fp.min_std = c.min_std; fp.max_std = c.max_std;
+    fp.value = value; fp.actions = h->actions; fp.act_mask = act_mask; fp.mean = h->mean; fp.std = h->std;
+    fp.gumbel_exp = tape ? tape->gumbel_exp : nullptr; fp.final_eps = tape ? tape->final_eps : nullptr;
+    fp.seed = seed; fp.call = call; fp.prev_mean = prev_mean; fp.action = action;
+    fp.err = err;
+    if (dbg) {
+        if (dbg->value) { fp.dbg_value = dbg->value + (size_t)it * N; fp.dbg_value_es = (long)I * N; }
+        if (dbg->elite_idx) { fp.dbg_idx = dbg->elite_idx + (size_t)it * K; fp.dbg_idx_es = (long)I * K; }
+        if (dbg->score) { fp.dbg_score = dbg->score + (size_t)it * K; fp.dbg_score_es = (long)I * K; }
+        if (dbg->mean) { fp.dbg_mean = dbg->mean + (size_t)it * H * A; fp.dbg_mean_es = (long)I * H * A; }
+        if (dbg->std) { fp.dbg_std = dbg->std + (size_t)it * H * A; fp.dbg_std_es = (long)I * H * A; }
+    }
+}
+// the per-iteration action dump of a debug call: h->actions [E,H,N,A] -> dbg->actions [E,I,H,N,A] at iteration `it`
+inline int dump_actions(const tdmpc2_plan *h, const tdmpc2_debug *dbg, int E, int it, hipStream_t st) {
+    if (!dbg || !dbg->actions) return 0;
+    const size_t hna = (size_t)h->cfg.horizon * h->cfg.num_samples * h->cfg.action_dim;
+    HIP_TRY(hipMemcpy2DAsync(dbg->actions + (size_t)it * hna, (size_t)h->cfg.iterations * hna * 4, h->actions, hna * 4, hna * 4, E,
+                             hipMemcpyDeviceToDevice, st));
+    return 0;
+}
 
 // ---- layer-at-a-time family (k_layered.hip: kernels + their host orchestration, layered_host.cuh)
 int lay_setup(tdmpc2_plan *h, hipStream_t st, int E, const float *task_emb, const float *prev_mean, const unsigned char *t0,
@@ -112,8 +142,8 @@ int lay_set_qidx(tdmpc2_plan *h, hipStream_t st, int E, const int *qidx, long st
 // ---- model rollout / losses (k_model.hip per action padding: the fused family's kernels; its generic unit: the row kernels;
 // k_layered.hip: the layered family's stages).  Routes: model_route.h.
 struct ModelOps {
-    void (*dyn)(int ar, const ModelParamsT<NetS> &p, int gx, size_t lds, hipStream_t st);
-    void (*chain)(int ar, const ModelParamsT<NetS> &p, int gx, int gy, int gz, size_t lds, hipStream_t st);
+    void (*dyn)(int ar, const ModelParams &p, int gx, size_t lds, hipStream_t st);
+    void (*chain)(int ar, const ModelParams &p, int gx, int gy, int gz, size_t lds, hipStream_t st);
     int (*set_lds)(int ar, size_t lds_bytes);
 };
 const ModelOps &model_ops_ap16(); const ModelOps &model_ops_ap32(); const ModelOps &model_ops_ap48(); const ModelOps &model_ops_ap64();
@@ -128,7 +158,7 @@ int lay_model(tdmpc2_plan *h, hipStream_t st, const ModelRoute &r, int B, int H,
 // ---- policy loss (k_policy_loss.hip per action padding: ks_value_ent of the fused family; its generic unit: the one-workgroup kernels)
 #include "policy_loss_params.h"
 struct PolicyLossOps {
-    void (*value_ent)(int ar, const ValueEntParamsT<NetS> &p, int grid, size_t lds, hipStream_t st);
+    void (*value_ent)(int ar, const ValueEntParams &p, int grid, size_t lds, hipStream_t st);
     int (*set_lds)(int ar, size_t lds_bytes);
 };
 const PolicyLossOps &policy_loss_ops_ap16(); const PolicyLossOps &policy_loss_ops_ap32(); const PolicyLossOps &policy_loss_ops_ap48(); const PolicyLossOps &policy_loss_ops_ap64();

@@ -816,23 +816,11 @@ int lay_run(tdmpc2_plan *h, hipStream_t st, int E, const float *z0, const float 
             HIP_TRY(hipEventRecord(h->ev[h->ev_used + 1], st));
             h->ev_used += 2;
         }
-        if (dbg && dbg->actions)
-            HIP_TRY(hipMemcpy2DAsync(dbg->actions + (size_t)it * H * N * A, (size_t)I * H * N * A * 4, h->actions,
-                                     (size_t)H * N * A * 4, (size_t)H * N * A * 4, E, hipMemcpyDeviceToDevice, st));
-        RefitParams fp{};
-        fp.Nvalid = c.num_valid_samples; fp.E = E; fp.N = N; fp.H = H; fp.A = A; fp.K = K; fp.iter = it; fp.last = (it == I - 1); fp.eval_mode = eval_mode; fp.stage = refit_stage;
-        fp.temperature = c.temperature; fp.min_std = c.min_std; fp.max_std = c.max_std;
-        fp.value = h->value; fp.actions = h->actions; fp.act_mask = act_mask; fp.mean = h->mean; fp.std = h->std;
-        fp.gumbel_exp = tape ? tape->gumbel_exp : nullptr; fp.final_eps = tape ? tape->final_eps : nullptr;
-        fp.seed = seed; fp.call = call; fp.prev_mean = prev_mean; fp.action = action;
-        fp.err = h->lay.fuse_ln ? h->cl_err_dev : nullptr;  // a fused-epilogue wait that gave up: NaN action, prev_mean kept
-        if (dbg) {
-            if (dbg->value) { fp.dbg_value = dbg->value + (size_t)it * N; fp.dbg_value_es = (long)I * N; }
-            if (dbg->elite_idx) { fp.dbg_idx = dbg->elite_idx + (size_t)it * K; fp.dbg_idx_es = (long)I * K; }
-            if (dbg->score) { fp.dbg_score = dbg->score + (size_t)it * K; fp.dbg_score_es = (long)I * K; }
-            if (dbg->mean) { fp.dbg_mean = dbg->mean + (size_t)it * H * A; fp.dbg_mean_es = (long)I * H * A; }
-            if (dbg->std) { fp.dbg_std = dbg->std + (size_t)it * H * A; fp.dbg_std_es = (long)I * H * A; }
-        }
+        if ((rc = dump_actions(h, dbg, E, it, st))) return rc;
+        RefitParams fp;
+        // (err: a fused-epilogue wait that gave up: NaN action, prev_mean kept)
+        fill_refit(h, fp, E, it, eval_mode, h->value, act_mask, tape, seed, call, prev_mean, action, dbg, refit_stage,
+                   h->lay.fuse_ln ? h->cl_err_dev : nullptr);
         if ((rc = launch_refit(fp, E, N, refit_lds, st))) return rc;
     }
     return TDMPC2_OK;

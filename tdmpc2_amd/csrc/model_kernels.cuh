@@ -66,7 +66,7 @@ __device__ __forceinline__ void model_first_layer_s(const CT &c, const LayerS &l
 }
 
 template <int APAD, int AR>
-__global__ __launch_bounds__(NTHREADS, 2) void ks_value_roll(ModelParamsT<NetS> p) {
+__global__ __launch_bounds__(NTHREADS, 2) void ks_value_roll(ModelParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x;
     typedef CtxT<APAD, 2, 8, AR> CT;
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void ks_value_roll(ModelParamsT<NetS> 
 }
 
 template <int APAD, int AR>
-__global__ __launch_bounds__(NTHREADS, 2) void ks_value_chain(ModelParamsT<NetS> p) {
+__global__ __launch_bounds__(NTHREADS, 2) void ks_value_chain(ModelParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x;
     typedef CtxT<APAD, 2, 8, AR> CT;

@@ -22,11 +22,10 @@ struct ModelOutArgs {
 };
 
 // fused family: ks_value_roll (grid: row tiles) and ks_value_chain (grid: row tiles x steps x chains)
-template <class NET>
-struct ModelParamsT {
+struct ModelParams {
     int B, H, A, Apad, nq, nnets, steps;
-    NET dyn, rew, term;
-    NET q[MAXQ];
+    NetS dyn, rew, term;
+    NetS q[MAXQ];
     const float *z0;        // [B, L]
     const float *actions;   // [H, B, A]
     float *zs;              // [H + 1, B, L]: the caller's output or the handle's workspace; zs[0] is written by the host

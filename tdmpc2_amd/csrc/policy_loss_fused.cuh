@@ -55,7 +55,7 @@ __device__ __forceinline__ void head_pi_rows_ent_s(const CT &c, int A, int Apad,
 }
 
 template <int APAD, int AR>
-__global__ __launch_bounds__(NTHREADS, 2) void ks_value_ent(ValueEntParamsT<NetS> p) {
+__global__ __launch_bounds__(NTHREADS, 2) void ks_value_ent(ValueEntParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x;
     typedef CtxT<APAD, 2, 8, AR> CT;

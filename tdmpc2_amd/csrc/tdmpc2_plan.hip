@@ -304,8 +304,7 @@ int ksws_ensure(tdmpc2_plan *h, int mode) {
     return 0;
 }
 
-template <class NET> NET to_dev(const HostNet &n);
-template <> NetS to_dev<NetS>(const HostNet &n) {  // split: hi/lo f16 packing + per-matrix scale; exact fp32: fp32 packing, scale 1
+NetS to_dev(const HostNet &n) {  // split: hi/lo f16 packing + per-matrix scale; exact fp32: fp32 packing, scale 1
     NetS w;
     for (int i = 0; i < 3; ++i)
         w.l[i] = LayerS{n.l[i].wps ? n.l[i].wps : reinterpret_cast<const _Float16 *>(n.l[i].wp), n.l[i].bias, n.l[i].g, n.l[i].b,
@@ -340,107 +339,40 @@ int check_ready(tdmpc2_plan *h) {
 
 // The fused kernels are instantiated per action padding (compile-time LDS strides) and arithmetic (AR 0 = f16x2 split,
 // 1 = exact fp32 MFMA); ks_rollout / ks_pitraj also per workgroup geometry -- one translation unit per padding (k_fused.hip,
-// k_cluster.hip), reached through the tables of launch.h.
-#ifndef TDMPC2_DEFAULT_THROUGHPUT_ST
-#define TDMPC2_DEFAULT_THROUGHPUT_ST 2  // sample tiles per workgroup when a call has enough plans to fill the chip
-#endif
-const ModelOps &model_ops(int apad) {
+// k_cluster.hip, k_model.hip, k_policy_loss.hip), reached through the tables of launch.h.  Experiment builds (tools/ablate.sh,
+// TDMPC2_ONLY_APAD) hold one action padding only, a quarter of the compile time.
+#define TDK_CAT_(a, b) a##b
+#define TDK_CAT(a, b) TDK_CAT_(a, b)
 #ifdef TDMPC2_ONLY_APAD
-#define TDK_MOPS_CAT_(a, b) a##b
-#define TDK_MOPS_CAT(a, b) TDK_MOPS_CAT_(a, b)
-    (void)apad;
-    return TDK_MOPS_CAT(model_ops_ap, TDMPC2_ONLY_APAD)();
+#define TDK_OPS_BY_APAD(OPS, name) \
+    const OPS &name(int) { return TDK_CAT(name##_ap, TDMPC2_ONLY_APAD)(); }
 #else
-    switch (apad) {
-        case 16: return model_ops_ap16();
-        case 32: return model_ops_ap32();
-        case 48: return model_ops_ap48();
-        default: return model_ops_ap64();
+#define TDK_OPS_BY_APAD(OPS, name)         \
+    const OPS &name(int apad) {            \
+        switch (apad) {                    \
+            case 16: return name##_ap16(); \
+            case 32: return name##_ap32(); \
+            case 48: return name##_ap48(); \
+            default: return name##_ap64(); \
+        }                                  \
     }
 #endif
+TDK_OPS_BY_APAD(ModelOps, model_ops)
+TDK_OPS_BY_APAD(PolicyLossOps, policy_loss_ops)
+TDK_OPS_BY_APAD(FusedOps, fused_ops)
+TDK_OPS_BY_APAD(ClusterOps, cluster_ops)
+
+// What fused_route.h decides from: the handle's scalars and the call's plan count.
+FusedIn fused_in(const tdmpc2_plan *h, int E) {
+    const tdmpc2_plan_cfg &c = h->cfg;
+    FusedIn in{};
+    in.E = E; in.tiles = h->tiles; in.N = c.num_samples; in.K = c.num_elites; in.H = c.horizon; in.A = c.action_dim;
+    in.P = c.num_pi_trajs; in.num_cus = h->num_cus; in.cluster_mode = h->cluster_mode; in.cl_max_clusters = h->cl_max_clusters;
+    in.cl2 = h->cl2_xbuf && h->cl2_mode; in.episodic = c.episodic != 0; in.cl_fault = h->cl_fault != 0;
+    in.force_rows = h->force_rows; in.fold_refit = h->fold_refit;
+    in.lds_bytes = h->lds_bytes; in.row_bytes = h->row_bytes; in.cl_lds = h->cl_lds;
+    return in;
 }
-const PolicyLossOps &policy_loss_ops(int apad) {
-#ifdef TDMPC2_ONLY_APAD
-#define TDK_PLOPS_CAT_(a, b) a##b
-#define TDK_PLOPS_CAT(a, b) TDK_PLOPS_CAT_(a, b)
-    (void)apad;
-    return TDK_PLOPS_CAT(policy_loss_ops_ap, TDMPC2_ONLY_APAD)();
-#else
-    switch (apad) {
-        case 16: return policy_loss_ops_ap16();
-        case 32: return policy_loss_ops_ap32();
-        case 48: return policy_loss_ops_ap48();
-        default: return policy_loss_ops_ap64();
-    }
-#endif
-}
-const FusedOps &fused_ops(int apad) {
-#ifdef TDMPC2_ONLY_APAD  // experiment builds (tools/ablate.sh): one action padding only, a quarter of the compile time
-#define TDK_OPS_CAT_(a, b) a##b
-#define TDK_OPS_CAT(a, b) TDK_OPS_CAT_(a, b)
-    (void)apad;
-    return TDK_OPS_CAT(fused_ops_ap, TDMPC2_ONLY_APAD)();
-#else
-    switch (apad) {
-        case 16: return fused_ops_ap16();
-        case 32: return fused_ops_ap32();
-        case 48: return fused_ops_ap48();
-        default: return fused_ops_ap64();
-    }
-#endif
-}
-const ClusterOps &cluster_ops(int apad) {
-#ifdef TDMPC2_ONLY_APAD
-    (void)apad;
-    return TDK_OPS_CAT(cluster_ops_ap, TDMPC2_ONLY_APAD)();
-#else
-    switch (apad) {
-        case 16: return cluster_ops_ap16();
-        case 32: return cluster_ops_ap32();
-        case 48: return cluster_ops_ap48();
-        default: return cluster_ops_ap64();
-    }
-#endif
-}
-template <class NET> struct Kern;
-template <> struct Kern<NetS> {
-    // 32- or 64-row workgroups.  A 64-row workgroup reuses every weight fragment for two row tiles and is the
-    // efficient one when the chip is full; a call with few plans is better served by twice as many 32-row workgroups.
-    // Model: one workgroup per CU at a time, a round of 32-row workgroups takes 0.61 of a round of 64-row ones
-    // (measured, c1: 0.34 vs 0.556 ms); pick the geometry with the shorter sum of rounds (E = 16: +30 %).
-    static int sample_tiles(const tdmpc2_plan *h, int E, bool tracing) {
-        if (tracing) return 2;  // the activation trace is laid out per 64-row tile
-        if (h->force_rows) return h->force_rows / 32;
-        const long cus = plan_cus(h->num_cus);
-        const long w2 = (long)E * h->tiles, w1 = 2 * w2;
-        const long r2 = (w2 + cus - 1) / cus, r1 = (w1 + cus - 1) / cus;
-        return 0.61 * (double)r1 < (double)r2 ? 1 : TDMPC2_DEFAULT_THROUGHPUT_ST;
-    }
-    // Always 8 wavefronts per workgroup.  A 4-wave, 32-row geometry (two workgroups per CU, so that one's VALU epilogue
-    // overlaps the other's MFMA k-loop; the device code is templated for it: CtxT<APAD, 1, 4>) was measured and lost
-    // 5.83 vs 4.88 ms per launch: each weight fragment then feeds one row tile, the k-loop needs 85 B/clk/CU of
-    // fragment loads and becomes L1-bound.
-    static int waves(const tdmpc2_plan *, int, int) { return 8; }
-    static void setup(const tdmpc2_plan *h, const SetupParamsT<NetS> &p, int E, hipStream_t st) {
-        fused_ops(h->Apad).setup(h->split ? 0 : 1, p, E, h->lds_bytes, st);
-    }
-    static void pitraj(const tdmpc2_plan *h, const PiTrajParamsT<NetS> &p, int E, hipStream_t st) {
-        // one 32-row tile holds the policy-prior trajectories when P <= 32 (the reference uses 24)
-        const int nst = p.P <= 32 ? 1 : 2;
-        const size_t lds = nst == 1 ? h->lds_bytes - (size_t)32 * h->row_bytes : h->lds_bytes;
-        fused_ops(h->Apad).pitraj(h->split ? 0 : 1, nst, p, E, lds, st);
-    }
-    static void rollout(const tdmpc2_plan *h, const RolloutParamsT<NetS> &p, int grid, hipStream_t st, int nst, int nw) {
-        (void)nw;
-        const bool tracing = p.trace_tiles || p.trace_scalars;  // (the host forces 64-row workgroups for a trace call)
-        const size_t lds = nst == 2 ? h->lds_bytes : h->lds_bytes - (size_t)32 * h->row_bytes;
-        fused_ops(h->Apad).rollout(h->split ? 0 : 1, nst, h->cfg.episodic != 0, tracing, p, grid, lds, st);
-    }
-    // cluster path: `clusters` row tiles of 32 samples, 8 workgroups each, in groups of 8 clusters (one per XCD)
-    static void rollout_cluster(const tdmpc2_plan *h, const RolloutParamsT<NetS> &p, int clusters, hipStream_t st) {
-        cluster_ops(h->Apad).rollout_cl(h->cfg.episodic != 0, p, (clusters + 7) / 8 * 64, h->cl_lds, st);
-    }
-};
 
 // Cluster launches of different streams are serialised per device: a launch whose workgroups are only partly resident
 // spins on members that wait for a CU, and two such launches could wait for each other.  (Other kernels may share the
@@ -454,44 +386,64 @@ struct ClusterGate {
 };
 ClusterGate g_cluster_gate;
 
-template <class NET>
-int launch_setup(tdmpc2_plan *h, int E, const float *z0, const float *task_emb, const float *prev_mean,
-                 const unsigned char *t0, hipStream_t st, bool skip_cvec = false) {
-    SetupParamsT<NET> p{};
+int launch_setup(tdmpc2_plan *h, const FusedRoute &r, int E, const float *z0, const float *task_emb, const float *prev_mean,
+                 const unsigned char *t0, hipStream_t st) {
+    SetupParams p{};
     p.E = E; p.H = h->cfg.horizon; p.A = h->cfg.action_dim; p.T = h->cfg.task_dim; p.multitask = h->cfg.multitask;
     p.nq = h->cfg.num_q; p.nnets = h->nnets; p.stride = h->stride; p.max_std = h->cfg.max_std;
-    p.dyn = to_dev<NET>(h->dyn); p.rew = to_dev<NET>(h->rew); p.pi = to_dev<NET>(h->pi);
-    for (int i = 0; i < h->cfg.num_q; ++i) p.q[i] = to_dev<NET>(h->q[i]);
+    p.dyn = to_dev(h->dyn); p.rew = to_dev(h->rew); p.pi = to_dev(h->pi);
+    for (int i = 0; i < h->cfg.num_q; ++i) p.q[i] = to_dev(h->q[i]);
     p.wemb[BE_DYN] = h->dyn.l[0].wemb; p.wemb[BE_REW] = h->rew.l[0].wemb; p.wemb[BE_PI] = h->pi.l[0].wemb;
     for (int i = 0; i < h->cfg.num_q; ++i) p.wemb[BE_Q0 + i] = h->q[i].l[0].wemb;
     p.z0 = z0; p.task_emb = task_emb; p.prev_mean = prev_mean; p.t0 = t0;
     p.beff = h->beff; p.cvec = h->cvec; p.mean = h->mean; p.std = h->std;
-    // cluster path: the arrival words of this call's clusters start every plan at zero (phase numbers grow through its launches)
-    p.cl_flags = (h->cl_max_clusters && (long)E * h->tiles * 2 <= h->cl_max_clusters) ? h->cl_flags : nullptr;
+    p.cl_flags = r.arm_cl ? h->cl_flags : nullptr;
     p.cl_flag_words = h->tiles * 2 * CL_FLAG_STRIDE;
-    p.cl2_flags = (p.cl_flags && E == 1 && h->cl2_flags && h->cl2_mode && h->cluster_mode == 2) ? h->cl2_flags : nullptr;
+    p.cl2_flags = r.arm_cl2 ? h->cl2_flags : nullptr;
     p.cl2_flag_words = h->tiles * 4 * CL_FLAG_STRIDE;
-    p.skip_cvec = skip_cvec ? 1 : 0;
+    p.skip_cvec = r.skip_cvec ? 1 : 0;
     p.err_clear = h->cl_err_dev;  // word 0 of the error line back to zero, in stream order (fault_fresh)
-    Kern<NET>::setup(h, p, E, st);
+    fused_ops(h->Apad).setup(h->split ? 0 : 1, p, E, h->lds_bytes, st);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-template <class NET>
-void fill_rollout(tdmpc2_plan *h, RolloutParamsT<NET> &p, int E) {
+// the policy-prior pass of its own (whole plans that do not fold it into the first rollout launch, sharded plans)
+int launch_pitraj(tdmpc2_plan *h, const FusedRoute &r, int E, const float *z0, const float *act_mask, const tdmpc2_noise *tape,
+                  uint64_t seed, unsigned call, hipStream_t st) {
+    const tdmpc2_plan_cfg &c = h->cfg;
+    PiTrajParams p{};
+    p.E = E; p.N = c.num_samples; p.H = c.horizon; p.A = c.action_dim; p.Apad = h->Apad; p.P = c.num_pi_trajs; p.stride = h->stride;
+    p.multitask = c.multitask; p.nnets = h->nnets; p.log_std_min = c.log_std_min; p.log_std_dif = c.log_std_dif;
+    p.dyn = to_dev(h->dyn); p.pi = to_dev(h->pi);
+    p.z0 = z0; p.beff = h->beff; p.act_mask = act_mask; p.pi_traj_eps = tape ? tape->pi_traj_eps : nullptr;
+    p.seed = seed; p.call = call; p.actions = h->actions; p.zscratch = h->zscratch;
+    p.zscratch_estride = (long)h->tiles * ROWS * WIDTH;
+    fused_ops(h->Apad).pitraj(h->split ? 0 : 1, r.pitraj_nst, p, E, r.pitraj_lds, st);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// what every rollout launch of a call shares; the route's row tiles
+void fill_rollout(tdmpc2_plan *h, const FusedRoute &r, RolloutParams &p, int E) {
     const tdmpc2_plan_cfg &c = h->cfg;
     p.E = E; p.N = c.num_samples; p.H = c.horizon; p.A = c.action_dim; p.Apad = h->Apad; p.P = c.num_pi_trajs;
-    p.stride = h->stride; p.tiles = h->tiles; p.nq = c.num_q; p.num_bins = c.num_bins; p.multitask = c.multitask;
+    p.stride = h->stride; p.tiles = r.tiles; p.tile_off = r.tile_off; p.nq = c.num_q; p.num_bins = c.num_bins; p.multitask = c.multitask;
     p.nnets = h->nnets; p.log_std_min = c.log_std_min; p.log_std_dif = c.log_std_dif;
-    p.dyn = to_dev<NET>(h->dyn); p.rew = to_dev<NET>(h->rew); p.pi = to_dev<NET>(h->pi);
-    if (c.episodic) p.term = to_dev<NET>(h->term);
-    for (int i = 0; i < c.num_q; ++i) p.q[i] = to_dev<NET>(h->q[i]);
+    p.dyn = to_dev(h->dyn); p.rew = to_dev(h->rew); p.pi = to_dev(h->pi);
+    if (c.episodic) p.term = to_dev(h->term);
+    for (int i = 0; i < c.num_q; ++i) p.q[i] = to_dev(h->q[i]);
     p.bins = h->bins; p.beff = h->beff; p.cvec = h->cvec; p.mean = h->mean; p.std = h->std;
     p.actions = h->actions; p.value = h->value; p.zscratch = h->zscratch;
     p.ticket = h->ticket; p.fold_refit = 0;
     p.iters_total = c.iterations;
     p.timing = h->timing;
+}
+// the per-tile rollout launch of a route (ks_rollout; a trace call runs its tracing instantiation)
+int launch_rollout(tdmpc2_plan *h, const FusedRoute &r, const RolloutParams &p, hipStream_t st) {
+    fused_ops(h->Apad).rollout(h->split ? 0 : 1, r.nst, h->cfg.episodic != 0, p.trace_tiles || p.trace_scalars, p, r.grid, r.lds, st);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 // A bounded inter-workgroup wait gave up (the handle's error word is set): the plan / call in flight returned NaN.  Switch to
@@ -547,7 +499,7 @@ bool fault_poll(tdmpc2_plan *h) {
 }
 // Start of a call that stands for itself (a plan, an estimate_value, a td_target ...; NOT the later calls of a sharded plan, whose
 // final pick must still see a wait that gave up in its first iteration): word 0 back to zero, in stream order.  The fused
-// family's ks_setup does it itself (SetupParamsT::err_clear).
+// family's ks_setup does it itself (SetupParams::err_clear).
 int fault_fresh(tdmpc2_plan *h, hipStream_t st) {
     if (h->cl_err_dev) HIP_TRY(hipMemsetAsync(h->cl_err_dev, 0, 4, st));
     return 0;
@@ -564,46 +516,56 @@ int validate_envs(tdmpc2_plan *h, int E) {
 }
 
 
-// Everything of TDMPC2._plan after encode() (tdmpc2/tdmpc2.py:154-206) on the fused 512-wide path.
-template <class NET>
+// The opening the training calls share (policy_value / td_target, model_rollout / model_losses, policy_loss), in this order: the
+// task tables against the handle's kind (then `own`: the call's own refusals that sit there), bound weights, the sticky fault word,
+// a fresh verdict word, the target ensemble, the call-counter tick.  `needs`: the call's name(s) and verb as the refusal words them.
+template <class Own>
+int begin_value_call(tdmpc2_plan *h, const char *needs, const tdmpc2_task_tables *tk, bool target, hipStream_t st, unsigned *call,
+                     Own own) {
+    const tdmpc2_plan_cfg &c = h->cfg;
+    if (c.multitask) {
+        if (!tk || !tk->task_ids || !tk->task_emb || !tk->act_mask || tk->n_tasks < 1)
+            return fail(TDMPC2_ERR_INVALID, "multitask %s the row -> task map and the per-task tables", needs);
+    } else if (tk) {
+        return fail(TDMPC2_ERR_INVALID, "task tables given to a single-task handle");
+    }
+    int rc = own();
+    if (rc) return rc;
+    if ((rc = check_ready(h))) return rc;
+    (void)fault_poll(h);  // (a wait that gave up in an earlier call: this one already runs on the paths without waits)
+    // between the calls of a sharded plan word 0 is that plan's verdict (its final pick reads it): keep it
+    if (!h->in_shard && (rc = fault_fresh(h, st))) return rc;
+    if (target)
+        for (int i = 0; i < 3; ++i)
+            for (int qh = 0; qh < c.num_q; ++qh)
+                if (!h->tq[qh].l[i].bound)
+                    return fail(TDMPC2_ERR_STATE, "layer %d of target Q head %d is not bound (net TDMPC2_NET_TARGET_Q)", i, qh);
+    *call = h->call++;  // (model_rollout / model_losses draw nothing: their tick keeps the siblings' numbering uniform)
+    return 0;
+}
+
+// Everything of TDMPC2._plan after encode() (tdmpc2/tdmpc2.py:154-206) on the fused 512-wide path: fused_route_plan decides,
+// this launches.
 int fused_run(tdmpc2_plan *h, hipStream_t st, int E, const float *z0, const float *task_emb, const float *act_mask,
               const float *disc_pow, float *prev_mean, const uint8_t *t0, int eval_mode, const tdmpc2_noise *tape,
               uint64_t seed, float *action, const tdmpc2_debug *dbg) {
     const tdmpc2_plan_cfg &c = h->cfg;
-    const int H = c.horizon, N = c.num_samples, A = c.action_dim, K = c.num_elites, P = c.num_pi_trajs, I = c.iterations;
+    const int H = c.horizon, N = c.num_samples, A = c.action_dim, P = c.num_pi_trajs, I = c.iterations;
     const unsigned call = h->call++;
     int rc;
-    // single-plan latency: 8 workgroups per 32-row tile when the whole call then still fits the chip in one round
-    const long clusters = (long)E * h->tiles * 2;
-    const bool cluster = h->cluster_mode != 0 && h->cl_max_clusters > 0 && clusters <= h->cl_max_clusters &&
-                         (clusters + 7) / 8 * 64 <= plan_cus(h->num_cus);
-    // ... which also computes the policy-prior trajectories (cluster 0 of each plan, first launch) and needs no z0 products
-    const bool pi_fold = cluster && P > 0 && P <= 32;
-    if ((rc = launch_setup<NET>(h, E, z0, task_emb, prev_mean, t0, st, cluster))) return rc;
-    if (P > 0 && !pi_fold) {
-        PiTrajParamsT<NET> p{};
-        p.E = E; p.N = N; p.H = H; p.A = A; p.Apad = h->Apad; p.P = P; p.stride = h->stride; p.multitask = c.multitask;
-        p.nnets = h->nnets; p.log_std_min = c.log_std_min; p.log_std_dif = c.log_std_dif;
-        p.dyn = to_dev<NET>(h->dyn); p.pi = to_dev<NET>(h->pi);
-        p.z0 = z0; p.beff = h->beff; p.act_mask = act_mask; p.pi_traj_eps = tape ? tape->pi_traj_eps : nullptr;
-        p.seed = seed; p.call = call; p.actions = h->actions; p.zscratch = h->zscratch;
-        p.zscratch_estride = (long)h->tiles * ROWS * WIDTH;
-        Kern<NET>::pitraj(h, p, E, st);
-        HIP_TRY(hipGetLastError());
-    }
-    RolloutParamsT<NET> rp{};
-    fill_rollout<NET>(h, rp, E);
+    const FusedRoute r = fused_route_plan(fused_in(h, E));
+    const bool cluster = r.kind != FR_TILE;
+    if ((rc = launch_setup(h, r, E, z0, task_emb, prev_mean, t0, st))) return rc;
+    if (r.pitraj && (rc = launch_pitraj(h, r, E, z0, act_mask, tape, seed, call, st))) return rc;
+    RolloutParams rp{};
+    fill_rollout(h, r, rp, E);
     rp.z0 = z0; rp.act_mask = act_mask; rp.disc_pow = disc_pow; rp.seed = seed; rp.call = call; rp.given_actions = 0;
-    rp.pi_fold = pi_fold ? 1 : 0;
+    rp.pi_fold = r.pi_fold ? 1 : 0;
     rp.pi_traj_eps = tape ? tape->pi_traj_eps : nullptr;
-    const int nst = cluster ? 1 : Kern<NET>::sample_tiles(h, E, false), nw = Kern<NET>::waves(h, E, nst);
-    rp.tiles = h->tiles * (2 / nst);
     rp.cl_xbuf = h->cl_xbuf; rp.cl_flags = h->cl_flags; rp.cl_err = h->cl_err_dev; rp.cl_zs = h->cl_zs;
     rp.cl_fault = h->cl_fault;
     rp.cl2_xbuf = h->cl2_xbuf; rp.cl2_flags = h->cl2_flags; rp.cl2_zs = h->cl2_zs; rp.cl2_mail = h->cl2_mail;
-    // a single non-episodic plan: from the second launch on the reward chain runs beside the dynamics chain on a second cluster
-    // per tile (ks_rollout_cl2: all 256 CUs)
-    const bool cluster2 = cluster && h->cluster_mode == 2 && E == 1 && h->cl2_xbuf && h->cl2_mode && !c.episodic && !h->cl_fault;
+    rp.fold_refit = r.fold ? 1 : 0;
     std::unique_lock<std::mutex> gate;
     bool gate_record = false;
     const int gdev = c.device >= 0 && c.device < 64 ? c.device : 0;
@@ -622,18 +584,6 @@ int fused_run(tdmpc2_plan *h, hipStream_t st, int E, const float *z0, const floa
             gate_record = true;
         }
     }
-    // elite selection + refit: inside the rollout launch (last workgroup of each plan, LDS budget = the 32-row tile) or as
-    // a launch of its own (TDMPC2_TUNE_FOLD_REFIT 0)
-    int refit_stage = 0;
-    size_t refit_lds = refit_lds_bytes(N, K, H, A, &refit_stage, (size_t)32 * h->row_bytes);
-    // the in-launch refit stages the re-derived elite actions in the (then idle) tile memory; if they do not fit, or the
-    // caller wants the per-iteration action dump, the refit runs as a launch of its own
-    // auto: only when the whole launch is one round of workgroups (few plans: latency).  With several rounds every round
-    // ends with the refits of the plans that completed in it, on CUs whose next workgroup then starts late: measured
-    // +0.5 ms on the 4.4 ms launch of 256 plans, against 30 us for the separate k_refit launch.
-    const bool one_round = cluster || (long)E * rp.tiles <= plan_cus(h->num_cus);
-    const bool fold = refit_stage && (h->fold_refit == 1 || (h->fold_refit == 2 && one_round));
-    if (!fold) refit_lds = refit_lds_bytes(N, K, H, A, &refit_stage);
     for (int it = 0; it < I; ++it) {
         rp.iter = it;
         if (tape) {
@@ -645,45 +595,27 @@ int fused_run(tdmpc2_plan *h, hipStream_t st, int E, const float *z0, const floa
             rp.qidx_estride = (long)I * 2;
         }
         RefitParams &fp = rp.rf;
-        fp = RefitParams{};
-        fp.Nvalid = c.num_valid_samples; fp.E = E; fp.N = N; fp.H = H; fp.A = A; fp.K = K; fp.iter = it; fp.last = (it == I - 1); fp.eval_mode = eval_mode; fp.stage = refit_stage;
-        fp.temperature = c.temperature; fp.min_std = c.min_std; fp.max_std = c.max_std;
-        fp.value = h->value; fp.actions = h->actions; fp.act_mask = act_mask; fp.mean = h->mean; fp.std = h->std;
-        fp.gumbel_exp = tape ? tape->gumbel_exp : nullptr; fp.final_eps = tape ? tape->final_eps : nullptr;
-        fp.seed = seed; fp.call = call; fp.prev_mean = prev_mean; fp.action = action;
-        fp.err = cluster ? h->cl_err_dev : nullptr;
-        if (dbg) {
-            if (dbg->value) { fp.dbg_value = dbg->value + (size_t)it * N; fp.dbg_value_es = (long)I * N; }
-            if (dbg->elite_idx) { fp.dbg_idx = dbg->elite_idx + (size_t)it * K; fp.dbg_idx_es = (long)I * K; }
-            if (dbg->score) { fp.dbg_score = dbg->score + (size_t)it * K; fp.dbg_score_es = (long)I * K; }
-            if (dbg->mean) { fp.dbg_mean = dbg->mean + (size_t)it * H * A; fp.dbg_mean_es = (long)I * H * A; }
-            if (dbg->std) { fp.dbg_std = dbg->std + (size_t)it * H * A; fp.dbg_std_es = (long)I * H * A; }
-        }
-        rp.fold_refit = fold ? 1 : 0;
-        if (fold) {
+        fill_refit(h, fp, E, it, eval_mode, h->value, act_mask, tape, seed, call, prev_mean, action, dbg, r.refit_stage,
+                   cluster ? h->cl_err_dev : nullptr);
+        if (r.fold) {
             fp.regen = 1; fp.P = P; fp.Apad = h->Apad;
             fp.sample_eps = rp.sample_eps; fp.sample_eps_estride = rp.sample_eps_estride;
         }
         if (h->profiling && h->ev_used + 2 <= (int)h->ev.size()) HIP_TRY(hipEventRecord(h->ev[h->ev_used], st));
-        // ks_rollout_cl2 maps blocks to (tile, role) in groups of 8 tiles x 2 roles: BOTH roles of every started group of 8
-        // tiles need their blocks ((2 * clusters + 7) / 8 groups left tiles 0 .. 3 of a 64- / 128-sample plan without their R
-        // cluster: D's mailbox wait gave up and the plan returned NaN)
-        if (cluster2) cluster_ops(h->Apad).rollout_cl2(rp, (int)((clusters + 7) / 8 * 2 * 64), h->cl_lds, st);
-        else if (cluster) Kern<NET>::rollout_cluster(h, rp, (int)clusters, st);
-        else Kern<NET>::rollout(h, rp, E * rp.tiles, st, nst, nw);
-        HIP_TRY(hipGetLastError());
+        if (r.kind == FR_TILE) {
+            if ((rc = launch_rollout(h, r, rp, st))) return rc;
+        } else {
+            if (r.kind == FR_CLUSTER2) cluster_ops(h->Apad).rollout_cl2(rp, r.grid, r.lds, st);
+            else cluster_ops(h->Apad).rollout_cl(c.episodic != 0, rp, r.grid, r.lds, st);
+            HIP_TRY(hipGetLastError());
+        }
         if (h->profiling && h->ev_used + 2 <= (int)h->ev.size()) {
             HIP_TRY(hipEventRecord(h->ev[h->ev_used + 1], st));
             h->ev_used += 2;
         }
-        if (!fold) {
-            hipLaunchKernelGGL(k_refit, dim3(E), dim3(refit_threads(N)), refit_lds, st, fp);
-            HIP_TRY(hipGetLastError());
-        }
+        if (!r.fold && (rc = launch_refit(fp, E, N, r.refit_lds, st))) return rc;
         // the per-iteration action dump reads h->actions after the refit (which does not write them)
-        if (dbg && dbg->actions)
-            HIP_TRY(hipMemcpy2DAsync(dbg->actions + (size_t)it * H * N * A, (size_t)I * H * N * A * 4, h->actions,
-                                     (size_t)H * N * A * 4, (size_t)H * N * A * 4, E, hipMemcpyDeviceToDevice, st));
+        if ((rc = dump_actions(h, dbg, E, it, st))) return rc;
     }
     if (gate_record) {
         HIP_TRY(hipEventRecord(g_cluster_gate.ev[gdev], st));
@@ -693,30 +625,26 @@ int fused_run(tdmpc2_plan *h, hipStream_t st, int E, const float *z0, const floa
 }
 
 // TDMPC2._estimate_value (tdmpc2/tdmpc2.py:122-136) on given action sequences, fused path.
-template <class NET>
 int fused_estimate_value(tdmpc2_plan *h, hipStream_t st, int E, const float *z0, const float *task_emb,
                          const float *act_mask, const float *disc_pow, const float *actions, const float *pi_eps,
                          const int32_t *qidx, float *value, float *trace_tiles, float *trace_scalars) {
     const tdmpc2_plan_cfg &c = h->cfg;
     const int N = c.num_samples, A = c.action_dim;
     int rc;
+    const FusedRoute r = fused_route_value(fused_in(h, E), trace_tiles != nullptr || trace_scalars != nullptr);
     // setup needs prev_mean / t0 only for mean/std init, which this entry does not use: feed dummies
     HIP_TRY(hipMemsetAsync(h->mean, 0, (size_t)E * c.horizon * A * 4, st));
     HIP_TRY(hipMemsetAsync(h->value, 1, (size_t)E, st));  // E bytes of ones used as t0 = 1 flags (no warm start read)
-    if ((rc = launch_setup<NET>(h, E, z0, task_emb, h->mean, reinterpret_cast<const unsigned char *>(h->value), st))) return rc;
-    RolloutParamsT<NET> rp{};
-    fill_rollout<NET>(h, rp, E);
+    if ((rc = launch_setup(h, r, E, z0, task_emb, h->mean, reinterpret_cast<const unsigned char *>(h->value), st))) return rc;
+    RolloutParams rp{};
+    fill_rollout(h, r, rp, E);
     rp.z0 = z0; rp.act_mask = act_mask; rp.disc_pow = disc_pow; rp.given_actions = 1; rp.iter = 0;
     rp.actions = const_cast<float *>(actions);
     rp.value = value;
     rp.pi_eps = pi_eps; rp.pi_eps_estride = (long)N * A;
     rp.qidx = qidx; rp.qidx_estride = 2;
     rp.trace_tiles = trace_tiles; rp.trace_scalars = trace_scalars;
-    const int nst = Kern<NET>::sample_tiles(h, E, trace_tiles != nullptr || trace_scalars != nullptr), nw = Kern<NET>::waves(h, E, nst);
-    rp.tiles = h->tiles * (2 / nst);
-    Kern<NET>::rollout(h, rp, E * rp.tiles, st, nst, nw);
-    HIP_TRY(hipGetLastError());
-    return TDMPC2_OK;
+    return launch_rollout(h, r, rp, st);
 }
 
 }  // namespace
@@ -1589,24 +1517,11 @@ int launch_value(tdmpc2_plan *h, int rows, const float *z, bool target, bool red
                  uint64_t seed, const float *reward, const float *terminated, float discount, const tdmpc2_task_tables *tk,
                  float *action, float *out, hipStream_t st) {
     const tdmpc2_plan_cfg &c = h->cfg;
-    if (c.multitask) {
-        if (!tk || !tk->task_ids || !tk->task_emb || !tk->act_mask || tk->n_tasks < 1)
-            return fail(TDMPC2_ERR_INVALID, "multitask policy_value / td_target need the row -> task map and the per-task tables");
-        if (reward && !tk->discount) return fail(TDMPC2_ERR_INVALID, "multitask td_target needs the per-task discounts");
-    } else if (tk) {
-        return fail(TDMPC2_ERR_INVALID, "task tables given to a single-task handle");
-    }
-    int rc = check_ready(h);
+    unsigned call;
+    int rc = begin_value_call(h, "policy_value / td_target need", tk, target, st, &call, [&] {
+        return c.multitask && reward && !tk->discount ? fail(TDMPC2_ERR_INVALID, "multitask td_target needs the per-task discounts") : 0;
+    });
     if (rc) return rc;
-    (void)fault_poll(h);  // (a wait that gave up in an earlier call: this one already runs on the paths without waits)
-    // between the calls of a sharded plan word 0 is that plan's verdict (its final pick reads it): keep it
-    if (!h->in_shard && (rc = fault_fresh(h, st))) return rc;
-    if (target)
-        for (int i = 0; i < 3; ++i)
-            for (int qh = 0; qh < c.num_q; ++qh)
-                if (!h->tq[qh].l[i].bound)
-                    return fail(TDMPC2_ERR_STATE, "layer %d of target Q head %d is not bound (net TDMPC2_NET_TARGET_Q)", i, qh);
-    const unsigned call = h->call++;
     if (h->lay.on) {
         const size_t rows_p = round_up((size_t)rows, GBM), cap = round_up((size_t)c.max_envs * c.num_samples, GBM);
         if (rows_p > cap)
@@ -1622,11 +1537,11 @@ int launch_value(tdmpc2_plan *h, int rows, const float *z, bool target, bool red
                          c.multitask ? h->task_rows : nullptr, action, out);
     }
     if (c.multitask && (rc = build_task_tables(h, tk, target, 0, st))) return rc;
-    ValueParamsT<NetS> p{};
+    ValueParams p{};
     p.rows = rows; p.A = c.action_dim; p.Apad = h->Apad; p.nq = c.num_q; p.num_bins = c.num_bins; p.reduce_min = reduce_min ? 1 : 0;
     p.log_std_min = c.log_std_min; p.log_std_dif = c.log_std_dif; p.discount = discount;
-    p.pi = to_dev<NetS>(h->pi);
-    for (int i = 0; i < c.num_q; ++i) p.q[i] = to_dev<NetS>(target ? h->tq[i] : h->q[i]);
+    p.pi = to_dev(h->pi);
+    for (int i = 0; i < c.num_q; ++i) p.q[i] = to_dev(target ? h->tq[i] : h->q[i]);
     p.bins = h->bins; p.z = z; p.pi_eps = pi_eps; p.qidx = qidx; p.seed = seed; p.call = call;
     p.reward = reward; p.terminated = terminated; p.action = action; p.out = out;
     p.nnets = h->nnets;
@@ -1721,22 +1636,9 @@ int launch_model(tdmpc2_plan *h, int B, int H, const float *z0, const float *act
         if (!tg->next_z || !tg->reward || !tg->td_target || !losses) return fail(TDMPC2_ERR_INVALID, "null target / losses argument");
         if (c.episodic && !tg->terminated) return fail(TDMPC2_ERR_INVALID, "episodic handle: `terminated` is required");
     }
-    if (c.multitask) {
-        if (!tk || !tk->task_ids || !tk->task_emb || !tk->act_mask || tk->n_tasks < 1)
-            return fail(TDMPC2_ERR_INVALID, "multitask model_rollout / model_losses need the row -> task map and the per-task tables");
-    } else if (tk) {
-        return fail(TDMPC2_ERR_INVALID, "task tables given to a single-task handle");
-    }
-    int rc = check_ready(h);
+    unsigned call;
+    int rc = begin_value_call(h, "model_rollout / model_losses need", tk, target, st, &call, [] { return 0; });
     if (rc) return rc;
-    (void)fault_poll(h);
-    if (!h->in_shard && (rc = fault_fresh(h, st))) return rc;
-    if (target)
-        for (int i = 0; i < 3; ++i)
-            for (int qh = 0; qh < c.num_q; ++qh)
-                if (!h->tq[qh].l[i].bound)
-                    return fail(TDMPC2_ERR_STATE, "layer %d of target Q head %d is not bound (net TDMPC2_NET_TARGET_Q)", i, qh);
-    h->call++;  // one tick like policy_value / td_target (nothing is drawn here: the tick keeps the siblings' numbering uniform)
     const size_t Ld = (size_t)c.latent_dim, HB = (size_t)H * B;
     if (r.launches == 0) {  // H = 0 and no termination logit: zs[0] = z0 is all there is
         if (out->zs && out->zs != z0) HIP_TRY(hipMemcpyAsync(out->zs, z0, (size_t)B * Ld * 4, hipMemcpyDeviceToDevice, st));
@@ -1763,11 +1665,11 @@ int launch_model(tdmpc2_plan *h, int B, int H, const float *z0, const float *act
     if (h->lay.on) {
         if ((rc = lay_model(h, st, r, B, H, actions, zs, target, c.multitask ? h->task_rows : nullptr, oa, ls))) return rc;
     } else {
-        ModelParamsT<NetS> p{};
+        ModelParams p{};
         p.B = B; p.H = H; p.A = c.action_dim; p.Apad = h->Apad; p.nq = c.num_q; p.nnets = h->nnets; p.steps = r.st[MS_DYN].steps;
-        p.dyn = to_dev<NetS>(h->dyn); p.rew = to_dev<NetS>(h->rew);
-        if (c.episodic) p.term = to_dev<NetS>(h->term);
-        for (int i = 0; i < c.num_q; ++i) p.q[i] = to_dev<NetS>(target ? h->tq[i] : h->q[i]);
+        p.dyn = to_dev(h->dyn); p.rew = to_dev(h->rew);
+        if (c.episodic) p.term = to_dev(h->term);
+        for (int i = 0; i < c.num_q; ++i) p.q[i] = to_dev(target ? h->tq[i] : h->q[i]);
         p.z0 = z0; p.actions = actions; p.zs = zs; p.out = oa; p.ls = ls;
         if (c.multitask) { p.task_ids = tk->task_ids; p.beff_tab = h->beff_tab; }
         const int ar = h->split ? 0 : 1;
@@ -1835,19 +1737,12 @@ int launch_policy_loss(tdmpc2_plan *h, int B, int steps, const float *zs, const 
     if (!out) out = &none;
     if (B < 1) return fail(TDMPC2_ERR_INVALID, "batch %d < 1", B);
     if (steps < 0 || steps > PL_MAX_STEPS) return fail(TDMPC2_ERR_INVALID, "steps %d outside [0, %d]", steps, (int)PL_MAX_STEPS);
-    if (c.multitask) {
-        if (!tk || !tk->task_ids || !tk->task_emb || !tk->act_mask || tk->n_tasks < 1)
-            return fail(TDMPC2_ERR_INVALID, "multitask policy_loss needs the row -> task map and the per-task tables");
-    } else if (tk) {
-        return fail(TDMPC2_ERR_INVALID, "task tables given to a single-task handle");
-    }
-    if (in->update_scale && B > PL_SCALE_MAX_N)
-        return fail(TDMPC2_ERR_UNSUPPORTED, "the running scale takes at most %d values; got batch %d", (int)PL_SCALE_MAX_N, B);
-    int rc = check_ready(h);
+    unsigned call;
+    int rc = begin_value_call(h, "policy_loss needs", tk, false, st, &call, [&] {
+        return in->update_scale && B > PL_SCALE_MAX_N
+                   ? fail(TDMPC2_ERR_UNSUPPORTED, "the running scale takes at most %d values; got batch %d", (int)PL_SCALE_MAX_N, B) : 0;
+    });
     if (rc) return rc;
-    (void)fault_poll(h);
-    if (!h->in_shard && (rc = fault_fresh(h, st))) return rc;
-    const unsigned call = h->call++;
     const int T = steps + 1;
     const size_t rows = (size_t)T * B;
     if ((rc = grow_ws(h, &h->ploss_rows, &h->ploss_rows_cap, 3 * rows, st))) return rc;
@@ -1871,11 +1766,11 @@ int launch_policy_loss(tdmpc2_plan *h, int B, int steps, const float *zs, const 
         err = (h->split && h->lay.fuse_ln) ? h->cl_err_dev : nullptr;
     } else {
         if (c.multitask && (rc = build_task_tables(h, tk, false, 0, st))) return rc;
-        ValueEntParamsT<NetS> p{};
+        ValueEntParams p{};
         p.rows = (int)rows; p.A = c.action_dim; p.Apad = h->Apad; p.nq = c.num_q; p.num_bins = c.num_bins; p.reduce_min = 0;
         p.log_std_min = c.log_std_min; p.log_std_dif = c.log_std_dif;
-        p.pi = to_dev<NetS>(h->pi);
-        for (int i = 0; i < c.num_q; ++i) p.q[i] = to_dev<NetS>(h->q[i]);
+        p.pi = to_dev(h->pi);
+        for (int i = 0; i < c.num_q; ++i) p.q[i] = to_dev(h->q[i]);
         p.bins = h->bins; p.z = zs; p.pi_eps = pi_eps; p.qidx = qidx; p.seed = seed; p.call = call;
         p.action = out->action; p.out = wq; p.entropy = went; p.scaled_entropy = wsent;
         p.nnets = h->nnets;
@@ -1929,31 +1824,6 @@ int tdmpc2_plan_termination_stats(tdmpc2_plan_t *h, int n, const float *term_log
 // the identical set-up, draws the identical actions (same tape / same Philox seed) and performs the identical elite
 // selection + refit on the all-gathered values.  Per CEM iteration a rank calls shard_values for ITS row range, the host
 // all-gathers value[E, N / G] over RCCL (4 KB per plan), and every rank calls shard_refit.  tdmpc2_amd/dist.py drives it.
-namespace {
-void fill_refit(tdmpc2_plan *h, RefitParams &fp, int E, int it, int eval_mode, float *value, const float *act_mask,
-                const tdmpc2_noise *tape, uint64_t seed, unsigned call, float *prev_mean, float *action, const tdmpc2_debug *dbg,
-                int stage) {
-    const tdmpc2_plan_cfg &c = h->cfg;
-    const int H = c.horizon, N = c.num_samples, A = c.action_dim, K = c.num_elites, I = c.iterations;
-    fp = RefitParams{};
-    fp.Nvalid = c.num_valid_samples; fp.E = E; fp.N = N; fp.H = H; fp.A = A; fp.K = K; fp.iter = it; fp.last = (it == I - 1); fp.eval_mode = eval_mode; fp.stage = stage;
-    fp.temperature = c.temperature; fp.min_std = c.min_std; fp.max_std = c.max_std;
-    fp.value = value; fp.actions = h->actions; fp.act_mask = act_mask; fp.mean = h->mean; fp.std = h->std;
-    fp.gumbel_exp = tape ? tape->gumbel_exp : nullptr; fp.final_eps = tape ? tape->final_eps : nullptr;
-    fp.seed = seed; fp.call = call; fp.prev_mean = prev_mean; fp.action = action;
-    // a bounded inter-workgroup wait (fused NormedLinear epilogue) that gave up in ANY iteration of this sharded plan: NaN
-    // action, prev_mean kept -- word 0 is cleared by shard_begin only (in stream order), not by the calls in between
-    fp.err = h->cl_err_dev; fp.err2 = nullptr;
-    if (dbg) {
-        if (dbg->value) { fp.dbg_value = dbg->value + (size_t)it * N; fp.dbg_value_es = (long)I * N; }
-        if (dbg->elite_idx) { fp.dbg_idx = dbg->elite_idx + (size_t)it * K; fp.dbg_idx_es = (long)I * K; }
-        if (dbg->score) { fp.dbg_score = dbg->score + (size_t)it * K; fp.dbg_score_es = (long)I * K; }
-        if (dbg->mean) { fp.dbg_mean = dbg->mean + (size_t)it * H * A; fp.dbg_mean_es = (long)I * H * A; }
-        if (dbg->std) { fp.dbg_std = dbg->std + (size_t)it * H * A; fp.dbg_std_es = (long)I * H * A; }
-    }
-}
-}  // namespace
-
 int tdmpc2_plan_shard_begin(tdmpc2_plan_t *h, int n_envs, const float *z0, const float *task_emb, const float *act_mask,
                             const float *prev_mean, const uint8_t *t0, const tdmpc2_noise *tape, uint64_t seed, void *stream) {
     if (!h) return fail(TDMPC2_ERR_INVALID, "null handle");
@@ -1983,18 +1853,9 @@ int tdmpc2_plan_shard_begin(tdmpc2_plan_t *h, int n_envs, const float *z0, const
         guard.ok = true;
         return TDMPC2_OK;
     }
-    if ((rc = launch_setup<NetS>(h, E, z0, task_emb, prev_mean, t0, st))) return rc;
-    if (P > 0) {
-        PiTrajParamsT<NetS> p{};
-        p.E = E; p.N = c.num_samples; p.H = c.horizon; p.A = c.action_dim; p.Apad = h->Apad; p.P = P; p.stride = h->stride;
-        p.multitask = c.multitask; p.nnets = h->nnets; p.log_std_min = c.log_std_min; p.log_std_dif = c.log_std_dif;
-        p.dyn = to_dev<NetS>(h->dyn); p.pi = to_dev<NetS>(h->pi);
-        p.z0 = z0; p.beff = h->beff; p.act_mask = act_mask; p.pi_traj_eps = tape ? tape->pi_traj_eps : nullptr;
-        p.seed = seed; p.call = call; p.actions = h->actions; p.zscratch = h->zscratch;
-        p.zscratch_estride = (long)h->tiles * ROWS * WIDTH;
-        Kern<NetS>::pitraj(h, p, E, st);
-        HIP_TRY(hipGetLastError());
-    }
+    const FusedRoute r = fused_route_shard(fused_in(h, E), 0, c.num_samples);
+    if ((rc = launch_setup(h, r, E, z0, task_emb, prev_mean, t0, st))) return rc;
+    if (r.pitraj && (rc = launch_pitraj(h, r, E, z0, act_mask, tape, seed, call, st))) return rc;
     guard.ok = true;
     return TDMPC2_OK;
 }
@@ -2026,16 +1887,12 @@ int tdmpc2_plan_shard_values(tdmpc2_plan_t *h, int n_envs, int iter, int row_beg
     if (h->lay.on)
         return lay_estimate_value(h, st, E, z0, act_mask, disc_pow, h->actions, pi_eps, (long)I * N * A, qbuf, seed, call, iter, value,
                                   nullptr, row_begin, row_end - row_begin);
-    RolloutParamsT<NetS> rp{};
-    fill_rollout<NetS>(h, rp, E);
+    const FusedRoute r = fused_route_shard(fused_in(h, E), row_begin, row_end);
+    RolloutParams rp{};
+    fill_rollout(h, r, rp, E);
     rp.z0 = z0; rp.act_mask = act_mask; rp.disc_pow = disc_pow; rp.seed = seed; rp.call = call; rp.given_actions = 1; rp.iter = iter;
     rp.value = value; rp.pi_eps = pi_eps; rp.pi_eps_estride = (long)I * N * A; rp.qidx = qbuf; rp.qidx_estride = 2;
-    const int nst = h->force_rows == 32 ? 1 : 2;
-    const int trows = 32 * nst;
-    rp.tiles = (row_end - row_begin) / trows; rp.tile_off = row_begin / trows;
-    Kern<NetS>::rollout(h, rp, E * rp.tiles, st, nst, 8);
-    HIP_TRY(hipGetLastError());
-    return TDMPC2_OK;
+    return launch_rollout(h, r, rp, st);
 }
 
 int tdmpc2_plan_shard_refit(tdmpc2_plan_t *h, int n_envs, int iter, float *value, const float *act_mask, float *prev_mean,
@@ -2049,22 +1906,19 @@ int tdmpc2_plan_shard_refit(tdmpc2_plan_t *h, int n_envs, int iter, float *value
     if (iter < 0 || iter >= c.iterations) return fail(TDMPC2_ERR_INVALID, "iteration %d outside [0, %d)", iter, c.iterations);
     if (tape && (!tape->gumbel_exp || (!eval_mode && !tape->final_eps))) return fail(TDMPC2_ERR_INVALID, "noise tape has null fields");
     hipStream_t st = (hipStream_t)stream;
-    int stage = 0;
+    int stage = 0, rc;
     const size_t lds = refit_lds_bytes(c.num_samples, c.num_elites, c.horizon, c.action_dim, &stage);
     RefitParams fp;
-    fill_refit(h, fp, n_envs, iter, eval_mode, value, c.multitask ? act_mask : nullptr, tape, seed, h->shard_call, prev_mean, action, dbg, stage);
-    hipLaunchKernelGGL(k_refit, dim3(n_envs), dim3(refit_threads(c.num_samples)), lds, st, fp);
-    HIP_TRY(hipGetLastError());
+    // err: a bounded inter-workgroup wait (fused NormedLinear epilogue) that gave up in ANY iteration of this sharded plan: NaN
+    // action, prev_mean kept -- word 0 is cleared by shard_begin only (in stream order), not by the calls in between
+    fill_refit(h, fp, n_envs, iter, eval_mode, value, c.multitask ? act_mask : nullptr, tape, seed, h->shard_call, prev_mean, action, dbg,
+               stage, h->cl_err_dev);
+    if ((rc = launch_refit(fp, n_envs, c.num_samples, lds, st))) return rc;
     if (fp.last) {
         h->in_shard = false;
         if (h->safe_once) { h->safe_once = false; apply_modes(h); }
     }
-    if (dbg && dbg->actions)
-        HIP_TRY(hipMemcpy2DAsync(dbg->actions + (size_t)iter * c.horizon * c.num_samples * c.action_dim,
-                                 (size_t)c.iterations * c.horizon * c.num_samples * c.action_dim * 4, h->actions,
-                                 (size_t)c.horizon * c.num_samples * c.action_dim * 4, (size_t)c.horizon * c.num_samples * c.action_dim * 4,
-                                 n_envs, hipMemcpyDeviceToDevice, st));
-    return TDMPC2_OK;
+    return dump_actions(h, dbg, n_envs, iter, st);
 }
 
 // ---------------------------------------------------------------- packed weight file
@@ -2444,7 +2298,7 @@ int run_impl(tdmpc2_plan *h, int n_envs, const float *z0, const float *task_emb,
         if ((rc = fault_fresh(h, st))) return rc;
         return lay_run(h, st, n_envs, z0, task_emb, act_mask, disc_pow, prev_mean, t0, eval_mode, tape, seed, action, dbg);
     }
-    return fused_run<NetS>(h, st, n_envs, z0, task_emb, act_mask, disc_pow, prev_mean, t0, eval_mode, tape, seed, action, dbg);
+    return fused_run(h, st, n_envs, z0, task_emb, act_mask, disc_pow, prev_mean, t0, eval_mode, tape, seed, action, dbg);
 }
 }  // namespace
 extern "C" {
@@ -2479,7 +2333,7 @@ int tdmpc2_plan_estimate_value_trace(tdmpc2_plan_t *h, int n_envs, const float *
         return lay_estimate_value(h, st, E, z0, act_mask, disc_pow, actions, pi_eps, (long)N * A, h->lay.qidx, 0, 0, 0, value,
                                   trace_scalars);
     }
-    return fused_estimate_value<NetS>(h, st, E, z0, task_emb, act_mask, disc_pow, actions, pi_eps, qidx, value, trace_tiles,
+    return fused_estimate_value(h, st, E, z0, task_emb, act_mask, disc_pow, actions, pi_eps, qidx, value, trace_tiles,
                                       trace_scalars);
 }
 
@@ -2498,9 +2352,7 @@ int tdmpc2_plan_refit(tdmpc2_plan_t *h, int n_envs, float *value, const float *a
     fp.temperature = c.temperature; fp.min_std = c.min_std; fp.max_std = c.max_std;
     fp.value = value; fp.actions = actions; fp.act_mask = c.multitask ? act_mask : nullptr;
     fp.mean = mean ? mean : h->mean; fp.std = std ? std : h->std; fp.score = score; fp.elite_idx = elite_idx;
-    hipLaunchKernelGGL(k_refit, dim3(n_envs), dim3(refit_threads(c.num_samples)), refit_lds, st, fp);
-    HIP_TRY(hipGetLastError());
-    return TDMPC2_OK;
+    return launch_refit(fp, n_envs, c.num_samples, refit_lds, st);
 }
 
 // ================================================================ pixel encoder, batch route (k_pixel_batch.hip, pixel_batch_route.h)
