@@ -62,6 +62,7 @@
 #ifndef TDMPC2_PLAN_H
 #define TDMPC2_PLAN_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -742,6 +743,40 @@ int tdmpc2_buffer_sample(tdmpc2_buffer_t *b, int32_t batch, void *const *outs, i
 int tdmpc2_buffer_stats(tdmpc2_buffer_t *b, tdmpc2_buffer_info *info, void *stream);
 /* The call counter of the NEXT sample (the reproducibility handle torch.manual_seed gives the reference's sampler), stream-ordered. */
 int tdmpc2_buffer_set_call_counter(tdmpc2_buffer_t *b, uint32_t next_call, void *stream);
+
+/* ---- trainable layer (additions to ABI 14): forward and backward of the one layer every MLP of the model is made of ----------
+ * NormedLinear (tdmpc2/common/layers.py:94-118): Linear -> dropout mask -> LayerNorm -> Mish, or -> SimNorm(simnorm_dim) on the
+ * last layer of the encoder and the dynamics; kind LINEAR is the plain nn.Linear that closes the other MLPs.  `groups` stacks
+ * identically shaped layers (the Q ensemble).  No handle, no state: a call is its descriptor, its pointers and, for backward, a
+ * caller-owned workspace.  A call allocates nothing and never synchronises the host, so it can be captured in a hipGraph.
+ *   Layout    contiguous fp32 on the current device.  G = groups, R = rows, K = in_dim, N = out_dim.  w [G, N, K]; b, ln_w, ln_b
+ *             [G, N]; y, pre, mask, dy [G, R, N]; x, dx [G, R, K], or [R, K] with shared_x (the ensemble's first layer reads one
+ *             input; dx is then the sum over groups, one chain in the order g = 0 .. G - 1); stat [G, R, 2] = (mean, rstd).
+ *   Forward   pre = (x w^T + b) * mask (mask optional: dropout's 0 or 1 / (1 - p)); stat from F.layer_norm's biased variance,
+ *             rstd = 1 / sqrt(var + ln_eps); y = mish(u) (softplus threshold 20) or softmax over contiguous groups of simnorm_dim
+ *             with the max subtracted, u = (pre - mean) rstd ln_w + ln_b.  LINEAR: y = (x w^T + b) * mask; ln_*, pre, stat ignored.
+ *   Backward  OVERWRITES dx [as x], dw [G, N, K], db, dln_w, dln_b [G, N].  dx may be NULL (a first layer); the parameter
+ *             gradients may be NULL together (frozen parameters; LINEAR has two, dw and db, and ignores dln_*).  ln_b is read
+ *             because u is recomputed from pre and stat rather than stored.
+ *   Numerics  exact fp32.  The three contractions run on v_mfma_f32_32x32x2_f32: every output element is one fmaf chain in
+ *             rising reduction index, never split, so a row's y and dx do not depend on the other rows of the call and results
+ *             are bit-identical from run to run.  Row and column sums have fixed orders (tdmpc2_amd/csrc/layer_grad_route.h).
+ * TDMPC2_ERR_INVALID before the device is touched: NULL descriptor or required pointer; groups, rows, in_dim or out_dim < 1;
+ * unknown kind; SIMNORM with simnorm_dim < 1 or out_dim % simnorm_dim != 0; shared_x with groups == 1; ws NULL or ws_bytes too
+ * small (a LINEAR backward without mask needs none); only some of the parameter gradients; dx and all of them NULL.  A descriptor whose GEMM grids would pass 2^31 workgroups:
+ * TDMPC2_ERR_UNSUPPORTED, also before the device is touched. */
+enum { TDMPC2_LAYER_LINEAR = 0, TDMPC2_LAYER_MISH = 1, TDMPC2_LAYER_SIMNORM = 2 };
+typedef struct tdmpc2_layer_desc {
+    int32_t kind, groups, rows, in_dim, out_dim, shared_x, simnorm_dim;
+    float ln_eps;
+} tdmpc2_layer_desc;   /* 32 bytes, no padding */
+/* Bytes of workspace a backward call of this descriptor needs.  Host only: never touches a device. */
+int tdmpc2_layer_workspace_bytes(const tdmpc2_layer_desc *desc, size_t *backward_ws_bytes);
+int tdmpc2_layer_forward(const tdmpc2_layer_desc *desc, const float *x, const float *w, const float *b, const float *ln_w,
+                         const float *ln_b, const float *mask, float *y, float *pre, float *stat, void *stream);
+int tdmpc2_layer_backward(const tdmpc2_layer_desc *desc, const float *x, const float *w, const float *ln_w, const float *ln_b,
+                          const float *pre, const float *stat, const float *mask, const float *dy, float *dx, float *dw, float *db,
+                          float *dln_w, float *dln_b, void *ws, size_t ws_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,105 @@
+"""PyTorch autograd over the library's trainable layer (tdmpc2_layer_forward / tdmpc2_layer_backward, include/tdmpc2_plan.h).
+
+`LayerFn` is one NormedLinear (Linear -> dropout mask -> LayerNorm -> Mish or SimNorm) or one plain Linear, forward and backward in
+HIP; `mlp_apply` and `ensemble_apply` walk the modules of tdmpc2_amd/layers.py through it, so that `loss.backward()` over
+`WorldModel.next / reward / pi / Q` computes every MLP gradient in the library.  There is no fallback: a CPU tensor is an error.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import layers, native
+
+
+class LayerFn(torch.autograd.Function):
+    """y = layer(x).  x [..., K] (leading dimensions are flattened to rows); ungrouped parameters w [N, K], b / ln_w / ln_b [N]
+    give y [..., N]; stacked parameters w [G, N, K], ... take x [G, ..., K], or with `shared_x` one x [..., K] for all groups,
+    and give y [G, ..., N].  mask: None or dropout's multipliers, shaped as y.  Saves x, pre, stat and mask."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, ln_w, ln_b, mask, kind, shared_x, simnorm_dim, eps):
+        grouped = w.dim() == 3
+        G = w.shape[0] if grouped else 1
+        N, K = w.shape[-2], w.shape[-1]
+        lead = x.shape[1:-1] if grouped and not shared_x else x.shape[:-1]
+        if x.shape[-1] != K or (grouped and not shared_x and x.shape[0] != G):
+            raise native.NativeError(f"LayerFn: x {tuple(x.shape)} does not fit w {tuple(w.shape)} (shared_x={bool(shared_x)})")
+        R = 1
+        for s in lead:
+            R *= int(s)
+        desc = native.layer_desc(kind, G, R, K, N, shared_x, simnorm_dim, eps)
+        xc, wc, bc = x.detach().contiguous(), w.detach().contiguous(), b.detach().contiguous()
+        ln = kind != native.LAYER_LINEAR
+        lwc = ln_w.detach().contiguous() if ln else None
+        lbc = ln_b.detach().contiguous() if ln else None
+        mc = mask.detach().contiguous() if mask is not None else None
+        y = torch.empty((G, R, N), dtype=torch.float32, device=x.device)
+        pre = torch.empty_like(y) if ln else None
+        stat = torch.empty((G, R, 2), dtype=torch.float32, device=x.device) if ln else None
+        native.layer_forward(desc, xc, wc, bc, lwc, lbc, mc, y, pre, stat)
+        ctx.desc, ctx.ln, ctx.x_shape, ctx.w_shape = desc, ln, x.shape, w.shape
+        ctx.save_for_backward(xc, wc, lwc, lbc, pre, stat, mc)
+        return y.view(*((G,) if grouped else ()), *lead, N)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xc, wc, lwc, lbc, pre, stat, mc = ctx.saved_tensors
+        desc, ln = ctx.desc, ctx.ln
+        need_x = ctx.needs_input_grad[0]
+        need_p = any(ctx.needs_input_grad[1:5] if ln else ctx.needs_input_grad[1:3])
+        dev = dy.device
+        new = lambda t: torch.empty_like(t)  # noqa: E731
+        dx = new(xc) if need_x else None
+        dw = new(wc) if need_p else None
+        db = torch.empty(wc.shape[:-1], dtype=torch.float32, device=dev) if need_p else None
+        dlw = new(lwc) if need_p and ln else None
+        dlb = new(lbc) if need_p and ln else None
+        ws = None
+        if ln or mc is not None:
+            ws = torch.empty(native.layer_workspace_bytes(desc), dtype=torch.uint8, device=dev)  # torch's caching allocator
+        native.layer_backward(desc, xc, wc, lwc, lbc, pre, stat, mc, dy.contiguous(), dx, dw, db, dlw, dlb, ws)
+        want = ctx.needs_input_grad
+        return (dx.view(ctx.x_shape) if want[0] else None, dw if want[1] else None, db if want[2] else None,
+                dlw if ln and want[3] else None, dlb if ln and want[4] else None, None, None, None, None, None)
+
+
+def _dropout_mask(p: float, shape, device):
+    """Dropout's multipliers (0 or 1 / (1 - p)), drawn exactly as nn.Dropout draws them."""
+    return F.dropout(torch.ones(shape, dtype=torch.float32, device=device), p, True)
+
+
+def normed_linear_apply(m, x, mask=None):
+    """One module of a `layers.mlp()` Sequential: a NormedLinear (Mish or SimNorm) or a plain nn.Linear."""
+    if isinstance(m, layers.NormedLinear):
+        if isinstance(m.act, layers.SimNorm):
+            kind, sd = native.LAYER_SIMNORM, m.act.dim
+        elif isinstance(m.act, nn.Mish):
+            kind, sd = native.LAYER_MISH, 0
+        else:
+            raise native.NativeError(f"the library's layer has Mish and SimNorm only (got {m.act!r})")
+        if mask is None and m.dropout is not None and m.training and m.dropout.p > 0:
+            mask = _dropout_mask(m.dropout.p, (*x.shape[:-1], m.out_features), x.device)
+        return LayerFn.apply(x, m.weight, m.bias, m.ln.weight, m.ln.bias, mask, kind, False, sd, m.ln.eps)
+    if type(m) is nn.Linear and m.bias is not None:
+        return LayerFn.apply(x, m.weight, m.bias, None, None, mask, native.LAYER_LINEAR, False, 0, 0.0)
+    raise native.NativeError(f"mlp_apply: no library layer for {m!r}")
+
+
+def mlp_apply(seq, x):
+    """`seq(x)` for a `layers.mlp()` Sequential, every layer in the library."""
+    for m in seq:
+        x = normed_linear_apply(m, x)
+    return x
+
+
+def ensemble_apply(params, x):
+    """`QEnsemble.apply_params(params, x)` for a `layers.StackedMLPParams`: x [..., K] -> [n, ..., out]; the first layer reads the
+    one x for every member (shared_x), so its dx is the sum over members."""
+    l0, l1, l2 = params.layer(0), params.layer(1), params.layer(2)
+    shared = params.n > 1  # (one member: its x is simply [1, ..., K])
+    h = LayerFn.apply(x if shared else x.unsqueeze(0), l0.weight, l0.bias, l0.ln.weight, l0.ln.bias, None, native.LAYER_MISH, shared, 0,
+                      1e-5)
+    h = LayerFn.apply(h, l1.weight, l1.bias, l1.ln.weight, l1.ln.bias, None, native.LAYER_MISH, False, 0, 1e-5)
+    return LayerFn.apply(h, l2.weight, l2.bias, None, None, None, native.LAYER_LINEAR, False, 0, 0.0)

@@ -42,6 +42,7 @@ UNITS+=("ploss|k_policy_loss.hip|${TDMPC2_FLAGS_ploss:-}")
 UNITS+=("refresh|k_refresh.hip|${TDMPC2_FLAGS_refresh:-}")
 UNITS+=("pixbatch|k_pixel_batch.hip|${TDMPC2_FLAGS_pixbatch:-}")
 UNITS+=("buffer|k_buffer.hip|${TDMPC2_FLAGS_buffer:-}")
+UNITS+=("lgrad|k_layer_grad.hip|${TDMPC2_FLAGS_lgrad:-}")  # trainable layer: NormedLinear forward / backward, its own C ABI (tdmpc2_layer_*)
 for ap in ${APADS}; do
     UNITS+=("fused${ap}|k_fused.hip|-DTU_APAD=${ap} ${TDMPC2_FLAGS_fused:-}")
     UNITS+=("cluster${ap}|k_cluster.hip|-DTU_APAD=${ap} ${TDMPC2_FLAGS_cluster:-}")

@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "tdmpc2_plan_pix_batch_reserve", "tdmpc2_plan_encode_pix_batch",
     "tdmpc2_buffer_create", "tdmpc2_buffer_destroy", "tdmpc2_buffer_add", "tdmpc2_buffer_load", "tdmpc2_buffer_sample",
     "tdmpc2_buffer_stats", "tdmpc2_buffer_set_call_counter",
+    "tdmpc2_layer_workspace_bytes", "tdmpc2_layer_forward", "tdmpc2_layer_backward",
 ]
 
 NET_DYNAMICS, NET_REWARD, NET_PI, NET_Q, NET_TERMINATION, NET_TARGET_Q = range(6)
@@ -139,6 +140,14 @@ class BufferCfg(C.Structure):  # struct tdmpc2_buffer_cfg
 class BufferInfo(C.Structure):  # struct tdmpc2_buffer_info
     _fields_ = [("num_eps", C.c_uint64), ("live_steps", C.c_uint64), ("cursor", C.c_uint64), ("eligible", C.c_uint32),
                 ("next_call", C.c_uint32)]
+
+
+LAYER_LINEAR, LAYER_MISH, LAYER_SIMNORM = range(3)  # enum TDMPC2_LAYER_*
+
+
+class LayerDesc(C.Structure):  # struct tdmpc2_layer_desc
+    _fields_ = [(n, C.c_int32) for n in ("kind", "groups", "rows", "in_dim", "out_dim", "shared_x", "simnorm_dim")] + \
+               [("ln_eps", C.c_float)]
 
 
 class Debug(C.Structure):
@@ -301,6 +310,12 @@ def _open(path):
     lib.tdmpc2_buffer_stats.restype = i32
     lib.tdmpc2_buffer_set_call_counter.argtypes = [vp, C.c_uint32, vp]
     lib.tdmpc2_buffer_set_call_counter.restype = i32
+    lib.tdmpc2_layer_workspace_bytes.argtypes = [C.POINTER(LayerDesc), C.POINTER(C.c_size_t)]
+    lib.tdmpc2_layer_workspace_bytes.restype = i32
+    lib.tdmpc2_layer_forward.argtypes = [C.POINTER(LayerDesc)] + [vp] * 10
+    lib.tdmpc2_layer_forward.restype = i32
+    lib.tdmpc2_layer_backward.argtypes = [C.POINTER(LayerDesc)] + [vp] * 14 + [C.c_size_t, vp]
+    lib.tdmpc2_layer_backward.restype = i32
     if lib.tdmpc2_plan_abi_version() != ABI_VERSION:
         raise NativeError(f"ABI version mismatch: library {lib.tdmpc2_plan_abi_version()}, binding {ABI_VERSION}")
     return lib
@@ -1374,3 +1389,60 @@ class NativeBuffer:
     def set_call_counter(self, value: int):
         with torch.cuda.device(self.device):
             self._check(self.lib.tdmpc2_buffer_set_call_counter(self._h, int(value) & 0xFFFFFFFF, self._stream()))
+
+
+# ---------------------------------------------------------------- trainable layer (tdmpc2_layer_*)
+LAYER_CALLS = 0  # library layer calls made through the wrappers below (forward + backward): what the tests of the flag count
+
+
+def layer_desc(kind: int, groups: int, rows: int, in_dim: int, out_dim: int, shared_x: bool = False, simnorm_dim: int = 0,
+               ln_eps: float = 1e-5) -> LayerDesc:
+    return LayerDesc(kind=int(kind), groups=int(groups), rows=int(rows), in_dim=int(in_dim), out_dim=int(out_dim),
+                     shared_x=int(bool(shared_x)), simnorm_dim=int(simnorm_dim), ln_eps=float(ln_eps))
+
+
+def _layer_check(rc: int):
+    if rc != 0:
+        raise NativeError(f"tdmpc2_layer error {rc}: {load_library().tdmpc2_last_error().decode()}")
+
+
+def layer_workspace_bytes(desc: LayerDesc) -> int:
+    n = C.c_size_t()
+    _layer_check(load_library().tdmpc2_layer_workspace_bytes(C.byref(desc), C.byref(n)))
+    return int(n.value)
+
+
+def _layer_tensors(what, device, **ts):
+    for name, t in ts.items():
+        if t is None:
+            continue
+        if t.device != device or t.dtype != torch.float32 or not t.is_contiguous():
+            raise NativeError(f"{what}: {name} must be a contiguous fp32 tensor on {device} (got {t.dtype}, {t.device}, "
+                              f"contiguous={t.is_contiguous()})")
+
+
+def layer_forward(desc: LayerDesc, x, w, b, ln_w=None, ln_b=None, mask=None, y=None, pre=None, stat=None):
+    """tdmpc2_layer_forward on the current stream; tensors are contiguous fp32 on one GPU (checked), outputs are written in place."""
+    global LAYER_CALLS
+    if x.device.type != "cuda":
+        raise NativeError(f"layer_forward runs on an MI355X only (device {x.device}); there is no CPU fallback")
+    _layer_tensors("layer_forward", x.device, x=x, w=w, b=b, ln_w=ln_w, ln_b=ln_b, mask=mask, y=y, pre=pre, stat=stat)
+    LAYER_CALLS += 1
+    with torch.cuda.device(x.device):
+        _layer_check(load_library().tdmpc2_layer_forward(C.byref(desc), _ptr(x), _ptr(w), _ptr(b), _ptr(ln_w), _ptr(ln_b), _ptr(mask),
+                                                         _ptr(y), _ptr(pre), _ptr(stat), torch.cuda.current_stream(x.device).cuda_stream))
+
+
+def layer_backward(desc: LayerDesc, x, w, ln_w, ln_b, pre, stat, mask, dy, dx=None, dw=None, db=None, dln_w=None, dln_b=None, ws=None):
+    """tdmpc2_layer_backward on the current stream; `ws` is a uint8 tensor of at least layer_workspace_bytes(desc) bytes."""
+    global LAYER_CALLS
+    if dy.device.type != "cuda":
+        raise NativeError(f"layer_backward runs on an MI355X only (device {dy.device}); there is no CPU fallback")
+    _layer_tensors("layer_backward", dy.device, x=x, w=w, ln_w=ln_w, ln_b=ln_b, pre=pre, stat=stat, mask=mask, dy=dy, dx=dx, dw=dw,
+                   db=db, dln_w=dln_w, dln_b=dln_b)
+    LAYER_CALLS += 1
+    with torch.cuda.device(dy.device):
+        _layer_check(load_library().tdmpc2_layer_backward(
+            C.byref(desc), _ptr(x), _ptr(w), _ptr(ln_w), _ptr(ln_b), _ptr(pre), _ptr(stat), _ptr(mask), _ptr(dy), _ptr(dx), _ptr(dw),
+            _ptr(db), _ptr(dln_w), _ptr(dln_b), _ptr(ws), 0 if ws is None else ws.numel() * ws.element_size(),
+            torch.cuda.current_stream(dy.device).cuda_stream))

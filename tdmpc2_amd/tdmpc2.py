@@ -76,6 +76,15 @@ class TDMPC2(torch.nn.Module):
         self._one = torch.ones(1, dtype=torch.uint8, device=self.device) if self.device.type == "cuda" else None
         self._zero = torch.zeros(1, dtype=torch.uint8, device=self.device) if self.device.type == "cuda" else None
 
+    @property
+    def native_autograd(self) -> bool:
+        """True: the model's MLPs run through the library's trainable layer, forward and backward (WorldModel.native_autograd)."""
+        return self.model.native_autograd
+
+    @native_autograd.setter
+    def native_autograd(self, on: bool):
+        self.model.native_autograd = bool(on)
+
     # ------------------------------------------------------------------ checkpoint I/O
     def save(self, fp):
         """reference tdmpc2.py:72-79."""

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import checkpoint, layers
+from . import autograd, checkpoint, layers
 
 
 def _symexp(x):
@@ -52,6 +52,9 @@ class WorldModel(nn.Module):
         self._target_Qs_params = layers.StackedMLPParams(cfg.num_q, L + A + T, M, max(cfg.num_bins, 1), as_buffer=True)
         self.register_buffer("log_std_min", torch.tensor(float(cfg.log_std_min)))
         self.register_buffer("log_std_dif", torch.tensor(float(cfg.log_std_max)) - self.log_std_min)
+        # True (and the input on the GPU): the MLPs of encode (state), next, reward, termination, pi and Q run through the library's
+        # trainable layer (tdmpc2_amd/autograd.py), so loss.backward() computes their gradients in HIP; off by default -- the modules
+        self.native_autograd = False
         self.apply(self._weight_init)
         self._register_state_dict_hook(self._add_meta_keys)
         self._register_load_state_dict_pre_hook(self._convert_incoming, with_module=True)
@@ -110,30 +113,43 @@ class WorldModel(nn.Module):
             emb = emb.repeat(x.shape[0], 1)
         return torch.cat([x, emb], dim=-1)
 
+    def _mlp(self, seq, x):
+        if self.native_autograd and x.is_cuda:
+            return autograd.mlp_apply(seq, x)
+        return seq(x)
+
     def encode(self, obs, task):
         """reference world_model.py:103-112, including the [T, B, C, H, W] pixel-sequence branch."""
         if self.cfg.multitask:
             obs = self.task_emb(obs, task)
         if self.cfg.obs == "rgb" and obs.ndim == 5:
             return torch.stack([self._encoder[self.cfg.obs](o) for o in obs])
+        if self.cfg.obs == "state":
+            return self._mlp(self._encoder[self.cfg.obs], obs)
         return self._encoder[self.cfg.obs](obs)
 
     def next(self, z, a, task):
         if self.cfg.multitask:
             z = self.task_emb(z, task)
-        return self._dynamics(torch.cat([z, a], dim=-1))
+        return self._mlp(self._dynamics, torch.cat([z, a], dim=-1))
 
     def reward(self, z, a, task):
         if self.cfg.multitask:
             z = self.task_emb(z, task)
-        return self._reward(torch.cat([z, a], dim=-1))
+        return self._mlp(self._reward, torch.cat([z, a], dim=-1))
+
+    def termination(self, z, task, unnormalized=False):
+        """reference world_model.py:132-141 (episodic models only)."""
+        assert task is None
+        logit = self._mlp(self._termination, z)
+        return logit if unnormalized else torch.sigmoid(logit)
 
     def pi(self, z, task):
         """Returns (action, info) like the reference (world_model.py:144-184, math.py:12-29): info carries 'mean', 'log_std',
         'action_prob', 'entropy' and 'scaled_entropy' (a dict; the reference's TensorDict has the same keys)."""
         if self.cfg.multitask:
             z = self.task_emb(z, task)
-        mean, log_std = self._pi(z).chunk(2, dim=-1)
+        mean, log_std = self._mlp(self._pi, z).chunk(2, dim=-1)
         log_std = self.log_std_min + 0.5 * self.log_std_dif * (torch.tanh(log_std) + 1)
         eps = torch.randn_like(mean)
         if self.cfg.multitask:
@@ -155,7 +171,11 @@ class WorldModel(nn.Module):
         assert return_type in {"min", "avg", "all"}
         if self.cfg.multitask:
             z = self.task_emb(z, task)
-        out = self._Qs(torch.cat([z, a], dim=-1))
+        za = torch.cat([z, a], dim=-1)
+        if self.native_autograd and za.is_cuda:
+            out = autograd.ensemble_apply(self._Qs.params, za)
+        else:
+            out = self._Qs(za)
         if return_type == "all":
             return out
         qidx = torch.randperm(self.cfg.num_q, device=out.device)[:2]
