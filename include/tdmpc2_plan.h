@@ -778,6 +778,63 @@ int tdmpc2_layer_backward(const tdmpc2_layer_desc *desc, const float *x, const f
                           const float *pre, const float *stat, const float *mask, const float *dy, float *dx, float *dw, float *db,
                           float *dln_w, float *dln_b, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- optimiser step (additions to ABI 14): gradient clip and Adam over flat arenas --------------------------------------------
+ * What the learner does between backward and the re-pack (tdmpc2/tdmpc2.py:22-31, 227-230, 307-310): clip_grad_norm_ over an
+ * optimiser's parameters, Adam, zero_grad -- in three launches whatever the number of tensors.  A handle of its own: it shares
+ * nothing with a planner handle, and the re-pack stays tdmpc2_plan_refresh_weights, issued after the step.  No weight decay,
+ * amsgrad or maximize (the reference uses none).
+ *   Segments  a handle covers a fixed list of fp32 parameter tensors ("segments"), each in a group with its own lr (the reference's
+ *             encoder group; an empty group is allowed).  Parameters stay the model's own tensors, addressed by pointer, aligned to
+ *             4 bytes or better (a view into a stacked tensor may be misaligned for 16-byte accesses: whole quads of such a segment
+ *             are read and written as four dwords, its 1 .. 3 tail elements one by one).
+ *   Arenas    gradients and both moments are three flat fp32 arrays of arena_floats floats that the CALLER owns and passes to every
+ *             step; segment i starts at offsets[i] (tdmpc2_optim_layout), every segment padded to a multiple of 4 floats.  The
+ *             padding must be zero at the first step and stays zero: the kernels write zeros there.
+ *   Step      in stream order (tdmpc2_amd/csrc/optim_route.h: chunks, the norm's order and its longest addition chain):
+ *             1. norm = L2 norm of the whole gradient arena in a fixed order -- no float atomics, no waits between workgroups,
+ *                bit-identical from run to run and independent of the grid;
+ *             2. c = min(1, max_norm / (norm + 1e-6)) in fp32 (torch's form; always multiplied in; a NaN norm gives a NaN c);
+ *             3. device scalars, so that a captured step advances on replay: step += 1 (int64), b1p *= beta1, b2p *= beta2 (fp64
+ *                running products from 1, betas widened from fp32; no pow), ss_g = fp32(lr_g / (1 - b1p)) per group and
+ *                bc = fp32(sqrt(1 - b2p)), computed in fp64 and rounded once;
+ *             4. per element, every operation a separately rounded fp32 operation in this order (divide and sqrt correctly
+ *                rounded, no contraction), a1 = fp32(1 - beta1), a2 = fp32(1 - beta2) rounded once from the fp64 difference:
+ *                    g = g * c;  m = m + (g - m) * a1;  v = v * beta2 + (g * a2) * g;  d = sqrt(v) / bc + eps;  p = p - ss_g * (m / d)
+ *             5. zero_grad != 0: g = 0 in the same pass (zero_grad with the tensors kept); zero_grad == 0: the CLIPPED gradient is
+ *                stored back, as torch's clip_grad_norm_ scales in place.
+ *             EVERY segment is stepped on every call: a zero gradient counts as a gradient.  This equals the reference, where each
+ *             parameter of an optimiser receives a gradient on every step.  Non-finite gradients propagate exactly as in torch with
+ *             error_if_nonfinite=False: nothing filters them.
+ *   norm_out  DEVICE pointer to one float, or NULL.  A step allocates nothing, copies nothing from the host and never
+ *             synchronises: it can be captured in a hipGraph.
+ * TDMPC2_ERR_INVALID before the device is touched: NULL cfg / out / lr / segs; n_segs < 1, n_groups < 1, a count < 1, a group out
+ * of range, a NULL param; betas outside [0, 1), eps <= 0, max_norm <= 0, or NaN in any of them; a NULL arena or handle in step;
+ * step < 0 in set_step.  An arena of more than 2^31 chunks of 2048 floats: TDMPC2_ERR_UNSUPPORTED. */
+typedef struct tdmpc2_optim tdmpc2_optim_t;
+typedef struct tdmpc2_optim_seg {
+    float *param;      /* DEVICE pointer to `count` contiguous floats */
+    int64_t count;
+    int32_t group, reserved;
+} tdmpc2_optim_seg;
+typedef struct tdmpc2_optim_cfg {
+    int32_t device, n_segs, n_groups, reserved;
+    float beta1, beta2, eps, max_norm;
+    const float *lr;                 /* [n_groups], host */
+    const tdmpc2_optim_seg *segs;    /* [n_segs], host */
+} tdmpc2_optim_cfg;
+/* offsets [n_segs] and the length of each arena, in floats.  Host only: never touches a device. */
+int tdmpc2_optim_layout(const tdmpc2_optim_cfg *cfg, int64_t *offsets, int64_t *arena_floats);
+/* Validates, then makes the handle's one device allocation (segment table, scalars, the norm's partial sums) and uploads it once. */
+int tdmpc2_optim_create(const tdmpc2_optim_cfg *cfg, tdmpc2_optim_t **out);
+void tdmpc2_optim_destroy(tdmpc2_optim_t *o);
+int tdmpc2_optim_step(tdmpc2_optim_t *o, float *grad, float *exp_avg, float *exp_avg_sq, int zero_grad, float *norm_out,
+                      void *stream);
+/* The device's step counter; synchronises `stream`. */
+int tdmpc2_optim_get_step(tdmpc2_optim_t *o, int64_t *step, void *stream);
+/* Resume a saved optimiser: step, and b1p / b2p rebuilt by the same repeated fp64 product, so the scalars of the next step are
+ * bit-identical to those of an uninterrupted run.  Synchronises `stream`; host cost O(step). */
+int tdmpc2_optim_set_step(tdmpc2_optim_t *o, int64_t step, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,10 @@ class Config:
     # policy loss and its running Q scale (config.yaml:25,47): read by TDMPC2.policy_loss, the forward of update_pi
     entropy_coef: float = 1e-4
     tau: float = 0.01
+    # optimisers (config.yaml:22-24): read by TDMPC2.optim / pi_optim
+    lr: float = 3e-4
+    enc_lr_scale: float = 0.3
+    grad_clip_norm: float = 20.0
     # actor (config.yaml:44-47)
     log_std_min: float = -10.0
     log_std_max: float = 2.0

@@ -39,6 +39,8 @@ ABI_SYMBOLS = [
     "tdmpc2_buffer_create", "tdmpc2_buffer_destroy", "tdmpc2_buffer_add", "tdmpc2_buffer_load", "tdmpc2_buffer_sample",
     "tdmpc2_buffer_stats", "tdmpc2_buffer_set_call_counter",
     "tdmpc2_layer_workspace_bytes", "tdmpc2_layer_forward", "tdmpc2_layer_backward",
+    "tdmpc2_optim_layout", "tdmpc2_optim_create", "tdmpc2_optim_destroy", "tdmpc2_optim_step", "tdmpc2_optim_get_step",
+    "tdmpc2_optim_set_step",
 ]
 
 NET_DYNAMICS, NET_REWARD, NET_PI, NET_Q, NET_TERMINATION, NET_TARGET_Q = range(6)
@@ -148,6 +150,16 @@ LAYER_LINEAR, LAYER_MISH, LAYER_SIMNORM = range(3)  # enum TDMPC2_LAYER_*
 class LayerDesc(C.Structure):  # struct tdmpc2_layer_desc
     _fields_ = [(n, C.c_int32) for n in ("kind", "groups", "rows", "in_dim", "out_dim", "shared_x", "simnorm_dim")] + \
                [("ln_eps", C.c_float)]
+
+
+class OptimSeg(C.Structure):  # struct tdmpc2_optim_seg
+    _fields_ = [("param", C.c_void_p), ("count", C.c_int64), ("group", C.c_int32), ("reserved", C.c_int32)]
+
+
+class OptimCfg(C.Structure):  # struct tdmpc2_optim_cfg
+    _fields_ = [("device", C.c_int32), ("n_segs", C.c_int32), ("n_groups", C.c_int32), ("reserved", C.c_int32),
+                ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("max_norm", C.c_float),
+                ("lr", C.POINTER(C.c_float)), ("segs", C.POINTER(OptimSeg))]
 
 
 class Debug(C.Structure):
@@ -316,6 +328,19 @@ def _open(path):
     lib.tdmpc2_layer_forward.restype = i32
     lib.tdmpc2_layer_backward.argtypes = [C.POINTER(LayerDesc)] + [vp] * 14 + [C.c_size_t, vp]
     lib.tdmpc2_layer_backward.restype = i32
+    i64p = C.POINTER(C.c_int64)
+    lib.tdmpc2_optim_layout.argtypes = [C.POINTER(OptimCfg), i64p, i64p]
+    lib.tdmpc2_optim_layout.restype = i32
+    lib.tdmpc2_optim_create.argtypes = [C.POINTER(OptimCfg), C.POINTER(vp)]
+    lib.tdmpc2_optim_create.restype = i32
+    lib.tdmpc2_optim_destroy.argtypes = [vp]
+    lib.tdmpc2_optim_destroy.restype = None
+    lib.tdmpc2_optim_step.argtypes = [vp, vp, vp, vp, i32, vp, vp]
+    lib.tdmpc2_optim_step.restype = i32
+    lib.tdmpc2_optim_get_step.argtypes = [vp, i64p, vp]
+    lib.tdmpc2_optim_get_step.restype = i32
+    lib.tdmpc2_optim_set_step.argtypes = [vp, C.c_int64, vp]
+    lib.tdmpc2_optim_set_step.restype = i32
     if lib.tdmpc2_plan_abi_version() != ABI_VERSION:
         raise NativeError(f"ABI version mismatch: library {lib.tdmpc2_plan_abi_version()}, binding {ABI_VERSION}")
     return lib
@@ -1446,3 +1471,90 @@ def layer_backward(desc: LayerDesc, x, w, ln_w, ln_b, pre, stat, mask, dy, dx=No
             C.byref(desc), _ptr(x), _ptr(w), _ptr(ln_w), _ptr(ln_b), _ptr(pre), _ptr(stat), _ptr(mask), _ptr(dy), _ptr(dx), _ptr(dw),
             _ptr(db), _ptr(dln_w), _ptr(dln_b), _ptr(ws), 0 if ws is None else ws.numel() * ws.element_size(),
             torch.cuda.current_stream(dy.device).cuda_stream))
+
+
+# ---------------------------------------------------------------- optimiser step (tdmpc2_optim_*)
+def optim_cfg(segs, lrs, beta1: float, beta2: float, eps: float, max_norm: float, device_index: int = 0):
+    """struct tdmpc2_optim_cfg; segs: (device pointer, count, group) per segment, lrs: one per group.  Returns (cfg, keep): the
+    arrays the cfg points to live as long as `keep` does."""
+    seg_arr = (OptimSeg * max(len(segs), 1))()
+    for i, (ptr, count, group) in enumerate(segs):
+        seg_arr[i] = OptimSeg(int(ptr) if ptr else None, int(count), int(group), 0)
+    lr_arr = (C.c_float * max(len(lrs), 1))(*[float(v) for v in lrs])
+    cfg = OptimCfg(device=int(device_index), n_segs=len(segs), n_groups=len(lrs), reserved=0, beta1=float(beta1), beta2=float(beta2),
+                   eps=float(eps), max_norm=float(max_norm), lr=lr_arr, segs=seg_arr)
+    return cfg, (seg_arr, lr_arr)
+
+
+def optim_layout(cfg: OptimCfg):
+    """tdmpc2_optim_layout -> (offsets per segment, floats per arena).  Host only."""
+    lib = load_library()
+    offs, total = (C.c_int64 * max(int(cfg.n_segs), 1))(), C.c_int64()
+    rc = lib.tdmpc2_optim_layout(C.byref(cfg), offs, C.byref(total))
+    if rc != 0:
+        raise NativeError(f"tdmpc2_optim error {rc}: {lib.tdmpc2_last_error().decode()}")
+    return [int(v) for v in offs[:cfg.n_segs]], int(total.value)
+
+
+class NativeOptim:
+    """Owns one `tdmpc2_optim_t`: gradient clip + Adam over three caller-owned flat fp32 arenas, three launches per step."""
+
+    def __init__(self, segs, lrs, beta1, beta2, eps, max_norm, device: torch.device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise NativeError(f"the optimiser step runs on an MI355X only (device {device}); there is no CPU fallback")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.lib = load_library()
+        self.device = device
+        self._h = C.c_void_p()
+        cfg, keep = optim_cfg(segs, lrs, beta1, beta2, eps, max_norm, device.index)
+        self.offsets, self.arena_floats = optim_layout(cfg)
+        h = C.c_void_p()
+        self._check(self.lib.tdmpc2_optim_create(C.byref(cfg), C.byref(h)))
+        del keep
+        self._h = h
+
+    def _check(self, rc: int):
+        if rc != 0:
+            raise NativeError(f"tdmpc2_optim error {rc}: {self.lib.tdmpc2_last_error().decode()}")
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.lib.tdmpc2_optim_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _arena(self, name, t):
+        if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != self.arena_floats:
+            raise NativeError(f"optim step: {name} must be a contiguous fp32 tensor of {self.arena_floats} floats on {self.device}")
+        return _ptr(t)
+
+    def step(self, grad, exp_avg, exp_avg_sq, zero_grad: bool = True, norm_out: Optional[torch.Tensor] = None):
+        """tdmpc2_optim_step on the current stream; norm_out: a one-element fp32 tensor on the device, or None."""
+        if norm_out is not None:
+            _chk_tensor("norm_out", norm_out, torch.float32, tuple(norm_out.shape), self.device)
+            if norm_out.numel() != 1:
+                raise NativeError("optim step: norm_out holds one float")
+        with torch.cuda.device(self.device):
+            self._check(self.lib.tdmpc2_optim_step(self._h, self._arena("grad", grad), self._arena("exp_avg", exp_avg),
+                                                   self._arena("exp_avg_sq", exp_avg_sq), int(bool(zero_grad)), _ptr(norm_out),
+                                                   self._stream()))
+
+    def get_step(self) -> int:
+        n = C.c_int64()
+        with torch.cuda.device(self.device):
+            self._check(self.lib.tdmpc2_optim_get_step(self._h, C.byref(n), self._stream()))
+        return int(n.value)
+
+    def set_step(self, step: int):
+        with torch.cuda.device(self.device):
+            self._check(self.lib.tdmpc2_optim_set_step(self._h, int(step), self._stream()))

@@ -66,6 +66,7 @@ class TDMPC2(torch.nn.Module):
         self.native_refresh = False
         self._reuse_shift = False
         self._planner: Optional[NativePlanner] = None
+        self._optim = self._pi_optim = None  # made by the first read of `optim` / `pi_optim`: nothing for a planning-only user
         self._planner_log_std = None
         self._prev_mean_batch = None
         # Philox stream of the in-library noise: cfg.seed in the low word, the rank in the high word, so that env-sharded
@@ -157,6 +158,42 @@ class TDMPC2(torch.nn.Module):
         if self.native_encoder and self.cfg.obs == "state":
             sd.update({k: v for k, v in self.model.state_dict().items() if torch.is_tensor(v) and k.startswith("_encoder.state.")})
         return sd
+
+    # ------------------------------------------------------------------ optimisers (reference tdmpc2.py:22-31)
+    @property
+    def optim(self):
+        """The model's optimiser with the reference's groups (the encoder at lr * enc_lr_scale; the termination head and the task
+        embedding only where the model has them), clipping at cfg.grad_clip_norm: a tdmpc2_amd.ClipAdam, made at first use.  From
+        then on every parameter's .grad is a view into its gradient arena."""
+        if self._optim is None:
+            from .optim import ClipAdam
+            cfg, m = self.cfg, self.model
+            self._optim = ClipAdam([
+                {"params": m._encoder.parameters(), "lr": cfg.lr * cfg.enc_lr_scale},
+                {"params": m._dynamics.parameters()},
+                {"params": m._reward.parameters()},
+                {"params": m._termination.parameters() if cfg.episodic else []},
+                {"params": m._Qs.parameters()},
+                {"params": m._task_emb.parameters() if cfg.multitask else []},
+            ], lr=cfg.lr, max_norm=cfg.grad_clip_norm)
+        return self._optim
+
+    @property
+    def pi_optim(self):
+        """The policy prior's optimiser (reference tdmpc2.py:31: eps = 1e-5), clipping at cfg.grad_clip_norm (tdmpc2.py:227)."""
+        if self._pi_optim is None:
+            from .optim import ClipAdam
+            self._pi_optim = ClipAdam(self.model._pi.parameters(), lr=self.cfg.lr, eps=1e-5, max_norm=self.cfg.grad_clip_norm)
+        return self._pi_optim
+
+    def optimizer_step(self, which: str = "model"):
+        """clip_grad_norm_ + step + zero_grad of `optim` ("model") or `pi_optim` ("pi") in the library, then `sync_planner_weights()`
+        so that the planner's packed weights follow.  Returns the gradient norm (0-d device tensor)."""
+        if which not in ("model", "pi"):
+            raise ValueError(f"optimizer_step: which must be 'model' or 'pi', got {which!r}")
+        norm = (self.optim if which == "model" else self.pi_optim).step()
+        self.sync_planner_weights()
+        return norm
 
     def soft_update_target_Q(self):
         """reference world_model.py:82-86 (the last line of TDMPC2._update, tdmpc2.py:316): `_target_Qs_params` lerped in place
