@@ -835,6 +835,54 @@ int tdmpc2_optim_get_step(tdmpc2_optim_t *o, int64_t *step, void *stream);
  * bit-identical to those of an uninterrupted run.  Synchronises `stream`; host cost O(step). */
 int tdmpc2_optim_set_step(tdmpc2_optim_t *o, int64_t step, void *stream);
 
+/* ---- loss seeds (additions to ABI 14): the four losses of TDMPC2._update and the gradients they send into the layer backward ---
+ * The arithmetic between the last layer's output and loss.backward() (tdmpc2/tdmpc2.py:272-304): consistency (mse of the rollout's
+ * latents against encode(obs[1:])), reward and value (soft_ce: log_softmax against two_hot, math.py:5-9, 58-71), termination
+ * (binary_cross_entropy_with_logits), their coefficient-weighted total, and d total / d (z_pred, reward_logits, q_logits,
+ * term_logit).  No handle, no state: a call is its descriptor, its pointers and, for the forward, a caller-owned workspace.  A call
+ * allocates nothing and never synchronises the host, so forward + backward can be captured in a hipGraph.  No atomics, no wait
+ * between workgroups: the same inputs give the same bits.
+ *   Layout    contiguous fp32 on the current device.  T = steps, B = batch, L = latent_dim, NB = num_bins, Q = num_q.
+ *             z_pred, next_z [T, B, L] (zs[1:], the outputs of `next`, and encode(obs[1:])); reward_logits [T, B, NB]; q_logits
+ *             [Q, T, B, NB] (the layout of Q(..., 'all')); reward, td_target, term_logit, terminated [T, B].  term_logit and
+ *             terminated are both NULL exactly when episodic == 0.
+ *   Descriptor  vmin, vmax, bin_size, rho and the coefficients are fp32 and are widened, never re-derived (bin_size is the
+ *             caller's (vmax - vmin) / (NB - 1)).
+ *   Forward   2 launches.  losses [5] = consistency, reward, value, termination, total and step_means [4, steps] (may be NULL),
+ *             both defined exactly as for tdmpc2_plan_model_losses above.  Per-row terms go to ws (tdmpc2_loss_workspace_bytes) and
+ *             ONE workgroup adds them in the fixed order that tdmpc2_amd/csrc/loss_grad_route.h publishes.
+ *   Backward  1 launch over all row kinds; OVERWRITES the outputs that are not NULL (a NULL output drops its rows from the grid).
+ *             Nothing is saved by the forward: a row's max and sum are computed again.  With g = *grad_total (device float[1];
+ *             NULL = 1) and w_t = rho^t, every per-step constant computed on the host in fp64 and rounded once, g multiplied in as
+ *             one fp32 factor (g = 2 doubles every output bit for bit):
+ *               d_z_pred[t,b,l]        = c_t (z_pred - next_z),             c_t = g fp32(consistency_coef 2 w_t / (T B L))
+ *               d_reward_logits[t,b,k] = c_t (softmax_k S - th_k),          c_t = g fp32(reward_coef w_t / (T B))
+ *               d_q_logits[q,t,b,k]    = the same against td_target[t,b],   c_t = g fp32(value_coef w_t / (T Q B))
+ *               d_term_logit[t,b]      = c (sigmoid(x) - y),                c   = g fp32(termination_coef / (T B))
+ *             th is the two-hot row of math.two_hot (1 - off at the lower bin, off at the upper one, which wraps to bin 0 at vmax
+ *             with off = 0) and S = (1 - off) + off in fp32, as the backward of torch's log_softmax sums its incoming gradient.
+ *   Non-finite targets: a NaN in reward / td_target / next_z / terminated makes NaN exactly the loss terms (that loss, its
+ *             step_means entry, total) and the seed rows that read it; every other output keeps its bits.  +-Inf in reward /
+ *             td_target clamps to vmin / vmax as in two_hot.
+ * TDMPC2_ERR_INVALID before the device is touched: NULL descriptor or required pointer (all six model inputs, losses; backward: the
+ * same inputs); steps outside [1, 8]; batch, latent_dim or num_q < 1; termination pointers that do not match episodic (d_term_logit
+ * included); ws NULL or ws_bytes too small; a backward with all four outputs NULL.  TDMPC2_ERR_UNSUPPORTED, also before the device
+ * is touched: num_bins < 2 (as model_losses refuses it); a grid past 2^31 workgroups. */
+typedef struct tdmpc2_loss_desc {
+    int32_t steps, batch, latent_dim, num_q, num_bins, episodic;
+    float vmin, vmax, bin_size;
+    float rho, consistency_coef, reward_coef, value_coef, termination_coef;
+} tdmpc2_loss_desc;   /* 56 bytes, no padding */
+/* Bytes of workspace a forward call of this descriptor needs.  Host only: never touches a device. */
+int tdmpc2_loss_workspace_bytes(const tdmpc2_loss_desc *d, size_t *ws_bytes);
+int tdmpc2_loss_forward(const tdmpc2_loss_desc *d, const float *z_pred, const float *next_z, const float *reward_logits,
+                        const float *reward, const float *q_logits, const float *td_target, const float *term_logit,
+                        const float *terminated, float *losses, float *step_means, void *ws, size_t ws_bytes, void *stream);
+int tdmpc2_loss_backward(const tdmpc2_loss_desc *d, const float *z_pred, const float *next_z, const float *reward_logits,
+                         const float *reward, const float *q_logits, const float *td_target, const float *term_logit,
+                         const float *terminated, const float *grad_total, float *d_z_pred, float *d_reward_logits,
+                         float *d_q_logits, float *d_term_logit, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

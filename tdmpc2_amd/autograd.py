@@ -2,7 +2,9 @@
 
 `LayerFn` is one NormedLinear (Linear -> dropout mask -> LayerNorm -> Mish or SimNorm) or one plain Linear, forward and backward in
 HIP; `mlp_apply` and `ensemble_apply` walk the modules of tdmpc2_amd/layers.py through it, so that `loss.backward()` over
-`WorldModel.next / reward / pi / Q` computes every MLP gradient in the library.  There is no fallback: a CPU tensor is an error.
+`WorldModel.next / reward / pi / Q` computes every MLP gradient in the library.  `ModelLossFn` / `model_loss` are the four losses of
+`TDMPC2._update` and the gradient seeds of their total (tdmpc2_loss_forward / tdmpc2_loss_backward).  There is no fallback: a CPU
+tensor is an error.
 """
 from __future__ import annotations
 
@@ -103,3 +105,57 @@ def ensemble_apply(params, x):
                       1e-5)
     h = LayerFn.apply(h, l1.weight, l1.bias, l1.ln.weight, l1.ln.bias, None, native.LAYER_MISH, False, 0, 1e-5)
     return LayerFn.apply(h, l2.weight, l2.bias, None, None, None, native.LAYER_LINEAR, False, 0, 0.0)
+
+
+class ModelLossFn(torch.autograd.Function):
+    """(total, parts) = the losses of TDMPC2._update (tdmpc2_loss_forward); backward = the seeds of `total` (tdmpc2_loss_backward).
+    Saves the eight inputs, nothing else: the backward recomputes every row.  `parts` [4] is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, desc, z_pred, next_z, reward_logits, reward, q_logits, td_target, term_logit, terminated):
+        dev = z_pred.device
+        ins = [None if t is None else t.detach().contiguous() for t in
+               (z_pred, next_z, reward_logits, reward, q_logits, td_target, term_logit, terminated)]
+        losses = torch.empty(5, dtype=torch.float32, device=dev)
+        ws = torch.empty(native.loss_workspace_bytes(desc), dtype=torch.uint8, device=dev)  # torch's caching allocator
+        native.loss_forward(desc, *ins, losses=losses, ws=ws)
+        ctx.desc, ctx.episodic = desc, term_logit is not None
+        ctx.shapes = [None if t is None else t.shape for t in (z_pred, reward_logits, q_logits, term_logit)]
+        ctx.save_for_backward(*[t for t in ins if t is not None])
+        parts = losses[:4]
+        ctx.mark_non_differentiable(parts)
+        return losses[4], parts
+
+    @staticmethod
+    def backward(ctx, g_total, _g_parts):
+        saved = list(ctx.saved_tensors)
+        ins = saved + [None] * (8 - len(saved))
+        need = (ctx.needs_input_grad[1], ctx.needs_input_grad[3], ctx.needs_input_grad[5], ctx.episodic and ctx.needs_input_grad[7])
+        src = (ins[0], ins[2], ins[4], ins[6])
+        outs = [torch.empty_like(s) if n else None for n, s in zip(need, src)]
+        if any(o is not None for o in outs):
+            g = g_total.detach().to(torch.float32).reshape(1).contiguous()  # stays on the device: no host read
+            native.loss_backward(ctx.desc, *ins, grad_total=g, d_z_pred=outs[0], d_reward_logits=outs[1], d_q_logits=outs[2],
+                                 d_term_logit=outs[3])
+        dz, drl, dql, dtl = [None if o is None else o.view(s) for o, s in zip(outs, ctx.shapes)]
+        return None, dz, None, drl, None, dql, None, dtl, None
+
+
+def model_loss(cfg, z_pred, next_z, reward_logits, reward, q_logits, td_target, term_logit=None, terminated=None):
+    """The four losses of `TDMPC2._update` (reference tdmpc2.py:272-304) and their total in the library.  z_pred, next_z [T, B, L]
+    (zs[1:] and encode(obs[1:])), reward_logits [T, B, bins], q_logits [num_q, T, B, bins] (Q(..., 'all')), reward, td_target,
+    term_logit, terminated [T, B] or [T, B, 1]; the termination pair is given exactly when cfg.episodic.  Returns (total, parts):
+    the 0-d differentiable total and the detached [4] tensor consistency, reward, value, termination.  The targets (next_z, reward,
+    td_target, terminated) get no gradient; an input that needs none costs no rows of the backward launch.  There is no fallback:
+    a CPU tensor is an error."""
+    if (term_logit is None) != (terminated is None) or (term_logit is not None) != bool(cfg.episodic):
+        raise native.NativeError("model_loss: term_logit and terminated are given exactly when cfg.episodic")
+    if z_pred.dim() != 3 or q_logits.dim() != 4:
+        raise native.NativeError(f"model_loss: z_pred [T, B, L] and q_logits [num_q, T, B, bins] (got {tuple(z_pred.shape)}, "
+                                 f"{tuple(q_logits.shape)})")
+    T, B, L = z_pred.shape
+    desc = native.loss_desc(T, B, L, q_logits.shape[0], q_logits.shape[-1], cfg.episodic, cfg.vmin, cfg.vmax, cfg.bin_size, cfg.rho,
+                            cfg.consistency_coef, cfg.reward_coef, cfg.value_coef, cfg.termination_coef)
+    f32 = lambda t: None if t is None else t.to(torch.float32)  # noqa: E731
+    return ModelLossFn.apply(desc, z_pred, f32(next_z), reward_logits, f32(reward), q_logits, f32(td_target), term_logit,
+                             f32(terminated))

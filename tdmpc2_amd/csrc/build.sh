@@ -16,8 +16,9 @@
 #   k_buffer.hip               replay buffer: episode ring, slice draws, grouped gather, and its own C ABI (tdmpc2_buffer_*)
 #   k_layer_grad.hip           trainable layer: NormedLinear forward / backward, its own C ABI (tdmpc2_layer_*)
 #   k_optim.hip                optimiser step: gradient clip + Adam over flat arenas, its own C ABI (tdmpc2_optim_*); no fp contraction
+#   k_loss_grad.hip            loss seeds: the four losses of _update and their gradients, its own C ABI (tdmpc2_loss_*)
 # Objects are cached under build/ and rebuilt when a source they include is newer (make-style), so an experiment on one
-# family recompiles one file.  TDMPC2_EXTRA_FLAGS (all units), TDMPC2_FLAGS_<unit> (one unit: main, fused, cluster, layered, policy, model, ploss, refresh, pixbatch, buffer, lgrad, optim),
+# family recompiles one file.  TDMPC2_EXTRA_FLAGS (all units), TDMPC2_FLAGS_<unit> (one unit: main, fused, cluster, layered, policy, model, ploss, refresh, pixbatch, buffer, lgrad, optim, lossgrad),
 # TDMPC2_ONLY_APAD=48 (experiment builds: the fused / cluster units of one padding only), TDMPC2_OUT, TDMPC2_BUILD_DIR, JOBS.
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
@@ -48,6 +49,7 @@ UNITS+=("lgrad|k_layer_grad.hip|${TDMPC2_FLAGS_lgrad:-}")  # trainable layer: No
 # optimiser step: its element math is a chain of separately rounded fp32 operations -- at -O3 hipcc fuses a * b + c into v_fma_f32
 # (the _rn intrinsics included) unless contraction is off
 UNITS+=("optim|k_optim.hip|-ffp-contract=off ${TDMPC2_FLAGS_optim:-}")
+UNITS+=("lossgrad|k_loss_grad.hip|${TDMPC2_FLAGS_lossgrad:-}")  # loss seeds: _update's four losses and their gradients, its own C ABI (tdmpc2_loss_*)
 for ap in ${APADS}; do
     UNITS+=("fused${ap}|k_fused.hip|-DTU_APAD=${ap} ${TDMPC2_FLAGS_fused:-}")
     UNITS+=("cluster${ap}|k_cluster.hip|-DTU_APAD=${ap} ${TDMPC2_FLAGS_cluster:-}")

@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "tdmpc2_layer_workspace_bytes", "tdmpc2_layer_forward", "tdmpc2_layer_backward",
     "tdmpc2_optim_layout", "tdmpc2_optim_create", "tdmpc2_optim_destroy", "tdmpc2_optim_step", "tdmpc2_optim_get_step",
     "tdmpc2_optim_set_step",
+    "tdmpc2_loss_workspace_bytes", "tdmpc2_loss_forward", "tdmpc2_loss_backward",
 ]
 
 NET_DYNAMICS, NET_REWARD, NET_PI, NET_Q, NET_TERMINATION, NET_TARGET_Q = range(6)
@@ -160,6 +161,12 @@ class OptimCfg(C.Structure):  # struct tdmpc2_optim_cfg
     _fields_ = [("device", C.c_int32), ("n_segs", C.c_int32), ("n_groups", C.c_int32), ("reserved", C.c_int32),
                 ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("max_norm", C.c_float),
                 ("lr", C.POINTER(C.c_float)), ("segs", C.POINTER(OptimSeg))]
+
+
+class LossDesc(C.Structure):  # struct tdmpc2_loss_desc
+    _fields_ = [(n, C.c_int32) for n in ("steps", "batch", "latent_dim", "num_q", "num_bins", "episodic")] + \
+               [(n, C.c_float) for n in ("vmin", "vmax", "bin_size", "rho", "consistency_coef", "reward_coef", "value_coef",
+                                         "termination_coef")]
 
 
 class Debug(C.Structure):
@@ -341,6 +348,12 @@ def _open(path):
     lib.tdmpc2_optim_get_step.restype = i32
     lib.tdmpc2_optim_set_step.argtypes = [vp, C.c_int64, vp]
     lib.tdmpc2_optim_set_step.restype = i32
+    lib.tdmpc2_loss_workspace_bytes.argtypes = [C.POINTER(LossDesc), C.POINTER(C.c_size_t)]
+    lib.tdmpc2_loss_workspace_bytes.restype = i32
+    lib.tdmpc2_loss_forward.argtypes = [C.POINTER(LossDesc)] + [vp] * 11 + [C.c_size_t, vp]
+    lib.tdmpc2_loss_forward.restype = i32
+    lib.tdmpc2_loss_backward.argtypes = [C.POINTER(LossDesc)] + [vp] * 14
+    lib.tdmpc2_loss_backward.restype = i32
     if lib.tdmpc2_plan_abi_version() != ABI_VERSION:
         raise NativeError(f"ABI version mismatch: library {lib.tdmpc2_plan_abi_version()}, binding {ABI_VERSION}")
     return lib
@@ -1558,3 +1571,77 @@ class NativeOptim:
     def set_step(self, step: int):
         with torch.cuda.device(self.device):
             self._check(self.lib.tdmpc2_optim_set_step(self._h, int(step), self._stream()))
+
+
+# ---------------------------------------------------------------- loss seeds (tdmpc2_loss_*)
+LOSS_CALLS = 0  # library loss calls made through the wrappers below (forward + backward), kept like LAYER_CALLS
+
+
+def loss_desc(steps: int, batch: int, latent_dim: int, num_q: int, num_bins: int, episodic: bool, vmin: float, vmax: float,
+              bin_size: float, rho: float, consistency_coef: float, reward_coef: float, value_coef: float,
+              termination_coef: float) -> LossDesc:
+    return LossDesc(steps=int(steps), batch=int(batch), latent_dim=int(latent_dim), num_q=int(num_q), num_bins=int(num_bins),
+                    episodic=int(bool(episodic)), vmin=float(vmin), vmax=float(vmax), bin_size=float(bin_size), rho=float(rho),
+                    consistency_coef=float(consistency_coef), reward_coef=float(reward_coef), value_coef=float(value_coef),
+                    termination_coef=float(termination_coef))
+
+
+def _loss_check(rc: int):
+    if rc != 0:
+        raise NativeError(f"tdmpc2_loss error {rc}: {load_library().tdmpc2_last_error().decode()}")
+
+
+def loss_workspace_bytes(desc: LossDesc) -> int:
+    n = C.c_size_t()
+    _loss_check(load_library().tdmpc2_loss_workspace_bytes(C.byref(desc), C.byref(n)))
+    return int(n.value)
+
+
+def _loss_shapes(what, desc: LossDesc, **ts):
+    """Element counts of the layouts of include/tdmpc2_plan.h (the library sees pointers only)."""
+    T, B, L, Q, NB = desc.steps, desc.batch, desc.latent_dim, desc.num_q, desc.num_bins
+    want = dict(z_pred=T * B * L, next_z=T * B * L, reward_logits=T * B * NB, reward=T * B, q_logits=Q * T * B * NB, td_target=T * B,
+                term_logit=T * B, terminated=T * B, d_z_pred=T * B * L, d_reward_logits=T * B * NB, d_q_logits=Q * T * B * NB,
+                d_term_logit=T * B, losses=5, step_means=4 * T, grad_total=1)
+    for name, t in ts.items():
+        if t is not None and t.numel() != want[name]:
+            raise NativeError(f"{what}: {name} holds {t.numel()} floats, the descriptor asks for {want[name]}")
+
+
+def loss_forward(desc: LossDesc, z_pred, next_z, reward_logits, reward, q_logits, td_target, term_logit=None, terminated=None,
+                 losses=None, step_means=None, ws=None):
+    """tdmpc2_loss_forward on the current stream; tensors are contiguous fp32 on one GPU (checked); `losses` [5] and `step_means`
+    [4, steps] (optional) are written in place; `ws` is a uint8 tensor of at least loss_workspace_bytes(desc) bytes."""
+    global LOSS_CALLS
+    if z_pred.device.type != "cuda":
+        raise NativeError(f"loss_forward runs on an MI355X only (device {z_pred.device}); there is no CPU fallback")
+    ts = dict(z_pred=z_pred, next_z=next_z, reward_logits=reward_logits, reward=reward, q_logits=q_logits, td_target=td_target,
+              term_logit=term_logit, terminated=terminated, losses=losses, step_means=step_means)
+    _layer_tensors("loss_forward", z_pred.device, **ts)
+    _loss_shapes("loss_forward", desc, **ts)
+    LOSS_CALLS += 1
+    with torch.cuda.device(z_pred.device):
+        _loss_check(load_library().tdmpc2_loss_forward(
+            C.byref(desc), _ptr(z_pred), _ptr(next_z), _ptr(reward_logits), _ptr(reward), _ptr(q_logits), _ptr(td_target),
+            _ptr(term_logit), _ptr(terminated), _ptr(losses), _ptr(step_means), _ptr(ws),
+            0 if ws is None else ws.numel() * ws.element_size(), torch.cuda.current_stream(z_pred.device).cuda_stream))
+
+
+def loss_backward(desc: LossDesc, z_pred, next_z, reward_logits, reward, q_logits, td_target, term_logit=None, terminated=None,
+                  grad_total=None, d_z_pred=None, d_reward_logits=None, d_q_logits=None, d_term_logit=None):
+    """tdmpc2_loss_backward on the current stream; `grad_total` is a one-element fp32 tensor on the device or None (= 1); the
+    outputs that are not None are overwritten."""
+    global LOSS_CALLS
+    if z_pred.device.type != "cuda":
+        raise NativeError(f"loss_backward runs on an MI355X only (device {z_pred.device}); there is no CPU fallback")
+    ts = dict(z_pred=z_pred, next_z=next_z, reward_logits=reward_logits, reward=reward, q_logits=q_logits, td_target=td_target,
+              term_logit=term_logit, terminated=terminated, grad_total=grad_total, d_z_pred=d_z_pred,
+              d_reward_logits=d_reward_logits, d_q_logits=d_q_logits, d_term_logit=d_term_logit)
+    _layer_tensors("loss_backward", z_pred.device, **ts)
+    _loss_shapes("loss_backward", desc, **ts)
+    LOSS_CALLS += 1
+    with torch.cuda.device(z_pred.device):
+        _loss_check(load_library().tdmpc2_loss_backward(
+            C.byref(desc), _ptr(z_pred), _ptr(next_z), _ptr(reward_logits), _ptr(reward), _ptr(q_logits), _ptr(td_target),
+            _ptr(term_logit), _ptr(terminated), _ptr(grad_total), _ptr(d_z_pred), _ptr(d_reward_logits), _ptr(d_q_logits),
+            _ptr(d_term_logit), torch.cuda.current_stream(z_pred.device).cuda_stream))

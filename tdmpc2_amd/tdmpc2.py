@@ -68,6 +68,7 @@ class TDMPC2(torch.nn.Module):
         self._planner: Optional[NativePlanner] = None
         self._optim = self._pi_optim = None  # made by the first read of `optim` / `pi_optim`: nothing for a planning-only user
         self._planner_log_std = None
+        self.last_td_targets = None  # the TD target [H, B, 1] of the last update_model call
         self._prev_mean_batch = None
         # Philox stream of the in-library noise: cfg.seed in the low word, the rank in the high word, so that env-sharded
         # ranks built from one cfg (tdmpc2_amd/dist.py) do not draw identical exploration noise; a per-call counter is
@@ -530,6 +531,62 @@ class TDMPC2(torch.nn.Module):
         res = self.model_losses_latent(z0, next_z, action, reward, td, terminated, task, want=want)
         res["td_targets"] = td
         return res
+
+    # ------------------------------------------------------------------ the model half of _update as one method
+    def update_model(self, obs, action, reward, terminated=None, task=None, td_targets=None, pi_eps=None, qidx=None):
+        """The model half of `_update` (reference tdmpc2.py:260-310: everything but `update_pi` and the target-Q soft update), every
+        piece in the library: obs [H+1, B, *], action [H, B, A], reward / terminated [H, B, 1], task [B].  In order:
+          1. under no_grad, next_z = encode(obs[1:]) and the TD target (`_td_target`, or `td_targets` [H, B, 1] as given; `pi_eps` /
+             `qidx` pin its noise and heads; the target used stays readable as `last_td_targets`);
+          2. model.train();
+          3. the rollout through `model.next`, then `Q(..., 'all')`, `reward` and (episodic) `termination` under `native_autograd`;
+          4. `autograd.model_loss` and `total.backward()`;
+          5. `optimizer_step("model")`: clip, Adam, zero_grad and the planner's re-pack;
+          6. model.eval().
+        Returns consistency_loss, reward_loss, value_loss, termination_loss, total_loss and grad_norm as 0-d device tensors.
+        Raises NativeError when `native_autograd` is off: there is no torch path.  It equals the reference when cfg.dropout == 0:
+        the port's QEnsemble has no dropout in any mode, where the reference's Q heads drop inputs of their first layer in
+        train mode."""
+        from . import autograd
+        from .native import NativeError
+        if not self.native_autograd:
+            raise NativeError("update_model runs the model's layers and losses in the library: set native_autograd = True")
+        cfg = self.cfg
+        obs = obs.to(self.device)
+        action = action.to(self.device, torch.float32)
+        reward = reward.to(self.device, torch.float32)
+        H, B = action.shape[0], action.shape[1]
+        if terminated is None:
+            terminated = torch.zeros(H, B, 1, device=self.device)
+        terminated = terminated.to(self.device, torch.float32)
+        if task is not None:
+            task = torch.as_tensor(task, device=self.device)
+        self.optim  # noqa: B018  (made before backward: every .grad is then a view into its gradient arena)
+        with torch.no_grad():
+            next_z = self.model.encode(obs[1:], task)
+            if td_targets is None:
+                td_targets = self._td_target(next_z, reward, terminated, task, pi_eps=pi_eps, qidx=qidx)
+            td_targets = td_targets.to(self.device, torch.float32).reshape(H, B, 1)
+        self.last_td_targets = td_targets
+        self.model.train()
+        try:
+            z = self.model.encode(obs[0], task)
+            zs = [z]
+            for t in range(H):
+                z = self.model.next(z, action[t], task)
+                zs.append(z)
+            _zs, z_pred = torch.stack(zs[:-1]), torch.stack(zs[1:])
+            qs = self.model.Q(_zs, action, task, return_type="all")
+            reward_preds = self.model.reward(_zs, action, task)
+            term_pred = self.model.termination(z_pred, task, unnormalized=True) if cfg.episodic else None
+            total, parts = autograd.model_loss(cfg, z_pred, next_z, reward_preds, reward, qs, td_targets, term_pred,
+                                               terminated if cfg.episodic else None)
+            total.backward()
+            grad_norm = self.optimizer_step("model").clone()
+        finally:
+            self.model.eval()
+        return {"consistency_loss": parts[0], "reward_loss": parts[1], "value_loss": parts[2], "termination_loss": parts[3],
+                "total_loss": total.detach(), "grad_norm": grad_norm}
 
     def _encode_pix_batch(self, obs, H, B):
         """encode(obs[i]) for i = 0 .. H in one library call (tdmpc2_plan_encode_pix_batch): ShiftAug's shifts are drawn on the host
