@@ -638,13 +638,20 @@ __device__ __forceinline__ void epi_barrier(const CT &c) {
 // 32 FT wave + 32 ft + 8 m + 4 hh (two distinct addresses per wave instruction), the LayerNorm affine values from
 // c.gb at the same offsets; `next` = the layer whose epilogue follows this one in program order (null: none).  One barrier inside (the statistics exchange, which also orders every wave's last read of the operand tile
 // before the first write of the new one); the caller adds the one before the next contraction.
-template <int ACT, class CT, bool HASBIAS = true>
+// PIECES: a caller that wants other work between the pieces takes them one at a time through epi_pre / epi_math / epi_store
+// below and places the statistics barrier itself.  One body, so one source for the math and one order of operations: the whole
+// epilogue (EPI_ALL) is the statements below in a row, and every kernel's machine code is what it was before the mask
+// (tools/isa_digest.py).  No kernel takes the pieces apart today: running the held first-layer epilogues under the two-hot heads
+// with them was built and measured slower (profiles/head_shadow_ab.txt).
+enum { EPI_PRE = 1, EPI_MATH = 2, EPI_STORE = 4, EPI_ALL = 7 };
+template <int ACT, class CT, bool HASBIAS = true, int PIECES = EPI_ALL>
 __device__ __forceinline__ void epi_t(const CT &c, f32x16 (&acc)[CT::NST][CT::FT], float osc, float asc, const float *bias,
                                       GB next, float *zcopy) {
     constexpr int FT = CT::FT, NW = CT::NWAVES;
     constexpr float CNT = 32.f * FT;  // features of a row held by one wave
     const int j = c.lane & 31, hh = c.lane >> 5;
     const int poff = 32 * FT * c.wave + 4 * hh;
+    if constexpr (PIECES & EPI_PRE) {
     if constexpr (HASBIAS) {  // else: the caller applied scale and bias already (add_row_bias)
 #pragma unroll
         for (int ft = 0; ft < FT; ++ft) {
@@ -685,8 +692,12 @@ __device__ __forceinline__ void epi_t(const CT &c, f32x16 (&acc)[CT::NST][CT::FT
         }
     }
     TIMER_MARK(c, T_EPI_PRE)
+    }
+    if constexpr (PIECES == EPI_ALL) {
     __syncthreads();
     TIMER_MARK(c, T_EPI_SYNC)
+    }
+    if constexpr (PIECES & EPI_MATH) {
     float rstd[CT::NST], shift[CT::NST];
 #pragma unroll
     for (int st = 0; st < CT::NST; ++st) {
@@ -750,9 +761,27 @@ __device__ __forceinline__ void epi_t(const CT &c, f32x16 (&acc)[CT::NST][CT::FT
             }
         }
     }
+    }
+    if constexpr (PIECES & EPI_STORE) {
     regs_to_tile(c, acc, ACT == 0 ? asc : ACT_SCALE);  // SimNorm outputs lie in [0, 1]: fixed scale
     TIMER_MARK(c, T_EPI_MATH)  // LayerNorm affine + activation + split + tile store (the compiler merges them)
     if (zcopy) park(c, acc, zcopy);
+    }
+}
+// bias + this wave's partial statistics -> c.stats; the caller's barrier follows
+template <class CT>
+__device__ __forceinline__ void epi_pre(const CT &c, f32x16 (&acc)[CT::NST][CT::FT], float osc, const float *bias) {
+    epi_t<0, CT, true, EPI_PRE>(c, acc, osc, 0.f, bias, GB{}, nullptr);
+}
+// Chan combine over c.stats, LayerNorm affine from c.gb, Mish / SimNorm, in place in acc: registers and those two tables only
+template <int ACT, class CT>
+__device__ __forceinline__ void epi_math(const CT &c, f32x16 (&acc)[CT::NST][CT::FT], float asc) {
+    epi_t<ACT, CT, true, EPI_MATH>(c, acc, 0.f, asc, nullptr, GB{}, nullptr);
+}
+// the finished values -> operand form in the tile (+ the optional register-order copy): the only piece that touches the tile
+template <int ACT, class CT>
+__device__ __forceinline__ void epi_store(const CT &c, f32x16 (&acc)[CT::NST][CT::FT], float asc, float *zcopy) {
+    epi_t<ACT, CT, true, EPI_STORE>(c, acc, 0.f, asc, nullptr, GB{}, zcopy);
 }
 
 // acc * osc + bias of the lane's OWN sample rows: brow[st] = the first-layer bias vector of row 32 st + (lane & 31)
@@ -1128,6 +1157,48 @@ __device__ __forceinline__ void first_layers_s(const CT &c, const LayerS &la, co
     kloop_s(c, lb, kb0, kb1, accb);
 }
 
+// ---- actions of step t (tdmpc2.py:176-181) -> operand-form action columns; a thread handles PAIRS of action
+// columns so that one Philox call feeds two samples.  (A function of its own, not a block of the step loop: the same
+// statements, but hipcc then allocates the 64-row split kernel with 54 spilled vector registers instead of 68 and the benched
+// plan rate is 0.8 ... 1.0 % higher: profiles/head_shadow_ab.txt, the "noshadow" legs.)
+template <class CT>
+__device__ __forceinline__ void sample_actions(const CT &c, const RolloutParams &p, const int e, const int row0, const float *mask,
+                                               const float *sm_mean, const float *sm_std, const int t) {
+    constexpr int TROWS = CT::TROWS, NTHR = CT::NTHR;
+    const int tid = c.tid;
+    float *ag = p.actions + ((size_t)e * p.H + t) * p.N * p.A;
+    const int hp = p.Apad / 2;
+    for (int idx = tid; idx < TROWS * hp; idx += NTHR) {
+        const int row = idx / hp, a0 = 2 * (idx % hp);
+        const int n = row0 + row;
+        float v[2] = {0.f, 0.f};
+        const bool sampled = !(p.given_actions || n < p.P);
+        float z[2] = {0.f, 0.f};
+        if (sampled && a0 < p.A && !p.sample_eps) {
+            const unsigned pair = (unsigned)(((size_t)t * (p.N - p.P) + (n - p.P)) * hp + a0 / 2);
+            rng_normal2(p.seed, p.call, SITE_SAMPLE, p.iter, e, pair, z[0], z[1]);
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int a = a0 + u;
+            if (a < p.A) {
+                if (!sampled) {
+                    v[u] = ag[(size_t)n * p.A + a];
+                } else {
+                    float r = z[u];
+                    if (p.sample_eps)
+                        r = p.sample_eps[(size_t)e * p.sample_eps_estride +
+                                         (unsigned)(((size_t)t * (p.N - p.P) + (n - p.P)) * p.A + a)];
+                    v[u] = sample_action(sm_mean[t * p.A + a], sm_std[t * p.A + a], r);
+                }
+                if (mask && !p.given_actions) v[u] *= mask[a];
+                if (!p.given_actions) ag[(size_t)n * p.A + a] = v[u];
+            }
+            put_action(c, row, a, v[u]);
+        }
+    }
+}
+
 // ================================================================ kernel: one CEM iteration's rollouts
 // EP = 1: episodic planning -- the termination head (world_model.py:132-141) is evaluated on every new latent and masks
 // the later rewards and the terminal value (tdmpc2.py:128-136).  Its first layer reads the same z_t columns as the step's
@@ -1189,41 +1260,7 @@ __global__ __launch_bounds__(64 * NW, 2) void ks_rollout(RolloutParams p) {
     float termv = 0.f;  // EP: 1 once any latent of this row's trajectory was classified terminal (tdmpc2.py:133-134)
     TIMER_START(c)
     for (int t = 0; t < p.H; ++t) {
-        // ---- actions of step t (tdmpc2.py:176-181) -> operand-form action columns; a thread handles PAIRS of action
-        // columns so that one Philox call feeds two samples
-        {
-            float *ag = p.actions + ((size_t)e * p.H + t) * p.N * p.A;
-            const int hp = p.Apad / 2;
-            for (int idx = tid; idx < TROWS * hp; idx += NTHR) {
-                const int row = idx / hp, a0 = 2 * (idx % hp);
-                const int n = row0 + row;
-                float v[2] = {0.f, 0.f};
-                const bool sampled = !(p.given_actions || n < p.P);
-                float z[2] = {0.f, 0.f};
-                if (sampled && a0 < p.A && !p.sample_eps) {
-                    const unsigned pair = (unsigned)(((size_t)t * (p.N - p.P) + (n - p.P)) * hp + a0 / 2);
-                    rng_normal2(p.seed, p.call, SITE_SAMPLE, p.iter, e, pair, z[0], z[1]);
-                }
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    const int a = a0 + u;
-                    if (a < p.A) {
-                        if (!sampled) {
-                            v[u] = ag[(size_t)n * p.A + a];
-                        } else {
-                            float r = z[u];
-                            if (p.sample_eps)
-                                r = p.sample_eps[(size_t)e * p.sample_eps_estride +
-                                                 (unsigned)(((size_t)t * (p.N - p.P) + (n - p.P)) * p.A + a)];
-                            v[u] = sample_action(sm_mean[t * p.A + a], sm_std[t * p.A + a], r);
-                        }
-                        if (mask && !p.given_actions) v[u] *= mask[a];
-                        if (!p.given_actions) ag[(size_t)n * p.A + a] = v[u];
-                    }
-                    put_action(c, row, a, v[u]);
-                }
-            }
-        }
+        sample_actions(c, p, e, row0, mask, sm_mean, sm_std, t);  // a_t -> operand-form action columns
         __syncthreads();
         TIMER_MARK(c, T_ACT)
         // ---- first layers of dynamics and reward over the same [z_t | a_t] tile; the raw dynamics accumulators wait for
