@@ -58,8 +58,23 @@ enum { T_KLOOP = 0, T_EPI = 1, T_HEAD = 2, T_ACT = 3, T_PARK = 4, T_TILE = 5, T_
 // ARITH: 0 = f16x2 split (operand tile = hi / lo f16 planes), 1 = exact fp32 (v_mfma_f32_32x32x2_f32; operand tile =
 // fp32 rows of WIDTH + APAD + 4 floats, stride / 4 odd).  Everything but the contraction loops and the tile writes is
 // shared between the two.
+// ks_rollout runs two phases between its GEMMs in latency-hiding forms: the bias vector of the next epilogue staged through LDS
+// (CtxPhT::BIAS_LDS, see gb_prefetch) and z_H held in registers (ks_rollout, ZH_REGS).  The other kernels of the family keep the
+// plain forms (CtxT: same statements as before).  Each form has a compile-time switch for A/B builds (-DKS_NO_BIAS_LDS,
+// -DKS_NO_ZH_REGS); the shipped build defines neither.
+#ifdef KS_NO_BIAS_LDS
+constexpr bool KS_BIAS_LDS = false;
+#else
+constexpr bool KS_BIAS_LDS = true;
+#endif
+#ifdef KS_NO_ZH_REGS
+constexpr bool KS_ZH_REGS = false;
+#else
+constexpr bool KS_ZH_REGS = true;
+#endif
 template <int APAD, int ST = 2, int NW = 8, int AR = 0>
 struct CtxT {
+    static constexpr bool BIAS_LDS = false;
     static constexpr int NST = ST;
     static constexpr int NWAVES = NW;
     static constexpr int ARITH = AR;
@@ -79,6 +94,12 @@ struct CtxT {
     TIMER_FIELDS
     __device__ __forceinline__ float *f32() const { return reinterpret_cast<float *>(act); }  // fp32 view [TROWS][RSF]
     static constexpr __device__ __forceinline__ int RSF() { return RSF_; }
+};
+// ks_rollout's context: the same tile, tables and geometry + the successor epilogue's bias value in flight
+template <int APAD, int ST, int NW, int AR>
+struct CtxPhT : CtxT<APAD, ST, NW, AR> {
+    static constexpr bool BIAS_LDS = KS_BIAS_LDS;
+    mutable float pbias = 0.f;  // the bias value of feature `tid` (one of this wave's 64)
 };
 
 __device__ __forceinline__ float mish_fast(float x) {
@@ -602,10 +623,20 @@ __device__ __forceinline__ void regs_to_tile(const CT &c, const f32x16 (&y)[CT::
 // that ends the epilogue (gb_commit: every wave is past its reads of the previous values), and the next epilogue reads
 // float4s from LDS after its own statistics barrier.  Protocol: every epi_t names its successor's parameters and is
 // followed by epi_barrier().
-struct GB {  // LayerNorm weight / bias pointers of one layer, by value (no address of a kernel argument is taken)
-    const float *g = nullptr, *b = nullptr;
+// The bias vector of the linear layer travels the same way where the kernel asks for it (CT::BIAS_LDS: ks_rollout).  It was the
+// last broadcast read of the epilogue: 8 `global_load_dwordx4` per wave at the epilogue's first instruction, ~1.1 k cycles of
+// exposed latency each time.  It needs no LDS of its own: wave w's slice of the statistics table c.stats (TROWS * 2 >= 64
+// floats) is dead from the end of the Chan combine until that wave's next partials, and thread `tid` of wave w fetches the
+// value of feature `tid`, one of the 64 features wave w owns.  So the commit stores into the wave's OWN slice after the
+// barrier that ends the previous epilogue (every wave is past its combine), and the consuming epilogue reads its 64 values
+// back before it writes its own partials over them -- same wave, LDS order, no barrier.  Nothing between that barrier and the
+// consuming epilogue touches c.stats (the head routines work in the tile's staging view).  `bias` of GB names the vector the
+// successor epilogue will pass to epi_t: the layer's own, a per-plan cvec row (t = 0) or a multitask beff row.
+struct GB {  // LayerNorm weight / bias pointers (+ the linear bias) of one layer, by value (no address of a kernel argument is taken)
+    const float *g = nullptr, *b = nullptr, *bias = nullptr;
 };
-__device__ __forceinline__ GB gb_of(const LayerS &ly) { return GB{ly.g, ly.b}; }
+__device__ __forceinline__ GB gb_of(const LayerS &ly) { return GB{ly.g, ly.b, ly.bias}; }
+__device__ __forceinline__ GB gb_of(const LayerS &ly, const float *bias) { return GB{ly.g, ly.b, bias}; }
 
 template <class CT>
 __device__ __forceinline__ void gb_prefetch(const CT &c, const float *g, const float *b) {
@@ -617,7 +648,16 @@ __device__ __forceinline__ void gb_prefetch(const CT &c, const float *g, const f
     }
 }
 template <class CT>
+__device__ __forceinline__ void gb_prefetch(const CT &c, const GB next) {
+    gb_prefetch(c, next.g, next.b);
+    if constexpr (CT::BIAS_LDS) {
+        static_assert(CT::FT == 2 && CT::NTHR == WIDTH, "thread tid fetches feature tid of its own wave's 64");
+        c.pbias = next.bias[c.tid];
+    }
+}
+template <class CT>
 __device__ __forceinline__ void gb_commit(const CT &c) {
+    if constexpr (CT::BIAS_LDS) c.stats[c.wave * (CT::TROWS * 2) + c.lane] = c.pbias;
 #pragma unroll
     for (int u = 0; u < (WIDTH + CT::NTHR - 1) / CT::NTHR; ++u) {
         const int f = c.tid + u * CT::NTHR;
@@ -657,7 +697,11 @@ __device__ __forceinline__ void epi_t(const CT &c, f32x16 (&acc)[CT::NST][CT::FT
         for (int ft = 0; ft < FT; ++ft) {
             f32x4 b4[4];
 #pragma unroll
-            for (int m = 0; m < 4; ++m) b4[m] = *reinterpret_cast<const f32x4 *>(bias + poff + 32 * ft + 8 * m);
+            for (int m = 0; m < 4; ++m) {
+                if constexpr (CT::BIAS_LDS)  // staged by the previous epi_barrier's commit: `bias` is what the caller named as successor bias
+                    b4[m] = *reinterpret_cast<const f32x4 *>(c.stats + c.wave * (CT::TROWS * 2) + 4 * hh + 32 * ft + 8 * m);
+                else b4[m] = *reinterpret_cast<const f32x4 *>(bias + poff + 32 * ft + 8 * m);
+            }
 #pragma unroll
             for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -857,10 +901,22 @@ __device__ __forceinline__ void layer_full_s(const CT &c, const LayerS &ly, cons
                                              GB next, float *zcopy = nullptr) {
     f32x16 acc[CT::NST][CT::FT];
     zero_acc(acc);
-    if (next.g) gb_prefetch(c, next.g, next.b);  // in flight behind the whole contraction
+    if (next.g) gb_prefetch(c, next);  // in flight behind the whole contraction
     kloop_s(c, ly, kb0, kb1, acc);
     TIMER_MARK(c, T_KLOOP)
     epi_t<ACT>(c, acc, *ly.oscale, *ly.ascale, bias, next, zcopy);
+    epi_barrier(c);
+    TIMER_MARK(c, T_EPI)
+}
+// the same layer, its finished fp32 values (what `zcopy` would hold, in register order) left in the caller's accumulators
+template <int ACT, class CT>
+__device__ __forceinline__ void layer_held_s(const CT &c, const LayerS &ly, const float *bias, int kb0, int kb1, GB next,
+                                             f32x16 (&acc)[CT::NST][CT::FT]) {
+    zero_acc(acc);
+    if (next.g) gb_prefetch(c, next);
+    kloop_s(c, ly, kb0, kb1, acc);
+    TIMER_MARK(c, T_KLOOP)
+    epi_t<ACT>(c, acc, *ly.oscale, *ly.ascale, bias, next, nullptr);
     epi_barrier(c);
     TIMER_MARK(c, T_EPI)
 }
@@ -1217,11 +1273,14 @@ __global__ __launch_bounds__(64 * NW, 2) void ks_rollout(RolloutParams p) {
     __shared__ int s_is_last;
     const int e = blockIdx.x / p.tiles, tile = p.tile_off + blockIdx.x % p.tiles;  // tile_off: a row range of the plan (shard_values)
     const int tid = threadIdx.x;
-    typedef CtxT<APAD, ST, NW, AR> CT;
+    typedef CtxPhT<APAD, ST, NW, AR> CT;
     constexpr int TROWS = CT::TROWS, NTHR = CT::NTHR, FT = CT::FT;
     constexpr int ZKB16 = CT::ZKB;  // k-blocks of this arithmetic covering the latent columns
-    CT c{reinterpret_cast<_Float16 *>(smem), smem + TROWS * CT::RSF(), smem + TROWS * CT::RSF() + 1024, tid,
-         __builtin_amdgcn_readfirstlane(tid >> 6), tid & 63};
+    // z_H waits for the policy-prior chain in the held registers (idle there: the second Q head takes them afterwards) instead
+    // of a round trip through the workgroup's L2 scratch tile; EP = 1 keeps the round trip (its held set carries termination(z_H))
+    constexpr bool ZH_REGS = !EP && KS_ZH_REGS;
+    CT c{{reinterpret_cast<_Float16 *>(smem), smem + TROWS * CT::RSF(), smem + TROWS * CT::RSF() + 1024, tid,
+          __builtin_amdgcn_readfirstlane(tid >> 6), tid & 63}};
     float *sm_mean = smem + TROWS * CT::RSF() + 2048;  // [H*A] after the tile, the LayerNorm partials and c.gb
     float *sm_std = sm_mean + p.H * p.A;
     const int row0 = tile * TROWS;
@@ -1253,7 +1312,8 @@ __global__ __launch_bounds__(64 * NW, 2) void ks_rollout(RolloutParams p) {
     const float *b_pi = p.multitask ? p.beff + ((size_t)e * p.nnets + BE_PI) * WIDTH : p.pi.l[0].bias;
     const float *b_q0 = p.multitask ? p.beff + ((size_t)e * p.nnets + BE_Q0 + q0) * WIDTH : p.q[q0].l[0].bias;
     const float *b_q1 = p.multitask ? p.beff + ((size_t)e * p.nnets + BE_Q0 + q1) * WIDTH : p.q[q1].l[0].bias;
-    gb_prefetch(c, p.rew.l[0].g, p.rew.l[0].b);  // the first epilogue's LayerNorm parameters
+    const float *c_rew = p.cvec + ((size_t)e * 2 + 0) * WIDTH, *c_dyn = p.cvec + ((size_t)e * 2 + 1) * WIDTH;  // t = 0: z0 part + bias
+    gb_prefetch(c, gb_of(p.rew.l[0], c_rew));  // the first epilogue's LayerNorm parameters and bias
     epi_barrier(c);
 
     float G = 0.f;
@@ -1269,7 +1329,7 @@ __global__ __launch_bounds__(64 * NW, 2) void ks_rollout(RolloutParams p) {
         f32x16 accd[ST][FT];
         {
             f32x16 acc[ST][FT];
-            gb_prefetch(c, p.rew.l[1].g, p.rew.l[1].b);
+            gb_prefetch(c, gb_of(p.rew.l[1]));
             first_layers_s(c, p.dyn.l[0], p.rew.l[0], t == 0 ? ZKB16 : 0, KBA, accd, acc);
             TIMER_MARK(c, T_KLOOP)
             if constexpr (EP) {
@@ -1279,18 +1339,18 @@ __global__ __launch_bounds__(64 * NW, 2) void ks_rollout(RolloutParams p) {
                     kloop_s(c, p.term.l[0], 0, ZKB16, accd);
                 }
             }
-            epi_t<0>(c, acc, *p.rew.l[0].oscale, *p.rew.l[0].ascale, t == 0 ? p.cvec + ((size_t)e * 2 + 0) * WIDTH : b_rew,
-                     gb_of(p.rew.l[1]), nullptr);
+            epi_t<0>(c, acc, *p.rew.l[0].oscale, *p.rew.l[0].ascale, t == 0 ? c_rew : b_rew, gb_of(p.rew.l[1]), nullptr);
         }
         epi_barrier(c);
         TIMER_MARK(c, T_EPI)
         DUMP_TILE(c, p.trace_tiles, NSLOT, 5 * t + 0, p.rew.l[0].ascale);
         // ---- reward: layer 2, two-hot head
-        layer_full_s<0>(c, p.rew.l[1], p.rew.l[1].bias, 0, ZKB16, term_step ? gb_of(p.term.l[0]) : gb_of(p.dyn.l[0]));
+        layer_full_s<0>(c, p.rew.l[1], p.rew.l[1].bias, 0, ZKB16,
+                        term_step ? gb_of(p.term.l[0]) : gb_of(p.dyn.l[0], t == 0 ? c_dyn : b_dyn));
         DUMP_TILE(c, p.trace_tiles, NSLOT, 5 * t + 1, p.rew.l[1].ascale);
         // for the held epilogue below; in flight behind the head
-        if (term_step) gb_prefetch(c, p.term.l[1].g, p.term.l[1].b);
-        else gb_prefetch(c, p.dyn.l[1].g, p.dyn.l[1].b);
+        if (term_step) gb_prefetch(c, gb_of(p.term.l[1]));
+        else gb_prefetch(c, gb_of(p.dyn.l[1]));
         const float r = head_twohot_s(c, p.rew.l[2], p.bins, p.num_bins);
         TIMER_MARK(c, T_HEAD)
         if (tsc && (tid & 7) == 0) tsc[t] = r;
@@ -1298,36 +1358,44 @@ __global__ __launch_bounds__(64 * NW, 2) void ks_rollout(RolloutParams p) {
             if (term_step) {  // termination(z_t): layers 1 (held), 2, logit
                 epi_t<0>(c, accd, *p.term.l[0].oscale, *p.term.l[0].ascale, p.term.l[0].bias, gb_of(p.term.l[1]), nullptr);
                 epi_barrier(c);
-                layer_full_s<0>(c, p.term.l[1], p.term.l[1].bias, 0, ZKB16, gb_of(p.dyn.l[0]));
-                gb_prefetch(c, p.dyn.l[1].g, p.dyn.l[1].b);
+                layer_full_s<0>(c, p.term.l[1], p.term.l[1].bias, 0, ZKB16, gb_of(p.dyn.l[0], b_dyn));  // (t > 0)
+                gb_prefetch(c, gb_of(p.dyn.l[1]));
                 termv = fminf(termv + head_term_s(c, p.term.l[2]), 1.f);
                 unpark(c, accd, zs);
             }
         }
         G += disc[t] * (1.f - termv) * r;
         // ---- dynamics: release the held first layer, layers 2 and 3 (SimNorm)
-        epi_t<0>(c, accd, *p.dyn.l[0].oscale, *p.dyn.l[0].ascale, t == 0 ? p.cvec + ((size_t)e * 2 + 1) * WIDTH : b_dyn,
-                 gb_of(p.dyn.l[1]), nullptr);
+        epi_t<0>(c, accd, *p.dyn.l[0].oscale, *p.dyn.l[0].ascale, t == 0 ? c_dyn : b_dyn, gb_of(p.dyn.l[1]), nullptr);
         epi_barrier(c);
         TIMER_MARK(c, T_EPI)
         DUMP_TILE(c, p.trace_tiles, NSLOT, 5 * t + 2, p.dyn.l[0].ascale);
         layer_full_s<0>(c, p.dyn.l[1], p.dyn.l[1].bias, 0, ZKB16, gb_of(p.dyn.l[2]));
         DUMP_TILE(c, p.trace_tiles, NSLOT, 5 * t + 3, p.dyn.l[1].ascale);
-        layer_full_s<1>(c, p.dyn.l[2], p.dyn.l[2].bias, 0, ZKB16, t == p.H - 1 ? gb_of(p.pi.l[0]) : gb_of(p.rew.l[0]),
-                        t == p.H - 1 ? zs : nullptr);
+        if constexpr (ZH_REGS) {
+            if (t == p.H - 1) break;  // the last step's third layer follows the loop: its values stay in the held registers
+            layer_full_s<1>(c, p.dyn.l[2], p.dyn.l[2].bias, 0, ZKB16, gb_of(p.rew.l[0], b_rew), nullptr);
+        } else {
+            layer_full_s<1>(c, p.dyn.l[2], p.dyn.l[2].bias, 0, ZKB16,
+                            t == p.H - 1 ? gb_of(p.pi.l[0], b_pi) : gb_of(p.rew.l[0], b_rew), t == p.H - 1 ? zs : nullptr);
+        }
         DUMP_TILE(c, p.trace_tiles, NSLOT, 5 * t + 4);
     }
-    // ---- a_H = pi(z_H) (tdmpc2.py:135); z_H was also saved to zs.  EP: termination(z_H) first layer from the same tile.
-    f32x16 acch[ST][FT];  // held raw sums: termination first layer (EP), then the second Q head's
+    // ---- a_H = pi(z_H) (tdmpc2.py:135); z_H waits in acch (ZH_REGS) or in zs.  EP: termination(z_H) first layer from the same tile.
+    f32x16 acch[ST][FT];  // held: z_H (ZH_REGS) or the raw sums of the termination first layer (EP), then the second Q head's raw sums
+    if constexpr (ZH_REGS) {
+        layer_held_s<1>(c, p.dyn.l[2], p.dyn.l[2].bias, 0, ZKB16, gb_of(p.pi.l[0], b_pi), acch);
+        DUMP_TILE(c, p.trace_tiles, NSLOT, 5 * (p.H - 1) + 4);
+    }
     if constexpr (EP) {
         zero_acc(acch);
         kloop_s(c, p.term.l[0], 0, ZKB16, acch);
     }
     layer_full_s<0>(c, p.pi.l[0], b_pi, 0, ZKB16, gb_of(p.pi.l[1]));
     DUMP_TILE(c, p.trace_tiles, NSLOT, 5 * p.H + 0, p.pi.l[0].ascale);
-    layer_full_s<0>(c, p.pi.l[1], p.pi.l[1].bias, 0, ZKB16, EP ? gb_of(p.term.l[0]) : gb_of(p.q[q0].l[0]));
+    layer_full_s<0>(c, p.pi.l[1], p.pi.l[1].bias, 0, ZKB16, EP ? gb_of(p.term.l[0]) : gb_of(p.q[q0].l[0], b_q0));
     DUMP_TILE(c, p.trace_tiles, NSLOT, 5 * p.H + 1, p.pi.l[1].ascale);
-    if constexpr (EP) gb_prefetch(c, p.term.l[1].g, p.term.l[1].b);
+    if constexpr (EP) gb_prefetch(c, gb_of(p.term.l[1]));
     {
         auto eps = [&](int row, int a) -> float {
             const unsigned ridx = (unsigned)((size_t)(row0 + row) * p.A + a);
@@ -1341,17 +1409,18 @@ __global__ __launch_bounds__(64 * NW, 2) void ks_rollout(RolloutParams p) {
     if constexpr (EP) {  // termination(z_H) (tdmpc2.py:133-134, last loop iteration): the hidden layers overwrite z columns only
         epi_t<0>(c, acch, *p.term.l[0].oscale, *p.term.l[0].ascale, p.term.l[0].bias, gb_of(p.term.l[1]), nullptr);
         epi_barrier(c);
-        layer_full_s<0>(c, p.term.l[1], p.term.l[1].bias, 0, ZKB16, gb_of(p.q[q0].l[0]));
+        layer_full_s<0>(c, p.term.l[1], p.term.l[1].bias, 0, ZKB16, gb_of(p.q[q0].l[0], b_q0));
         termv = fminf(termv + head_term_s(c, p.term.l[2]), 1.f);
     }
-    tile_from_global_s(c, zs);
+    if constexpr (ZH_REGS) regs_to_tile(c, acch);  // the values unpark would deliver
+    else tile_from_global_s(c, zs);
     __syncthreads();
     TIMER_MARK(c, T_TILE)
     DUMP_TILE(c, p.trace_tiles, NSLOT, 5 * p.H + 2);
     // ---- Q(z_H, a_H): the two selected heads, first layers in one pass (world_model.py:186-216)
     {
         f32x16 acc[ST][FT];
-        gb_prefetch(c, p.q[q0].l[1].g, p.q[q0].l[1].b);
+        gb_prefetch(c, gb_of(p.q[q0].l[1]));
         first_layers_s(c, p.q[q1].l[0], p.q[q0].l[0], 0, KBA, acch, acc);
         TIMER_MARK(c, T_KLOOP)
         epi_t<0>(c, acc, *p.q[q0].l[0].oscale, *p.q[q0].l[0].ascale, b_q0, gb_of(p.q[q0].l[1]), nullptr);
@@ -1359,9 +1428,9 @@ __global__ __launch_bounds__(64 * NW, 2) void ks_rollout(RolloutParams p) {
     epi_barrier(c);
     TIMER_MARK(c, T_EPI)
     DUMP_TILE(c, p.trace_tiles, NSLOT, 5 * p.H + 3, p.q[q0].l[0].ascale);
-    layer_full_s<0>(c, p.q[q0].l[1], p.q[q0].l[1].bias, 0, ZKB16, gb_of(p.q[q1].l[0]));
+    layer_full_s<0>(c, p.q[q0].l[1], p.q[q0].l[1].bias, 0, ZKB16, gb_of(p.q[q1].l[0], b_q1));
     DUMP_TILE(c, p.trace_tiles, NSLOT, 5 * p.H + 4, p.q[q0].l[1].ascale);
-    gb_prefetch(c, p.q[q1].l[1].g, p.q[q1].l[1].b);  // for the held second-head epilogue below
+    gb_prefetch(c, gb_of(p.q[q1].l[1]));  // for the held second-head epilogue below
     const float qa = head_twohot_s(c, p.q[q0].l[2], p.bins, p.num_bins);
     TIMER_MARK(c, T_HEAD)
     epi_t<0>(c, acch, *p.q[q1].l[0].oscale, *p.q[q1].l[0].ascale, b_q1, gb_of(p.q[q1].l[1]), nullptr);
