@@ -3,8 +3,9 @@
 `LayerFn` is one NormedLinear (Linear -> dropout mask -> LayerNorm -> Mish or SimNorm) or one plain Linear, forward and backward in
 HIP; `mlp_apply` and `ensemble_apply` walk the modules of tdmpc2_amd/layers.py through it, so that `loss.backward()` over
 `WorldModel.next / reward / pi / Q` computes every MLP gradient in the library.  `ModelLossFn` / `model_loss` are the four losses of
-`TDMPC2._update` and the gradient seeds of their total (tdmpc2_loss_forward / tdmpc2_loss_backward).  There is no fallback: a CPU
-tensor is an error.
+`TDMPC2._update` and the gradient seeds of their total (tdmpc2_loss_forward / tdmpc2_loss_backward).  `PiHeadFn`, `PiLossFn` / `pi_loss`
+are `update_pi` between its layers (tdmpc2_pigrad_*, include/tdmpc2_pi_grad.h): the Gaussian head after `_pi`'s MLP, and two_hot_inv of
+the two drawn Q heads, the running scale and the rho-weighted loss.  There is no fallback: a CPU tensor is an error.
 """
 from __future__ import annotations
 
@@ -159,3 +160,94 @@ def model_loss(cfg, z_pred, next_z, reward_logits, reward, q_logits, td_target, 
     f32 = lambda t: None if t is None else t.to(torch.float32)  # noqa: E731
     return ModelLossFn.apply(desc, z_pred, f32(next_z), reward_logits, f32(reward), q_logits, f32(td_target), term_logit,
                              f32(terminated))
+
+
+def pi_desc(cfg, steps, batch, action_dim, num_bins, log_std_min, log_std_dif):
+    """The descriptor of the policy-loss unit for a [steps, batch] block of rows; log_std_min / log_std_dif are host floats."""
+    return native.pigrad_desc(steps, batch, action_dim, num_bins, cfg.multitask, cfg.vmin, cfg.vmax, cfg.rho, cfg.entropy_coef,
+                              log_std_min, log_std_dif)
+
+
+class PiHeadFn(torch.autograd.Function):
+    """(action, entropy, scaled_entropy) = the tail of WorldModel.pi after its MLP (tdmpc2_pigrad_head_forward): pi_out [T, B, 2A],
+    eps [T, B, A], mask [B, A] or None.  backward = tdmpc2_pigrad_head_backward, one launch.  Saves pi_out, eps and the mask,
+    nothing else: the backward recomputes every row.  `entropy` is not differentiable; eps and the mask get no gradient."""
+
+    @staticmethod
+    def forward(ctx, desc, pi_out, eps, mask):
+        T, B, A = desc.steps, desc.batch, desc.action_dim
+        dev = pi_out.device
+        yc, ec = pi_out.detach().contiguous(), eps.detach().to(torch.float32).contiguous()
+        mc = None if mask is None else mask.detach().to(torch.float32).contiguous()
+        action = torch.empty((T, B, A), dtype=torch.float32, device=dev)
+        entropy = torch.empty((T, B), dtype=torch.float32, device=dev)
+        se = torch.empty((T, B), dtype=torch.float32, device=dev)
+        native.pigrad_head_forward(desc, yc, ec, mc, action, entropy, se)
+        ctx.desc, ctx.masked, ctx.shape = desc, mc is not None, pi_out.shape
+        ctx.save_for_backward(*([yc, ec] + ([mc] if mc is not None else [])))
+        ctx.mark_non_differentiable(entropy)
+        return action, entropy, se
+
+    @staticmethod
+    def backward(ctx, d_action, _d_entropy, d_se):
+        saved = list(ctx.saved_tensors)
+        yc, ec, mc = saved[0], saved[1], (saved[2] if ctx.masked else None)
+        if not ctx.needs_input_grad[1] or (d_action is None and d_se is None):
+            return None, None, None, None
+        f = lambda g: None if g is None else g.detach().to(torch.float32).contiguous()  # noqa: E731
+        out = torch.empty_like(yc)
+        native.pigrad_head_backward(ctx.desc, yc, ec, mc, f(d_action), f(d_se), out)
+        return None, out.view(ctx.shape), None, None
+
+
+class PiLossFn(torch.autograd.Function):
+    """(pi_loss, parts) of TDMPC2.update_pi (reference tdmpc2.py:220-226) from the two drawn heads' logits: q = the average of
+    two_hot_inv (tdmpc2_pigrad_value_forward), `scale_module.update(q[0])` when asked, then the rho-weighted loss at the scale after
+    that update (tdmpc2_pigrad_loss_forward).  `parts` [2] = mean entropy, mean scaled_entropy, not differentiable.  backward = the
+    one launch of tdmpc2_pigrad_loss_backward; grad_output is handed over as a device pointer, with no host read.  Saves q_logits
+    and a copy of the scale the loss divided by."""
+
+    @staticmethod
+    def forward(ctx, desc, q_logits, entropy, scaled_entropy, scale_module, update_scale):
+        dev = q_logits.device
+        T, B = desc.steps, desc.batch
+        ql = q_logits.detach().contiguous()
+        en, se = entropy.detach().contiguous(), scaled_entropy.detach().contiguous()
+        q = torch.empty((T, B), dtype=torch.float32, device=dev)
+        native.pigrad_value_forward(desc, ql, q)
+        if update_scale:
+            scale_module.update(q[0])
+        scale = scale_module.value.detach().to(torch.float32).reshape(1).clone()
+        losses = torch.empty(3, dtype=torch.float32, device=dev)
+        native.pigrad_loss_forward(desc, q, en, se, scale, losses)
+        ctx.desc, ctx.shapes = desc, (q_logits.shape, scaled_entropy.shape)
+        ctx.save_for_backward(ql, scale)
+        parts = losses[1:]
+        ctx.mark_non_differentiable(parts)
+        return losses[0], parts
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_parts):
+        ql, scale = ctx.saved_tensors
+        need_q, need_se = ctx.needs_input_grad[1], ctx.needs_input_grad[3]
+        dq = torch.empty_like(ql) if need_q else None
+        dse = torch.empty((ctx.desc.steps, ctx.desc.batch), dtype=torch.float32, device=ql.device) if need_se else None
+        if need_q or need_se:
+            g = g_loss.detach().to(torch.float32).reshape(1).contiguous()  # stays on the device: no host read
+            native.pigrad_loss_backward(ctx.desc, ql, scale, g, dq, dse)
+        return (None, None if dq is None else dq.view(ctx.shapes[0]), None, None if dse is None else dse.view(ctx.shapes[1]), None,
+                None)
+
+
+def pi_loss(cfg, q_logits, entropy, scaled_entropy, scale_module, update_scale=True):
+    """The policy loss of `TDMPC2.update_pi` (reference tdmpc2.py:220-226) in the library.  q_logits [2, T, B, bins] (the two drawn
+    heads: `WorldModel.Q_pair`), entropy and scaled_entropy [T, B] or [T, B, 1] (`WorldModel.pi`'s info), scale_module a
+    `RunningScale` (updated with the first step's q unless `update_scale` is False).  Returns (pi_loss, parts): the 0-d
+    differentiable loss and the detached [2] tensor mean entropy, mean scaled_entropy.  Gradients reach q_logits and
+    scaled_entropy.  There is no fallback: a CPU tensor is an error."""
+    if q_logits.dim() != 4 or q_logits.shape[0] != 2:
+        raise native.NativeError(f"pi_loss: q_logits [2, T, B, bins] (got {tuple(q_logits.shape)})")
+    _, T, B, NB = q_logits.shape
+    desc = pi_desc(cfg, T, B, cfg.action_dim, NB, 0.0, 0.0)  # (the value and loss calls read neither log_std constant)
+    return PiLossFn.apply(desc, q_logits, entropy.detach().to(torch.float32), scaled_entropy.to(torch.float32), scale_module,
+                          bool(update_scale))  # (entropy only feeds a mean of the info dict)

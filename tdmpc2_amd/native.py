@@ -43,6 +43,9 @@ ABI_SYMBOLS = [
     "tdmpc2_optim_set_step",
     "tdmpc2_loss_workspace_bytes", "tdmpc2_loss_forward", "tdmpc2_loss_backward",
 ]
+# include/tdmpc2_pi_grad.h: the policy-loss unit, a header of its own beside ABI 14 (whose version and symbols stay as they are)
+PI_GRAD_SYMBOLS = ("tdmpc2_pigrad_head_forward", "tdmpc2_pigrad_head_backward", "tdmpc2_pigrad_value_forward",
+                   "tdmpc2_pigrad_loss_forward", "tdmpc2_pigrad_loss_backward")
 
 NET_DYNAMICS, NET_REWARD, NET_PI, NET_Q, NET_TERMINATION, NET_TARGET_Q = range(6)
 PATH_AUTO, PATH_FUSED, PATH_LAYERED = range(3)  # enum tdmpc2_path
@@ -167,6 +170,11 @@ class LossDesc(C.Structure):  # struct tdmpc2_loss_desc
     _fields_ = [(n, C.c_int32) for n in ("steps", "batch", "latent_dim", "num_q", "num_bins", "episodic")] + \
                [(n, C.c_float) for n in ("vmin", "vmax", "bin_size", "rho", "consistency_coef", "reward_coef", "value_coef",
                                          "termination_coef")]
+
+
+class PiGradDesc(C.Structure):  # struct tdmpc2_pigrad_desc (include/tdmpc2_pi_grad.h)
+    _fields_ = [(n, C.c_int32) for n in ("steps", "batch", "action_dim", "num_bins", "multitask")] + \
+               [(n, C.c_float) for n in ("vmin", "vmax", "rho", "entropy_coef", "log_std_min", "log_std_dif")]
 
 
 class Debug(C.Structure):
@@ -354,6 +362,10 @@ def _open(path):
     lib.tdmpc2_loss_forward.restype = i32
     lib.tdmpc2_loss_backward.argtypes = [C.POINTER(LossDesc)] + [vp] * 14
     lib.tdmpc2_loss_backward.restype = i32
+    for name, nptr in zip(PI_GRAD_SYMBOLS, (7, 7, 3, 7, 6)):  # pointers after the descriptor, the stream included
+        fn = getattr(lib, name)
+        fn.argtypes = [C.POINTER(PiGradDesc)] + [vp] * nptr
+        fn.restype = i32
     if lib.tdmpc2_plan_abi_version() != ABI_VERSION:
         raise NativeError(f"ABI version mismatch: library {lib.tdmpc2_plan_abi_version()}, binding {ABI_VERSION}")
     return lib
@@ -1645,3 +1657,68 @@ def loss_backward(desc: LossDesc, z_pred, next_z, reward_logits, reward, q_logit
             C.byref(desc), _ptr(z_pred), _ptr(next_z), _ptr(reward_logits), _ptr(reward), _ptr(q_logits), _ptr(td_target),
             _ptr(term_logit), _ptr(terminated), _ptr(grad_total), _ptr(d_z_pred), _ptr(d_reward_logits), _ptr(d_q_logits),
             _ptr(d_term_logit), torch.cuda.current_stream(z_pred.device).cuda_stream))
+
+
+# ---------------------------------------------------------------- policy loss seeds (tdmpc2_pigrad_*, include/tdmpc2_pi_grad.h)
+PI_GRAD_CALLS = 0  # library calls made through the wrappers below (forward + backward), kept like LOSS_CALLS
+
+
+def pigrad_desc(steps: int, batch: int, action_dim: int, num_bins: int, multitask: bool, vmin: float, vmax: float, rho: float,
+                entropy_coef: float, log_std_min: float, log_std_dif: float) -> PiGradDesc:
+    return PiGradDesc(steps=int(steps), batch=int(batch), action_dim=int(action_dim), num_bins=int(num_bins),
+                      multitask=int(bool(multitask)), vmin=float(vmin), vmax=float(vmax), rho=float(rho),
+                      entropy_coef=float(entropy_coef), log_std_min=float(log_std_min), log_std_dif=float(log_std_dif))
+
+
+def _pigrad_call(what: str, desc: PiGradDesc, first, **ts):
+    """Device, dtype, contiguity and element counts of the layouts of include/tdmpc2_pi_grad.h (the library sees pointers only),
+    then the call on the current stream."""
+    global PI_GRAD_CALLS
+    if first.device.type != "cuda":
+        raise NativeError(f"{what} runs on an MI355X only (device {first.device}); there is no CPU fallback")
+    T, B, A, NB = desc.steps, desc.batch, desc.action_dim, desc.num_bins
+    want = dict(pi_out=T * B * 2 * A, eps=T * B * A, action_mask=B * A, action=T * B * A, entropy=T * B, scaled_entropy=T * B,
+                d_action=T * B * A, d_scaled_entropy=T * B, d_pi_out=T * B * 2 * A, q_logits=2 * T * B * NB, q=T * B, scale=1,
+                losses=3, step_means=T, grad_total=1, d_q_logits=2 * T * B * NB)
+    _layer_tensors(what, first.device, **ts)
+    for name, t in ts.items():
+        if t is not None and t.numel() != want[name]:
+            raise NativeError(f"{what}: {name} holds {t.numel()} floats, the descriptor asks for {want[name]}")
+    PI_GRAD_CALLS += 1
+    with torch.cuda.device(first.device):
+        rc = getattr(load_library(), "tdmpc2_" + what)(C.byref(desc), *[_ptr(t) for t in ts.values()],
+                                                         torch.cuda.current_stream(first.device).cuda_stream)
+    if rc != 0:
+        raise NativeError(f"tdmpc2_pigrad error {rc}: {load_library().tdmpc2_last_error().decode()}")
+
+
+def pigrad_head_forward(desc: PiGradDesc, pi_out, eps, action_mask=None, action=None, entropy=None, scaled_entropy=None):
+    """tdmpc2_pigrad_head_forward: pi_out [T, B, 2A], eps [T, B, A], action_mask [B, A] (multitask) -> action [T, B, A], entropy and
+    scaled_entropy [T, B], written in place."""
+    _pigrad_call("pigrad_head_forward", desc, pi_out, pi_out=pi_out, eps=eps, action_mask=action_mask, action=action, entropy=entropy,
+                 scaled_entropy=scaled_entropy)
+
+
+def pigrad_head_backward(desc: PiGradDesc, pi_out, eps, action_mask=None, d_action=None, d_scaled_entropy=None, d_pi_out=None):
+    """tdmpc2_pigrad_head_backward: the incoming gradients (None = zero, not both) -> d_pi_out [T, B, 2A], overwritten."""
+    _pigrad_call("pigrad_head_backward", desc, pi_out, pi_out=pi_out, eps=eps, action_mask=action_mask, d_action=d_action,
+                 d_scaled_entropy=d_scaled_entropy, d_pi_out=d_pi_out)
+
+
+def pigrad_value_forward(desc: PiGradDesc, q_logits, q):
+    """tdmpc2_pigrad_value_forward: q_logits [2, T, B, NB] -> q [T, B] = the average of two_hot_inv of the two heads."""
+    _pigrad_call("pigrad_value_forward", desc, q_logits, q_logits=q_logits, q=q)
+
+
+def pigrad_loss_forward(desc: PiGradDesc, q, entropy, scaled_entropy, scale, losses, step_means=None):
+    """tdmpc2_pigrad_loss_forward: -> losses [3] (pi_loss, mean entropy, mean scaled_entropy) and step_means [T] (optional); `scale`
+    is a one-element fp32 tensor on the device (RunningScale.value)."""
+    _pigrad_call("pigrad_loss_forward", desc, q, q=q, entropy=entropy, scaled_entropy=scaled_entropy, scale=scale, losses=losses,
+                 step_means=step_means)
+
+
+def pigrad_loss_backward(desc: PiGradDesc, q_logits, scale, grad_total=None, d_q_logits=None, d_scaled_entropy=None):
+    """tdmpc2_pigrad_loss_backward: `grad_total` is a one-element fp32 tensor on the device or None (= 1); the outputs that are not
+    None are overwritten."""
+    _pigrad_call("pigrad_loss_backward", desc, q_logits, q_logits=q_logits, scale=scale, grad_total=grad_total, d_q_logits=d_q_logits,
+                 d_scaled_entropy=d_scaled_entropy)

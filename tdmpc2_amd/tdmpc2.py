@@ -69,6 +69,8 @@ class TDMPC2(torch.nn.Module):
         self._optim = self._pi_optim = None  # made by the first read of `optim` / `pi_optim`: nothing for a planning-only user
         self._planner_log_std = None
         self.last_td_targets = None  # the TD target [H, B, 1] of the last update_model call
+        self.last_zs = None          # its rollout's latents [H+1, B, L], detached: what update_pi is given
+        self.last_term_logit = None  # its termination logits [H, B, 1], detached (episodic models)
         self._prev_mean_batch = None
         # Philox stream of the in-library noise: cfg.seed in the low word, the rank in the high word, so that env-sharded
         # ranks built from one cfg (tdmpc2_amd/dist.py) do not draw identical exploration noise; a per-call counter is
@@ -546,11 +548,15 @@ class TDMPC2(torch.nn.Module):
         Returns consistency_loss, reward_loss, value_loss, termination_loss, total_loss and grad_norm as 0-d device tensors.
         Raises NativeError when `native_autograd` is off: there is no torch path.  It equals the reference when cfg.dropout == 0:
         the port's QEnsemble has no dropout in any mode, where the reference's Q heads drop inputs of their first layer in
-        train mode."""
-        from . import autograd
+        train mode.  It also leaves `last_zs` ([H+1, B, L], detached) and, on episodic models, `last_term_logit` ([H, B, 1])."""
         from .native import NativeError
         if not self.native_autograd:
             raise NativeError("update_model runs the model's layers and losses in the library: set native_autograd = True")
+        return self._update_model(obs, action, reward, terminated, task, td_targets, pi_eps, qidx, keep_train=False)
+
+    def _update_model(self, obs, action, reward, terminated, task, td_targets, pi_eps, qidx, keep_train):
+        """`update_model`; keep_train: its step 6 is left to the caller (`_update`, which runs `update_pi` in train mode first)."""
+        from . import autograd
         cfg = self.cfg
         obs = obs.to(self.device)
         action = action.to(self.device, torch.float32)
@@ -583,10 +589,82 @@ class TDMPC2(torch.nn.Module):
                                                terminated if cfg.episodic else None)
             total.backward()
             grad_norm = self.optimizer_step("model").clone()
+            self.last_zs = torch.stack(zs).detach()
+            self.last_term_logit = None if term_pred is None else term_pred.detach()
         finally:
-            self.model.eval()
+            if not keep_train:
+                self.model.eval()
         return {"consistency_loss": parts[0], "reward_loss": parts[1], "value_loss": parts[2], "termination_loss": parts[3],
                 "total_loss": total.detach(), "grad_norm": grad_norm}
+
+    # ------------------------------------------------------------------ the policy half of _update, and _update itself
+    def update_pi(self, zs, task=None, pi_eps=None, qidx=None):
+        """`update_pi` of the reference (tdmpc2.py:208-239) in its order, every piece in the library: zs [H+1, B, L] (detached here
+        as `_update` detaches it), task [B].
+          1. action, info = model.pi(zs, task): the MLP through the trainable layer, its tail through `autograd.PiHeadFn`
+             (`pi_eps` [H+1, B, A] pins the noise, else torch.randn_like draws it);
+          2. `model.Q_pair` on the online parameters, detached: the two heads `qidx` (drawn with torch.randperm on the device when
+             not given), the reference's Q(..., 'avg', detach=True);
+          3. `scale.update(qs[0])`, 4. the rho-weighted loss at the updated scale (both inside `autograd.pi_loss`);
+          5. `pi_loss.backward()`: the seeds of the loss, the Q pair's dx, the head and `_pi`'s layers, all in HIP;
+          6. `optimizer_step("pi")`: clip at cfg.grad_clip_norm, Adam with eps 1e-5, zero_grad and the planner's re-pack.
+        Returns pi_loss, pi_grad_norm, pi_entropy, pi_scaled_entropy (means, as `_update` reports them) and pi_scale as 0-d device
+        tensors.  The model's mode is left as it is (`_update` calls this in train mode, as the reference does).  Raises
+        NativeError when `native_autograd` is off: there is no torch path.  It equals the reference when cfg.dropout == 0: the
+        port's QEnsemble has no dropout in any mode."""
+        from . import autograd
+        from .native import NativeError
+        if not self.native_autograd:
+            raise NativeError("update_pi runs the policy's layers, its head and its loss in the library: set native_autograd = True")
+        cfg = self.cfg
+        zs = zs.detach().to(self.device, torch.float32)
+        if zs.dim() != 3:
+            raise NativeError(f"update_pi: zs [H+1, B, L] (got {tuple(zs.shape)})")
+        if task is not None:
+            task = torch.as_tensor(task, device=self.device)
+        if pi_eps is not None:
+            pi_eps = pi_eps.to(self.device, torch.float32)
+        if qidx is None:
+            qidx = torch.randperm(cfg.num_q, device=self.device)[:2]
+        self.pi_optim  # noqa: B018  (made before backward: every .grad of _pi is then a view into its gradient arena)
+        action, info = self.model.pi(zs, task, eps=pi_eps)
+        q_logits = self.model.Q_pair(zs, action, task, qidx)
+        pi_loss, parts = autograd.pi_loss(cfg, q_logits, info["entropy"], info["scaled_entropy"], self.scale)
+        pi_loss.backward()
+        pi_grad_norm = self.optimizer_step("pi").clone()
+        return {"pi_loss": pi_loss.detach(), "pi_grad_norm": pi_grad_norm.reshape(()), "pi_entropy": parts[0],
+                "pi_scaled_entropy": parts[1], "pi_scale": self.scale.value.detach().clone().reshape(())}
+
+    def _update(self, obs, action, reward, terminated=None, task=None):
+        """`_update` of the reference (tdmpc2.py:259-332): `update_model`, then `update_pi(zs.detach(), task)` with the model still
+        in train mode, then `soft_update_target_Q()`, then model.eval() and the reference's info dict as 0-d device tensors
+        (consistency_loss, reward_loss, value_loss, termination_loss, total_loss, grad_norm; on episodic models termination_rate and
+        termination_f1 of the last step through `termination_stats`; pi_loss, pi_grad_norm, pi_entropy, pi_scaled_entropy,
+        pi_scale).  Equality with the reference holds for cfg.dropout == 0: the port's QEnsemble has no dropout."""
+        from .native import NativeError
+        if not self.native_autograd:
+            raise NativeError("_update runs in the library: set native_autograd = True")
+        cfg = self.cfg
+        if terminated is None:
+            terminated = torch.zeros(action.shape[0], action.shape[1], 1, device=self.device)
+        try:
+            info = self._update_model(obs, action, reward, terminated, task, None, None, None, keep_train=True)
+            pi_info = self.update_pi(self.last_zs, task)
+            self.soft_update_target_Q()
+        finally:
+            self.model.eval()
+        if cfg.episodic:
+            st = self.planner().termination_stats(self.last_term_logit[-1].contiguous(),
+                                                  terminated[-1].to(self.device, torch.float32).contiguous())
+            info["termination_rate"], info["termination_f1"] = st[0], st[1]
+        info.update(pi_info)
+        return info
+
+    def update(self, buffer):
+        """One training iteration of the reference (tdmpc2.py:334-349): `_update` on `buffer.sample()` (a tdmpc2_amd.Buffer, whose
+        batch comes out time-major and on this device)."""
+        obs, action, reward, terminated, task = buffer.sample()
+        return self._update(obs, action, reward, terminated, task)
 
     def _encode_pix_batch(self, obs, H, B):
         """encode(obs[i]) for i = 0 .. H in one library call (tdmpc2_plan_encode_pix_batch): ShiftAug's shifts are drawn on the host

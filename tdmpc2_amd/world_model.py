@@ -30,6 +30,47 @@ def two_hot_inv(x, cfg):
     return _symexp(torch.sum(F.softmax(x, dim=-1) * bins, dim=-1, keepdim=True))
 
 
+def _pi_tail(out, eps, m, action_dims, log_std_min, log_std_dif):
+    """`WorldModel.pi` after its MLP in torch (reference world_model.py:160-184, math.py:12-39): out [..., 2A], eps [..., A], m the
+    mask rows and action_dims their sums (multitask) or None -> (action, info)."""
+    mean, log_std = out.chunk(2, dim=-1)
+    log_std = log_std_min + 0.5 * log_std_dif * (torch.tanh(log_std) + 1)
+    if m is not None:
+        mean, log_std, eps = mean * m, log_std * m, eps * m
+    log_prob = (-0.5 * eps.pow(2) - log_std - 0.9189385175704956).sum(-1, keepdim=True)  # math.gaussian_logprob
+    scaled_log_prob = log_prob * (eps.shape[-1] if action_dims is None else action_dims)
+    action = mean + eps * log_std.exp()
+    mean, action = torch.tanh(mean), torch.tanh(action)  # math.squash
+    log_prob = log_prob - torch.log(F.relu(1 - action.pow(2)) + 1e-6).sum(-1, keepdim=True)
+    entropy_scale = scaled_log_prob / (log_prob + 1e-8)
+    return action, {"mean": mean, "log_std": log_std, "action_prob": 1.0, "entropy": -log_prob,
+                    "scaled_entropy": -log_prob * entropy_scale}
+
+
+class _PiEntropyGrad(torch.autograd.Function):
+    """info['entropy'] of the library's policy head, kept differentiable as the modules' is.  The library's backward takes the
+    gradients of the action and of scaled_entropy (what update_pi differentiates); a backward that reaches `entropy` itself -- no
+    path of the learner does -- is torch autograd of `_pi_tail` on the saved inputs, evaluated only then.  The forward adds nothing."""
+
+    @staticmethod
+    def forward(ctx, entropy, out, eps, m, action_dims, log_std_min, log_std_dif):
+        ctx.save_for_backward(out, eps, log_std_min, log_std_dif, *([m, action_dims] if m is not None else []))
+        ctx.set_materialize_grads(False)
+        return entropy.view(entropy.shape)
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None, None, None, None
+        out, eps, lmin, ldif, *rest = ctx.saved_tensors
+        m, dims = rest if rest else (None, None)
+        with torch.enable_grad():
+            y = out.detach().requires_grad_(True)
+            ent = _pi_tail(y, eps, m, dims, lmin, ldif)[1]["entropy"]
+            (gy,) = torch.autograd.grad(ent, y, g.reshape(ent.shape))
+        return None, gy, None, None, None, None, None
+
+
 class WorldModel(nn.Module):
     def __init__(self, cfg):
         super().__init__()
@@ -55,6 +96,7 @@ class WorldModel(nn.Module):
         # True (and the input on the GPU): the MLPs of encode (state), next, reward, termination, pi and Q run through the library's
         # trainable layer (tdmpc2_amd/autograd.py), so loss.backward() computes their gradients in HIP; off by default -- the modules
         self.native_autograd = False
+        self._log_std_host = None  # host copies of log_std_min / log_std_dif for the library's policy head (made at first use)
         self.apply(self._weight_init)
         self._register_state_dict_hook(self._add_meta_keys)
         self._register_load_state_dict_pre_hook(self._convert_incoming, with_module=True)
@@ -82,6 +124,7 @@ class WorldModel(nn.Module):
 
     @staticmethod
     def _convert_incoming(module, state_dict, prefix, *args):
+        module._log_std_host = None
         incoming = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
         conv = checkpoint.convert_state_dict(incoming)
         if checkpoint.is_old_format(incoming):
@@ -144,28 +187,84 @@ class WorldModel(nn.Module):
         logit = self._mlp(self._termination, z)
         return logit if unnormalized else torch.sigmoid(logit)
 
-    def pi(self, z, task):
+    def pi(self, z, task, eps=None):
         """Returns (action, info) like the reference (world_model.py:144-184, math.py:12-29): info carries 'mean', 'log_std',
-        'action_prob', 'entropy' and 'scaled_entropy' (a dict; the reference's TensorDict has the same keys)."""
+        'action_prob', 'entropy' and 'scaled_entropy' (a dict; the reference's TensorDict has the same keys).  `eps` pins the
+        noise of the sample (shaped as the action); by default it is drawn with torch.randn_like, on either path.  With
+        `native_autograd` and the input on the GPU everything after the MLP runs in the library (autograd.PiHeadFn, forward and
+        backward): the same expression, so the action stream is unchanged in distribution, but its bits differ from torch's (the
+        library's tanh / exp / log and its order of the row sums)."""
         if self.cfg.multitask:
             z = self.task_emb(z, task)
-        mean, log_std = self._mlp(self._pi, z).chunk(2, dim=-1)
-        log_std = self.log_std_min + 0.5 * self.log_std_dif * (torch.tanh(log_std) + 1)
-        eps = torch.randn_like(mean)
+        out = self._mlp(self._pi, z)
+        if self.native_autograd and out.is_cuda:
+            return self._pi_native(out, task, eps)
+        eps = torch.randn_like(out[..., : out.shape[-1] // 2]) if eps is None else eps
         if self.cfg.multitask:
-            m = self._action_masks[task]
-            mean, log_std, eps = mean * m, log_std * m, eps * m
-            action_dims = self._action_masks.sum(-1)[task].unsqueeze(-1)
-        else:
-            action_dims = None
-        log_prob = (-0.5 * eps.pow(2) - log_std - 0.9189385175704956).sum(-1, keepdim=True)  # math.gaussian_logprob
-        scaled_log_prob = log_prob * (eps.shape[-1] if action_dims is None else action_dims)
-        action = mean + eps * log_std.exp()
-        mean, action = torch.tanh(mean), torch.tanh(action)  # math.squash
-        log_prob = log_prob - torch.log(F.relu(1 - action.pow(2)) + 1e-6).sum(-1, keepdim=True)
-        entropy_scale = scaled_log_prob / (log_prob + 1e-8)
-        return action, {"mean": mean, "log_std": log_std, "action_prob": 1.0, "entropy": -log_prob,
-                        "scaled_entropy": -log_prob * entropy_scale}
+            return _pi_tail(out, eps, self._action_masks[task], self._action_masks.sum(-1)[task].unsqueeze(-1), self.log_std_min,
+                            self.log_std_dif)
+        return _pi_tail(out, eps, None, None, self.log_std_min, self.log_std_dif)
+
+    def _log_std_consts(self):
+        """(log_std_min, log_std_dif) as host floats: two device reads, once (a load_state_dict drops the cache)."""
+        if self._log_std_host is None:
+            self._log_std_host = (float(self.log_std_min), float(self.log_std_dif))
+        return self._log_std_host
+
+    def _pi_native(self, out, task, eps):
+        """The tail of `pi` in the library.  out [..., 2A]: the rows are one block [1, R] of the head kernel, or, for a multitask
+        [T, B, 2A] with one task per batch column, [T, B] with the mask rows [B, A]."""
+        A = out.shape[-1] // 2
+        lead = out.shape[:-1]
+        R = 1
+        for n in lead:
+            R *= int(n)
+        mean_raw, ls_raw = out.chunk(2, dim=-1)
+        eps = torch.randn_like(mean_raw) if eps is None else eps.to(out.device, torch.float32)
+        T_, B_, mask = 1, R, None
+        if self.cfg.multitask:
+            mask = self._action_masks[task].to(torch.float32).reshape(-1, A)
+            if out.dim() == 3 and mask.shape[0] == out.shape[1] and out.shape[0] <= 16:
+                T_, B_ = int(out.shape[0]), int(out.shape[1])
+            elif out.dim() == 3 and mask.shape[0] == out.shape[1]:
+                mask = mask.repeat(out.shape[0], 1)
+            elif mask.shape[0] == 1:
+                mask = mask.expand(R, A)
+            elif mask.shape[0] != R:
+                raise autograd.native.NativeError(f"pi: {mask.shape[0]} tasks for rows {tuple(lead)}")
+        desc = autograd.pi_desc(self.cfg, T_, B_, A, 2, *self._log_std_consts())  # (the head reads no bins: any valid count)
+        action, entropy, se = autograd.PiHeadFn.apply(desc, out.reshape(T_, B_, 2 * A), eps.reshape(T_, B_, A), mask)
+        log_std = self.log_std_min + 0.5 * self.log_std_dif * (torch.tanh(ls_raw) + 1)
+        mean, m, dims = mean_raw, None, None
+        if self.cfg.multitask:
+            m, dims = self._action_masks[task], self._action_masks.sum(-1)[task].unsqueeze(-1)
+            mean, log_std = mean * m, log_std * m
+        entropy = entropy.view(*lead, 1)
+        if out.requires_grad:
+            entropy = _PiEntropyGrad.apply(entropy, out, eps, m, dims, self.log_std_min, self.log_std_dif)
+        return action.view(*lead, A), {"mean": torch.tanh(mean), "log_std": log_std, "action_prob": 1.0, "entropy": entropy,
+                                       "scaled_entropy": se.view(*lead, 1)}
+
+    def Q_pair(self, z, a, task, qidx):
+        """The logits of the two heads `qidx` of the online ensemble on DETACHED parameters -> [2, ..., num_bins]: the reference's
+        Q(z, a, task, return_type='avg', detach=True) (world_model.py:186-216) before two_hot_inv, restricted to the two drawn heads
+        -- 2 of num_q members' work; gradient reaches `a` (and z), never `_Qs`.  qidx: two head indices (tensor or sequence)."""
+        from types import SimpleNamespace
+        if self.cfg.multitask:
+            z = self.task_emb(z, task)
+        za = torch.cat([z, a], dim=-1)
+        idx = torch.as_tensor(qidx, device=za.device).long().reshape(2)
+        pick = lambda t: t.detach().index_select(0, idx)  # noqa: E731
+
+        def layer(i):
+            l = self._Qs.params.layer(i)
+            ln = SimpleNamespace(weight=pick(l.ln.weight), bias=pick(l.ln.bias)) if i < 2 else None
+            return SimpleNamespace(weight=pick(l.weight), bias=pick(l.bias), ln=ln)
+
+        sel = SimpleNamespace(n=2, layer=layer)
+        if self.native_autograd and za.is_cuda:
+            return autograd.ensemble_apply(sel, za)
+        return layers.QEnsemble.apply_params(sel, za)
 
     def Q(self, z, a, task, return_type="min"):
         assert return_type in {"min", "avg", "all"}
