@@ -18,6 +18,11 @@ patching `torch.randn`, `torch.randn_like`, `torch.randperm` and
 `Tensor.exponential_` while `_plan` runs — reference code untouched.
 Per-iteration locals (value, elite idx, score, mean, std) are read with
 `sys.settrace`, again without touching the reference.
+
+Training side: `run_reference_updates` runs `TDMPC2._update`, `update_pi` and
+`_td_target` (tdmpc2/tdmpc2.py:208-332) verbatim in the same way; what it has
+to restate (the optimisers, RunningScale's constructor, the soft update,
+`_detach_Qs`) is listed in its docstring.
 """
 from __future__ import annotations
 
@@ -95,6 +100,21 @@ class _Ens(nn.Module):
         return torch.vmap(lambda p, x: functional_call(self.base, (p,), (x,)), (0, None), randomness="different")(P, x)
 
 
+class _DetachedEns(nn.Module):
+    """`_detach_Qs` (world_model.py:40: `_Qs.params.data`): the online ensemble's values, cut from autograd.  The ensemble it reads
+    is no registered child, so the parameters stay `_Qs`'s alone and a backward through this module never reaches them."""
+
+    def __init__(self, ens):
+        super().__init__()
+        self.__dict__["ens"] = ens
+
+    def forward(self, x):
+        from torch.func import functional_call
+
+        P = {k.replace("__", "."): v.detach() for k, v in self.ens.p.items()}
+        return torch.vmap(lambda p, x: functional_call(self.ens.base, (p,), (x,)), (0, None), randomness="different")(P, x)
+
+
 def build_agent(cfg, state_dict: Dict[str, torch.Tensor], discount):
     """Duck-typed host objects carrying the reference's unbound methods."""
     ref = _import_reference()
@@ -119,7 +139,7 @@ def build_agent(cfg, state_dict: Dict[str, torch.Tensor], discount):
             # parameter sets); WorldModel.Q picks one by its `target` / `detach` flags (world_model.py:201-206)
             s._target_Qs = _Ens([layers.mlp(D, 2 * [cfg.mlp_dim], max(cfg.num_bins, 1), dropout=cfg.dropout)
                                  for _ in range(cfg.num_q)])
-            s._detach_Qs = s._Qs
+            s._detach_Qs = _DetachedEns(s._Qs)
             s.register_buffer("log_std_min", torch.tensor(float(cfg.log_std_min)))
             s.register_buffer("log_std_dif", torch.tensor(float(cfg.log_std_max)) - s.log_std_min)
 
@@ -138,6 +158,8 @@ def build_agent(cfg, state_dict: Dict[str, torch.Tensor], discount):
     Agent._plan = TDMPC2._plan
     Agent._estimate_value = TDMPC2._estimate_value
     Agent._td_target = TDMPC2._td_target
+    Agent._update = TDMPC2._update
+    Agent.update_pi = TDMPC2.update_pi
     agent = Agent()
     # load weights (checkpoint keys -> host modules)
     own = agent.model.state_dict()
@@ -239,6 +261,190 @@ def run_reference_td_target(cfg, state_dict, *, next_z, reward, terminated, task
             return agent._td_target(torch.as_tensor(next_z), torch.as_tensor(reward), torch.as_tensor(terminated), task_t)
     finally:
         torch.randn_like, torch.randperm = saved
+
+
+UPDATE_CONTROLS = ("enc_lr", "pi_eps", "no_emb_leak", "no_soft_update", "soft_update_first", "stale_pi_td", "soft_update_before_step")
+
+
+def run_reference_updates(cfg, state_dict, batch, pins, iterations, dtype, scale0, control=None):
+    """Call the reference's `TDMPC2._update` (tdmpc2/tdmpc2.py:259-332; `update_pi` :208-239 and `_td_target` :241-257 under it)
+    `iterations` times on one batch, verbatim, on the CPU in `dtype`.
+
+    batch: obs [H+1, B, *], action [H, B, A], reward [H, B, 1], terminated [H, B, 1] or None, task [B] or None.
+    pins: td_pi_eps [K, H, B, A], td_qidx [K, 2], pi_eps [K, H+1, B, A], qidx [K, 2] -- the four RNG draws of an iteration
+    (`randn_like` world_model.py:156 and `randperm` world_model.py:212, once under `_td_target` and once under `update_pi`), served by
+    patching `torch.randn_like` / `torch.randperm` while `_update` runs.
+    Returns {"infos": one dict of python floats per iteration, "td": [K, H, B, 1] `_update`'s own `td_targets`, "term_logit":
+    [K, B, 1] its `termination_pred[-1]` (episodic models, else None)}; both read from `_update`'s locals with `sys.settrace`.
+
+    Restated, because the reference's own cannot be imported as it is (nothing else is):
+      - the two optimisers of tdmpc2.py:22-31 (there with `capturable=True`, which is for CUDA graphs);
+      - `RunningScale` (common/scale.py:8-12: the constructor hard-codes cuda:0): made without it, with `cfg`, `value` = scale0 and
+        `_percentiles` = [5, 95] on the CPU, both in `dtype`; its methods are the reference's;
+      - `soft_update_target_Q` (world_model.py:82-86; needs tensordict): the lerp of the stacked target parameters towards the
+        online ones;
+      - `_detach_Qs` (world_model.py:40): `_DetachedEns`;
+      - `_action_masks` (world_model.py:22-24): loaded from the state dict.
+    cfg.dropout is 0 (the port's Q ensemble has none) and cfg.batch_size the batch's B.  Every hyperparameter the C ABI carries as
+    fp32 reaches the reference widened (tests.optim_common.widen): lr, the encoder's lr, both betas, both eps,
+    grad_clip_norm, rho, tau, entropy_coef and the four loss coefficients.  fp64 runs happen under
+    `torch.set_default_dtype(torch.float64)`: `_update` allocates `zs` with the default dtype.
+
+    control: one deliberately WRONG variant (UPDATE_CONTROLS), each in a restated piece or in a hook between the verbatim calls --
+    enc_lr: the encoder group at the plain lr; pi_eps: pi_optim's eps 1e-8; no_emb_leak: `_task_emb.weight.grad` cleared after
+    `update_pi`; no_soft_update; soft_update_first: the target lerped before `update_pi`; stale_pi_td: `_td_target` evaluated on
+    the `_pi` of one iteration earlier; soft_update_before_step: the target lerped before the model optimiser's step, towards the
+    online parameters of before it.  (`soft_update_first` commutes with `update_pi` -- one writes `_pi`, the other the target, both
+    only read the online Q -- and so reproduces the verbatim run bit for bit; `soft_update_before_step` is the order that is wrong.)"""
+    import numpy as np
+
+    from tdmpc2_amd.config import get_discount
+    from tests.optim_common import widen as w
+
+    assert control is None or control in UPDATE_CONTROLS, control
+    ref = _import_reference()
+    K = int(iterations)
+    H, B, A = cfg.horizon, int(batch["action"].shape[1]), cfg.action_dim
+    enc_lr = w(cfg.lr * cfg.enc_lr_scale)  # the product the port's optimiser forms (tdmpc2.py:23), then fp32
+    cfg = cfg.replace(dropout=0.0, batch_size=B, lr=w(cfg.lr), grad_clip_norm=w(cfg.grad_clip_norm), rho=w(cfg.rho), tau=w(cfg.tau),
+                      entropy_coef=w(cfg.entropy_coef), consistency_coef=w(cfg.consistency_coef), reward_coef=w(cfg.reward_coef),
+                      value_coef=w(cfg.value_coef), termination_coef=w(cfg.termination_coef))
+    lr = cfg.lr
+    saved_dtype = torch.get_default_dtype()
+    torch.set_default_dtype(dtype)
+    try:
+        if cfg.multitask:  # tdmpc2.py:35-37: an fp32 tensor there
+            discount = torch.tensor([get_discount(cfg, n) for n in cfg.episode_lengths], dtype=torch.float32).to(dtype)
+        else:
+            discount = get_discount(cfg, cfg.episode_length)
+        agent = build_agent(cfg, state_dict, discount).to(dtype)
+        m = agent.model
+        if cfg.multitask:
+            assert torch.equal(m._action_masks, torch.as_tensor(state_dict["_action_masks"]).to(dtype))
+        # ---- restated: tdmpc2.py:22-31 without capturable
+        betas = (w(0.9), w(0.999))
+        agent.optim = torch.optim.Adam([
+            {"params": m._encoder.parameters(), "lr": lr if control == "enc_lr" else enc_lr},
+            {"params": m._dynamics.parameters()},
+            {"params": m._reward.parameters()},
+            {"params": m._termination.parameters() if cfg.episodic else []},
+            {"params": m._Qs.parameters()},
+            {"params": m._task_emb.parameters() if cfg.multitask else []},
+        ], lr=lr, betas=betas, eps=w(1e-8))
+        agent.pi_optim = torch.optim.Adam(m._pi.parameters(), lr=lr, betas=betas, eps=w(1e-8 if control == "pi_eps" else 1e-5))
+        # ---- restated: common/scale.py:8-12 without the constructor
+        RunningScale = sys.modules["common.scale"].RunningScale
+        scale = RunningScale.__new__(RunningScale)
+        nn.Module.__init__(scale)
+        scale.cfg = cfg
+        scale.value = torch.nn.Buffer(torch.full((1,), float(scale0), dtype=dtype))
+        scale._percentiles = torch.nn.Buffer(torch.tensor([5, 95], dtype=dtype))
+        agent.scale = scale
+
+        # ---- restated: world_model.py:82-86
+        def soft_update_target_Q():
+            with torch.no_grad():
+                for k in m._Qs.p:
+                    m._target_Qs.p[k].lerp_(m._Qs.p[k], cfg.tau)
+
+        moved = ("no_soft_update", "soft_update_first", "soft_update_before_step")
+        m.soft_update_target_Q = (lambda: None) if control in moved else soft_update_target_Q
+        # ---- hooks between the verbatim calls (controls only)
+        if control == "soft_update_first":
+            def update_pi(zs, task):
+                soft_update_target_Q()
+                return ref.TDMPC2.update_pi(agent, zs, task)
+
+            agent.update_pi = update_pi
+        if control == "soft_update_before_step":
+            step = agent.optim.step
+
+            def step_after_lerp(*a, **kw):
+                soft_update_target_Q()
+                return step(*a, **kw)
+
+            agent.optim.step = step_after_lerp
+        pi_at_start = []  # _pi's parameters at the start of every iteration
+        if control == "stale_pi_td":
+            def _td_target(next_z, reward, terminated, task):
+                now = [p.detach().clone() for p in m._pi.parameters()]
+                with torch.no_grad():
+                    for p, old in zip(m._pi.parameters(), pi_at_start[max(len(pi_at_start) - 2, 0)]):
+                        p.copy_(old)
+                    try:
+                        return ref.TDMPC2._td_target(agent, next_z, reward, terminated, task)
+                    finally:
+                        for p, cur in zip(m._pi.parameters(), now):
+                            p.copy_(cur)
+
+            agent._td_target = _td_target
+
+        f = lambda x: None if x is None else torch.as_tensor(np.asarray(x)).to(dtype)  # noqa: E731
+        obs, action, reward = f(batch["obs"]), f(batch["action"]), f(batch["reward"])
+        terminated = f(batch.get("terminated"))
+        if terminated is None:
+            terminated = torch.zeros(H, B, 1, dtype=dtype)
+        task = None if batch.get("task") is None else torch.as_tensor(np.asarray(batch["task"])).long()
+        assert obs.shape[:2] == (H + 1, B) and action.shape == (H, B, A) and reward.shape == (H, B, 1) and terminated.shape == (H, B, 1)
+
+        update_code = getattr(ref.TDMPC2._update, "__wrapped__", ref.TDMPC2._update).__code__
+        seen = {}
+
+        def tracer(frame, event, arg):
+            if frame.f_code is not update_code:
+                return None
+
+            def local(frame, event, arg):
+                if event == "return":
+                    seen["td"] = frame.f_locals["td_targets"].detach().clone()
+                    if cfg.episodic:
+                        seen["term"] = frame.f_locals["termination_pred"][-1].detach().clone()
+                return local
+
+            return local
+
+        infos, tds, terms = [], [], []
+        saved = (torch.randn_like, torch.randperm)
+        for k in range(K):
+            draws = [("randn_like", pins["td_pi_eps"][k], (H, B, A)), ("randperm", pins["td_qidx"][k], (2,)),
+                     ("randn_like", pins["pi_eps"][k], (H + 1, B, A)), ("randperm", pins["qidx"][k], (2,))]
+            for kind, v, shape in draws:
+                assert tuple(np.shape(v)) == shape, (k, kind, np.shape(v), shape)
+
+            def draw(kind, shape=None):
+                assert draws and draws[0][0] == kind, f"iteration {k}: the reference called {kind}, expected {draws[0][0] if draws else 'nothing'}"
+                _, v, want = draws.pop(0)
+                assert shape is None or tuple(shape) == want, (k, kind, tuple(shape), want)
+                return torch.as_tensor(np.asarray(v))
+
+            def randn_like(x, **kw):
+                return draw("randn_like", x.shape).to(x.dtype).clone()
+
+            def randperm(n, **kw):
+                first = draw("randperm").long()
+                rest = torch.tensor([i for i in range(n) if i not in first.tolist()], dtype=torch.long)
+                return torch.cat([first, rest])
+
+            pi_at_start.append([p.detach().clone() for p in m._pi.parameters()])
+            seen.clear()
+            torch.randn_like, torch.randperm = randn_like, randperm
+            sys.settrace(tracer)
+            try:
+                info = agent._update(obs, action, reward, terminated, task)
+            finally:
+                sys.settrace(None)
+                torch.randn_like, torch.randperm = saved
+            assert not draws, f"iteration {k}: the reference consumed {4 - len(draws)} of 4 draws"
+            if control == "no_emb_leak" and cfg.multitask:
+                m._task_emb.weight.grad = None
+            assert not m.training
+            infos.append({n: float(v) for n, v in info.items()})
+            tds.append(seen["td"])
+            terms.append(seen.get("term"))
+        return {"infos": infos, "td": torch.stack(tds).numpy(),
+                "term_logit": torch.stack(terms).numpy() if cfg.episodic else None}
+    finally:
+        torch.set_default_dtype(saved_dtype)
 
 
 def run_reference_plan(cfg, state_dict, *, obs=None, z0=None, tape, prev_mean, t0, eval_mode, task, discount,

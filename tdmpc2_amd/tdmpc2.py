@@ -635,21 +635,28 @@ class TDMPC2(torch.nn.Module):
         return {"pi_loss": pi_loss.detach(), "pi_grad_norm": pi_grad_norm.reshape(()), "pi_entropy": parts[0],
                 "pi_scaled_entropy": parts[1], "pi_scale": self.scale.value.detach().clone().reshape(())}
 
-    def _update(self, obs, action, reward, terminated=None, task=None):
+    def _update(self, obs, action, reward, terminated=None, task=None, pins=None):
         """`_update` of the reference (tdmpc2.py:259-332): `update_model`, then `update_pi(zs.detach(), task)` with the model still
         in train mode, then `soft_update_target_Q()`, then model.eval() and the reference's info dict as 0-d device tensors
         (consistency_loss, reward_loss, value_loss, termination_loss, total_loss, grad_norm; on episodic models termination_rate and
         termination_f1 of the last step through `termination_stats`; pi_loss, pi_grad_norm, pi_entropy, pi_scaled_entropy,
-        pi_scale).  Equality with the reference holds for cfg.dropout == 0: the port's QEnsemble has no dropout."""
+        pi_scale).  Equality with the reference holds for cfg.dropout == 0: the port's QEnsemble has no dropout.
+        `pins` (parity tests): a dict with any of td_pi_eps [H, B, A] / td_qidx (the TD target's noise and heads), td_targets
+        [H, B, 1] (the target itself), pi_eps [H+1, B, A] / qidx (`update_pi`'s); None: every draw is made as before."""
         from .native import NativeError
         if not self.native_autograd:
             raise NativeError("_update runs in the library: set native_autograd = True")
         cfg = self.cfg
+        pins = dict(pins or {})
+        unknown = set(pins) - {"td_pi_eps", "td_qidx", "td_targets", "pi_eps", "qidx"}
+        if unknown:
+            raise ValueError(f"_update: unknown pins {sorted(unknown)}")
         if terminated is None:
             terminated = torch.zeros(action.shape[0], action.shape[1], 1, device=self.device)
         try:
-            info = self._update_model(obs, action, reward, terminated, task, None, None, None, keep_train=True)
-            pi_info = self.update_pi(self.last_zs, task)
+            info = self._update_model(obs, action, reward, terminated, task, pins.get("td_targets"), pins.get("td_pi_eps"),
+                                      pins.get("td_qidx"), keep_train=True)
+            pi_info = self.update_pi(self.last_zs, task, pi_eps=pins.get("pi_eps"), qidx=pins.get("qidx"))
             self.soft_update_target_Q()
         finally:
             self.model.eval()
