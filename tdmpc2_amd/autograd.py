@@ -97,12 +97,46 @@ def mlp_apply(seq, x):
     return x
 
 
-def ensemble_apply(params, x):
-    """`QEnsemble.apply_params(params, x)` for a `layers.StackedMLPParams`: x [..., K] -> [n, ..., out]; the first layer reads the
-    one x for every member (shared_x), so its dx is the sum over members."""
+class DropoutMasks:
+    """A device-side stream of dropout masks (tdmpc2_dropout_mask): Philox keyed by `seed`, counted by two words on the device that
+    every `draw` advances by one in stream order.  Nothing here reads the device or synchronises, so a draw can be captured in a
+    graph, and every replay then draws the next mask."""
+
+    def __init__(self, seed: int, device):
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise native.NativeError(f"DropoutMasks draws on an MI355X only (device {self.device}); there is no CPU fallback")
+        self.state = torch.zeros(2, dtype=torch.int32, device=self.device)  # the call counter (lo, hi)
+
+    def draw(self, shape, p: float):
+        """-> a fresh fp32 tensor of `shape` holding 0 (probability floor(p 2^32) / 2^32) or 1 / (1 - p), from torch's allocator."""
+        out = torch.empty(tuple(int(s) for s in shape), dtype=torch.float32, device=self.device)
+        native.dropout_mask(native.dropout_desc(out.numel(), p, self.seed), self.state, out)
+        return out
+
+    def state_dict(self):
+        """The seed and the counter (one device read): enough to resume the stream.  Not part of the reference's checkpoint."""
+        lo, hi = (int(v) & 0xFFFFFFFF for v in self.state.tolist())
+        return {"seed": self.seed, "counter": (hi << 32) | lo}
+
+    def load_state_dict(self, sd):
+        self.seed = int(sd["seed"]) & 0xFFFFFFFFFFFFFFFF
+        c = int(sd["counter"]) & 0xFFFFFFFFFFFFFFFF
+        words = [w - (1 << 32) if w >= (1 << 31) else w for w in (c & 0xFFFFFFFF, c >> 32)]
+        self.state.copy_(torch.tensor(words, dtype=torch.int32))
+
+
+def ensemble_apply(params, x, mask=None):
+    """`QEnsemble.apply_params(params, x, mask)` for a `layers.StackedMLPParams`: x [..., K] -> [n, ..., out]; the first layer reads
+    the one x for every member (shared_x), so its dx is the sum over members.  mask: None, or the dropout multipliers of the first
+    layer's Linear output, [n, ..., hidden] (fp32, e.g. a `DropoutMasks.draw`); the other layers have none."""
     l0, l1, l2 = params.layer(0), params.layer(1), params.layer(2)
     shared = params.n > 1  # (one member: its x is simply [1, ..., K])
-    h = LayerFn.apply(x if shared else x.unsqueeze(0), l0.weight, l0.bias, l0.ln.weight, l0.ln.bias, None, native.LAYER_MISH, shared, 0,
+    if mask is not None and tuple(mask.shape) != (params.n, *x.shape[:-1], l0.weight.shape[-2]):
+        raise native.NativeError(f"ensemble_apply: mask {tuple(mask.shape)} is not [n, ..., hidden] = "
+                                 f"{(params.n, *x.shape[:-1], l0.weight.shape[-2])}")
+    h = LayerFn.apply(x if shared else x.unsqueeze(0), l0.weight, l0.bias, l0.ln.weight, l0.ln.bias, mask, native.LAYER_MISH, shared, 0,
                       1e-5)
     h = LayerFn.apply(h, l1.weight, l1.bias, l1.ln.weight, l1.ln.bias, None, native.LAYER_MISH, False, 0, 1e-5)
     return LayerFn.apply(h, l2.weight, l2.bias, None, None, None, native.LAYER_LINEAR, False, 0, 0.0)

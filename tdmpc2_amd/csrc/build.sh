@@ -18,8 +18,9 @@
 #   k_optim.hip                optimiser step: gradient clip + Adam over flat arenas, its own C ABI (tdmpc2_optim_*); no fp contraction
 #   k_loss_grad.hip            loss seeds: the four losses of _update and their gradients, its own C ABI (tdmpc2_loss_*)
 #   k_pi_grad.hip              policy loss seeds: update_pi's head, value, loss and their gradients, its own C ABI and header (tdmpc2_pigrad_*, include/tdmpc2_pi_grad.h)
+#   k_dropout.hip              dropout masks: Philox multipliers for the Q ensemble's first layer, its own C ABI and header (tdmpc2_dropout_*, include/tdmpc2_dropout.h)
 # Objects are cached under build/ and rebuilt when a source they include is newer (make-style), so an experiment on one
-# family recompiles one file.  TDMPC2_EXTRA_FLAGS (all units), TDMPC2_FLAGS_<unit> (one unit: main, fused, cluster, layered, policy, model, ploss, refresh, pixbatch, buffer, lgrad, optim, lossgrad, pigrad),
+# family recompiles one file.  TDMPC2_EXTRA_FLAGS (all units), TDMPC2_FLAGS_<unit> (one unit: main, fused, cluster, layered, policy, model, ploss, refresh, pixbatch, buffer, lgrad, optim, lossgrad, pigrad, dropout),
 # TDMPC2_ONLY_APAD=48 (experiment builds: the fused / cluster units of one padding only), TDMPC2_OUT, TDMPC2_BUILD_DIR, JOBS.
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
@@ -52,6 +53,7 @@ UNITS+=("lgrad|k_layer_grad.hip|${TDMPC2_FLAGS_lgrad:-}")  # trainable layer: No
 UNITS+=("optim|k_optim.hip|-ffp-contract=off ${TDMPC2_FLAGS_optim:-}")
 UNITS+=("lossgrad|k_loss_grad.hip|${TDMPC2_FLAGS_lossgrad:-}")  # loss seeds: _update's four losses and their gradients, its own C ABI (tdmpc2_loss_*)
 UNITS+=("pigrad|k_pi_grad.hip|${TDMPC2_FLAGS_pigrad:-}")  # policy loss seeds: update_pi between its layers, forward and backward, its own C ABI (tdmpc2_pigrad_*)
+UNITS+=("dropout|k_dropout.hip|${TDMPC2_FLAGS_dropout:-}")  # dropout masks: Philox multipliers drawn on the device, its own C ABI (tdmpc2_dropout_*)
 for ap in ${APADS}; do
     UNITS+=("fused${ap}|k_fused.hip|-DTU_APAD=${ap} ${TDMPC2_FLAGS_fused:-}")
     UNITS+=("cluster${ap}|k_cluster.hip|-DTU_APAD=${ap} ${TDMPC2_FLAGS_cluster:-}")
@@ -66,7 +68,7 @@ compile_unit() {  # name src flags
     [ -f "${obj}" ] || need=1
     [ -f "${stamp}" ] && [ "$(cat "${stamp}")" == "${want}" ] || need=1
     if [ "${need}" == 0 ]; then
-        for dep in "${HERE}"/*.hip "${HERE}"/*.cuh "${HERE}"/*.h "${HERE}/../../include/tdmpc2_plan.h" "${HERE}/../../include/tdmpc2_pi_grad.h"; do
+        for dep in "${HERE}"/*.hip "${HERE}"/*.cuh "${HERE}"/*.h "${HERE}/../../include/tdmpc2_plan.h" "${HERE}/../../include/tdmpc2_pi_grad.h" "${HERE}/../../include/tdmpc2_dropout.h"; do
             if [ "${dep}" -nt "${obj}" ] && grep -q "$(basename "${dep}")" <(unit_deps "${src}"); then need=1; break; fi
         done
     fi

@@ -170,11 +170,15 @@ class QEnsemble(nn.Module):
         return self._n
 
     @staticmethod
-    def apply_params(p: StackedMLPParams, x):
+    def apply_params(p: StackedMLPParams, x, mask=None):
+        """mask: None, or dropout's multipliers of layer 0's Linear output, [n, ..., hidden] (reference common/layers.py:107-111:
+        between the Linear and its LayerNorm, on the first layer only)."""
         h = x.unsqueeze(0).expand(p.n, *x.shape)
         for i in (0, 1):
             l = p.layer(i)
             h = torch.baddbmm(l.bias.unsqueeze(1), h, l.weight.transpose(1, 2))
+            if i == 0 and mask is not None:
+                h = h * mask.to(h.dtype).reshape(h.shape)
             h = F.layer_norm(h, (h.shape[-1],), None, None, 1e-5) * l.ln.weight.unsqueeze(1) + l.ln.bias.unsqueeze(1)
             h = F.mish(h)
         l = p.layer(2)

@@ -46,6 +46,8 @@ ABI_SYMBOLS = [
 # include/tdmpc2_pi_grad.h: the policy-loss unit, a header of its own beside ABI 14 (whose version and symbols stay as they are)
 PI_GRAD_SYMBOLS = ("tdmpc2_pigrad_head_forward", "tdmpc2_pigrad_head_backward", "tdmpc2_pigrad_value_forward",
                    "tdmpc2_pigrad_loss_forward", "tdmpc2_pigrad_loss_backward")
+# include/tdmpc2_dropout.h: the dropout-mask unit, again a header of its own beside ABI 14
+DROPOUT_SYMBOLS = ("tdmpc2_dropout_mask",)
 
 NET_DYNAMICS, NET_REWARD, NET_PI, NET_Q, NET_TERMINATION, NET_TARGET_Q = range(6)
 PATH_AUTO, PATH_FUSED, PATH_LAYERED = range(3)  # enum tdmpc2_path
@@ -175,6 +177,11 @@ class LossDesc(C.Structure):  # struct tdmpc2_loss_desc
 class PiGradDesc(C.Structure):  # struct tdmpc2_pigrad_desc (include/tdmpc2_pi_grad.h)
     _fields_ = [(n, C.c_int32) for n in ("steps", "batch", "action_dim", "num_bins", "multitask")] + \
                [(n, C.c_float) for n in ("vmin", "vmax", "rho", "entropy_coef", "log_std_min", "log_std_dif")]
+
+
+class DropoutDesc(C.Structure):  # struct tdmpc2_dropout_desc (include/tdmpc2_dropout.h)
+    _fields_ = [("n", C.c_int64), ("p", C.c_float), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("call_lo", C.c_uint32),
+                ("call_hi", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class Debug(C.Structure):
@@ -366,6 +373,8 @@ def _open(path):
         fn = getattr(lib, name)
         fn.argtypes = [C.POINTER(PiGradDesc)] + [vp] * nptr
         fn.restype = i32
+    lib.tdmpc2_dropout_mask.argtypes = [C.POINTER(DropoutDesc), vp, vp, vp]
+    lib.tdmpc2_dropout_mask.restype = i32
     if lib.tdmpc2_plan_abi_version() != ABI_VERSION:
         raise NativeError(f"ABI version mismatch: library {lib.tdmpc2_plan_abi_version()}, binding {ABI_VERSION}")
     return lib
@@ -1722,3 +1731,36 @@ def pigrad_loss_backward(desc: PiGradDesc, q_logits, scale, grad_total=None, d_q
     None are overwritten."""
     _pigrad_call("pigrad_loss_backward", desc, q_logits, q_logits=q_logits, scale=scale, grad_total=grad_total, d_q_logits=d_q_logits,
                  d_scaled_entropy=d_scaled_entropy)
+
+
+# ---------------------------------------------------------------- dropout masks (tdmpc2_dropout_mask, include/tdmpc2_dropout.h)
+DROPOUT_CALLS = 0  # library calls made through the wrapper below, kept like PI_GRAD_CALLS
+
+
+def dropout_desc(n: int, p: float, seed: int = 0, call: int = 0) -> DropoutDesc:
+    """n elements at drop probability p; `seed` is the 64-bit Philox key, `call` the 64-bit call counter (read only when the call is
+    given no device counter)."""
+    seed, call = int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFFFFFFFFFF
+    return DropoutDesc(n=int(n), p=float(p), seed_lo=seed & 0xFFFFFFFF, seed_hi=seed >> 32, call_lo=call & 0xFFFFFFFF,
+                       call_hi=call >> 32, reserved=0)
+
+
+def dropout_mask(desc: DropoutDesc, state, out):
+    """tdmpc2_dropout_mask on the current stream: `out` (contiguous fp32 on the GPU, at least desc.n elements, 16-byte aligned) is
+    overwritten with dropout's multipliers.  `state`: None (the descriptor's call counter is used) or two int32 words on the same
+    device holding the counter, which the call advances by one in stream order.  No host read, no synchronisation."""
+    global DROPOUT_CALLS
+    if out.device.type != "cuda":
+        raise NativeError(f"dropout_mask runs on an MI355X only (device {out.device}); there is no CPU fallback")
+    _layer_tensors("dropout_mask", out.device, mask=out)
+    if out.numel() < desc.n:
+        raise NativeError(f"dropout_mask: mask holds {out.numel()} floats, the descriptor asks for {desc.n}")
+    if state is not None and (state.device != out.device or state.dtype != torch.int32 or state.numel() != 2
+                              or not state.is_contiguous()):
+        raise NativeError(f"dropout_mask: state must be two contiguous int32 words on {out.device} (got {state.dtype}, {state.device}, "
+                          f"{state.numel()} elements)")
+    DROPOUT_CALLS += 1
+    with torch.cuda.device(out.device):
+        rc = load_library().tdmpc2_dropout_mask(C.byref(desc), _ptr(state), _ptr(out), torch.cuda.current_stream(out.device).cuda_stream)
+    if rc != 0:
+        raise NativeError(f"tdmpc2_dropout error {rc}: {load_library().tdmpc2_last_error().decode()}")

@@ -89,6 +89,15 @@ class TDMPC2(torch.nn.Module):
     def native_autograd(self, on: bool):
         self.model.native_autograd = bool(on)
 
+    @property
+    def native_dropout(self) -> bool:
+        """True: in train mode the Q ensemble's first layer drops with masks drawn in the library (WorldModel.native_dropout)."""
+        return self.model.native_dropout
+
+    @native_dropout.setter
+    def native_dropout(self, on: bool):
+        self.model.native_dropout = bool(on)
+
     # ------------------------------------------------------------------ checkpoint I/O
     def save(self, fp):
         """reference tdmpc2.py:72-79."""
@@ -535,7 +544,7 @@ class TDMPC2(torch.nn.Module):
         return res
 
     # ------------------------------------------------------------------ the model half of _update as one method
-    def update_model(self, obs, action, reward, terminated=None, task=None, td_targets=None, pi_eps=None, qidx=None):
+    def update_model(self, obs, action, reward, terminated=None, task=None, td_targets=None, pi_eps=None, qidx=None, q_mask=None):
         """The model half of `_update` (reference tdmpc2.py:260-310: everything but `update_pi` and the target-Q soft update), every
         piece in the library: obs [H+1, B, *], action [H, B, A], reward / terminated [H, B, 1], task [B].  In order:
           1. under no_grad, next_z = encode(obs[1:]) and the TD target (`_td_target`, or `td_targets` [H, B, 1] as given; `pi_eps` /
@@ -546,15 +555,16 @@ class TDMPC2(torch.nn.Module):
           5. `optimizer_step("model")`: clip, Adam, zero_grad and the planner's re-pack;
           6. model.eval().
         Returns consistency_loss, reward_loss, value_loss, termination_loss, total_loss and grad_norm as 0-d device tensors.
-        Raises NativeError when `native_autograd` is off: there is no torch path.  It equals the reference when cfg.dropout == 0:
-        the port's QEnsemble has no dropout in any mode, where the reference's Q heads drop inputs of their first layer in
-        train mode.  It also leaves `last_zs` ([H+1, B, L], detached) and, on episodic models, `last_term_logit` ([H, B, 1])."""
+        Raises NativeError when `native_autograd` is off: there is no torch path.  The reference's Q heads drop elements of their
+        first layer's Linear output in train mode (cfg.dropout): with `native_dropout` step 3's Q pass draws those masks in the library
+        (`q_mask` [num_q, H, B, mlp_dim] pins them); with the flag off there is no dropout, and the call equals the reference when
+        cfg.dropout == 0.  It also leaves `last_zs` ([H+1, B, L], detached) and, on episodic models, `last_term_logit` ([H, B, 1])."""
         from .native import NativeError
         if not self.native_autograd:
             raise NativeError("update_model runs the model's layers and losses in the library: set native_autograd = True")
-        return self._update_model(obs, action, reward, terminated, task, td_targets, pi_eps, qidx, keep_train=False)
+        return self._update_model(obs, action, reward, terminated, task, td_targets, pi_eps, qidx, keep_train=False, q_mask=q_mask)
 
-    def _update_model(self, obs, action, reward, terminated, task, td_targets, pi_eps, qidx, keep_train):
+    def _update_model(self, obs, action, reward, terminated, task, td_targets, pi_eps, qidx, keep_train, q_mask=None):
         """`update_model`; keep_train: its step 6 is left to the caller (`_update`, which runs `update_pi` in train mode first)."""
         from . import autograd
         cfg = self.cfg
@@ -582,7 +592,7 @@ class TDMPC2(torch.nn.Module):
                 z = self.model.next(z, action[t], task)
                 zs.append(z)
             _zs, z_pred = torch.stack(zs[:-1]), torch.stack(zs[1:])
-            qs = self.model.Q(_zs, action, task, return_type="all")
+            qs = self.model.Q(_zs, action, task, return_type="all", q_mask=q_mask)
             reward_preds = self.model.reward(_zs, action, task)
             term_pred = self.model.termination(z_pred, task, unnormalized=True) if cfg.episodic else None
             total, parts = autograd.model_loss(cfg, z_pred, next_z, reward_preds, reward, qs, td_targets, term_pred,
@@ -598,7 +608,7 @@ class TDMPC2(torch.nn.Module):
                 "total_loss": total.detach(), "grad_norm": grad_norm}
 
     # ------------------------------------------------------------------ the policy half of _update, and _update itself
-    def update_pi(self, zs, task=None, pi_eps=None, qidx=None):
+    def update_pi(self, zs, task=None, pi_eps=None, qidx=None, q_mask=None):
         """`update_pi` of the reference (tdmpc2.py:208-239) in its order, every piece in the library: zs [H+1, B, L] (detached here
         as `_update` detaches it), task [B].
           1. action, info = model.pi(zs, task): the MLP through the trainable layer, its tail through `autograd.PiHeadFn`
@@ -610,8 +620,10 @@ class TDMPC2(torch.nn.Module):
           6. `optimizer_step("pi")`: clip at cfg.grad_clip_norm, Adam with eps 1e-5, zero_grad and the planner's re-pack.
         Returns pi_loss, pi_grad_norm, pi_entropy, pi_scaled_entropy (means, as `_update` reports them) and pi_scale as 0-d device
         tensors.  The model's mode is left as it is (`_update` calls this in train mode, as the reference does).  Raises
-        NativeError when `native_autograd` is off: there is no torch path.  It equals the reference when cfg.dropout == 0: the
-        port's QEnsemble has no dropout in any mode."""
+        NativeError when `native_autograd` is off: there is no torch path.  The reference's detached Q copy is a train-mode copy,
+        so its first layers drop here too: in train mode with `native_dropout` step 2 draws the two heads' masks in the library
+        (`q_mask` [2, H+1, B, mlp_dim] pins them); with the flag off there is no dropout, and the call equals the reference when
+        cfg.dropout == 0."""
         from . import autograd
         from .native import NativeError
         if not self.native_autograd:
@@ -628,7 +640,7 @@ class TDMPC2(torch.nn.Module):
             qidx = torch.randperm(cfg.num_q, device=self.device)[:2]
         self.pi_optim  # noqa: B018  (made before backward: every .grad of _pi is then a view into its gradient arena)
         action, info = self.model.pi(zs, task, eps=pi_eps)
-        q_logits = self.model.Q_pair(zs, action, task, qidx)
+        q_logits = self.model.Q_pair(zs, action, task, qidx, q_mask=q_mask)
         pi_loss, parts = autograd.pi_loss(cfg, q_logits, info["entropy"], info["scaled_entropy"], self.scale)
         pi_loss.backward()
         pi_grad_norm = self.optimizer_step("pi").clone()
@@ -640,23 +652,27 @@ class TDMPC2(torch.nn.Module):
         in train mode, then `soft_update_target_Q()`, then model.eval() and the reference's info dict as 0-d device tensors
         (consistency_loss, reward_loss, value_loss, termination_loss, total_loss, grad_norm; on episodic models termination_rate and
         termination_f1 of the last step through `termination_stats`; pi_loss, pi_grad_norm, pi_entropy, pi_scaled_entropy,
-        pi_scale).  Equality with the reference holds for cfg.dropout == 0: the port's QEnsemble has no dropout.
+        pi_scale).  With `native_dropout` (and cfg.dropout > 0) the two train-mode Q passes drop as the reference's do: one `_update`
+        makes exactly two mask draws, the value-loss pass first, then `update_pi`'s pair; the TD target draws none (the target
+        ensemble is in eval mode in the reference too).  With the flag off there is no dropout, and equality with the reference holds
+        for cfg.dropout == 0.
         `pins` (parity tests): a dict with any of td_pi_eps [H, B, A] / td_qidx (the TD target's noise and heads), td_targets
-        [H, B, 1] (the target itself), pi_eps [H+1, B, A] / qidx (`update_pi`'s); None: every draw is made as before."""
+        [H, B, 1] (the target itself), pi_eps [H+1, B, A] / qidx (`update_pi`'s), q_mask [num_q, H, B, mlp_dim] (the value-loss
+        pass's dropout multipliers) and pi_q_mask [2, H+1, B, mlp_dim] (`update_pi`'s); None: every draw is made as before."""
         from .native import NativeError
         if not self.native_autograd:
             raise NativeError("_update runs in the library: set native_autograd = True")
         cfg = self.cfg
         pins = dict(pins or {})
-        unknown = set(pins) - {"td_pi_eps", "td_qidx", "td_targets", "pi_eps", "qidx"}
+        unknown = set(pins) - {"td_pi_eps", "td_qidx", "td_targets", "pi_eps", "qidx", "q_mask", "pi_q_mask"}
         if unknown:
             raise ValueError(f"_update: unknown pins {sorted(unknown)}")
         if terminated is None:
             terminated = torch.zeros(action.shape[0], action.shape[1], 1, device=self.device)
         try:
             info = self._update_model(obs, action, reward, terminated, task, pins.get("td_targets"), pins.get("td_pi_eps"),
-                                      pins.get("td_qidx"), keep_train=True)
-            pi_info = self.update_pi(self.last_zs, task, pi_eps=pins.get("pi_eps"), qidx=pins.get("qidx"))
+                                      pins.get("td_qidx"), keep_train=True, q_mask=pins.get("q_mask"))
+            pi_info = self.update_pi(self.last_zs, task, pi_eps=pins.get("pi_eps"), qidx=pins.get("qidx"), q_mask=pins.get("pi_q_mask"))
             self.soft_update_target_Q()
         finally:
             self.model.eval()

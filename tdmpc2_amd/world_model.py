@@ -96,6 +96,11 @@ class WorldModel(nn.Module):
         # True (and the input on the GPU): the MLPs of encode (state), next, reward, termination, pi and Q run through the library's
         # trainable layer (tdmpc2_amd/autograd.py), so loss.backward() computes their gradients in HIP; off by default -- the modules
         self.native_autograd = False
+        # True (train mode, cfg.dropout > 0, the input on the GPU): Q and Q_pair multiply the first layer's Linear output of every
+        # member by a dropout mask drawn in the library (autograd.DropoutMasks, tdmpc2_dropout_mask), as the reference's Q heads do in
+        # train mode; off by default -- no dropout in any mode
+        self.native_dropout = False
+        self._q_masks = None  # made by the first read of `q_masks`
         self._log_std_host = None  # host copies of log_std_min / log_std_dif for the library's policy head (made at first use)
         self.apply(self._weight_init)
         self._register_state_dict_hook(self._add_meta_keys)
@@ -245,10 +250,28 @@ class WorldModel(nn.Module):
         return action.view(*lead, A), {"mean": torch.tanh(mean), "log_std": log_std, "action_prob": 1.0, "entropy": entropy,
                                        "scaled_entropy": se.view(*lead, 1)}
 
-    def Q_pair(self, z, a, task, qidx):
+    @property
+    def q_masks(self):
+        """The mask stream of the Q ensemble's dropout (autograd.DropoutMasks keyed by cfg.seed), made on the model's device at first use."""
+        if self._q_masks is None:
+            self._q_masks = autograd.DropoutMasks(int(getattr(self.cfg, "seed", 0)), self.log_std_min.device)
+        return self._q_masks
+
+    def _q_mask(self, n, za, q_mask):
+        """The mask of a Q pass over the rows `za` [..., K] for n members: the one given, or in train mode with `native_dropout`,
+        cfg.dropout > 0 and the input on the GPU a fresh draw [n, ..., mlp_dim]; else None."""
+        if q_mask is not None:
+            return q_mask
+        if self.training and self.native_dropout and self.cfg.dropout > 0 and za.is_cuda:
+            return self.q_masks.draw((n, *za.shape[:-1], self.cfg.mlp_dim), self.cfg.dropout)
+        return None
+
+    def Q_pair(self, z, a, task, qidx, q_mask=None):
         """The logits of the two heads `qidx` of the online ensemble on DETACHED parameters -> [2, ..., num_bins]: the reference's
         Q(z, a, task, return_type='avg', detach=True) (world_model.py:186-216) before two_hot_inv, restricted to the two drawn heads
-        -- 2 of num_q members' work; gradient reaches `a` (and z), never `_Qs`.  qidx: two head indices (tensor or sequence)."""
+        -- 2 of num_q members' work; gradient reaches `a` (and z), never `_Qs`.  qidx: two head indices (tensor or sequence).  q_mask [2, ..., mlp_dim]: the first layer's dropout multipliers of
+        the two heads; None: drawn for the two heads only under the conditions of `_q_mask` (the members' masks are independent, so
+        this is the reference's distribution), else no dropout."""
         from types import SimpleNamespace
         if self.cfg.multitask:
             z = self.task_emb(z, task)
@@ -262,17 +285,24 @@ class WorldModel(nn.Module):
             return SimpleNamespace(weight=pick(l.weight), bias=pick(l.bias), ln=ln)
 
         sel = SimpleNamespace(n=2, layer=layer)
+        q_mask = self._q_mask(2, za, q_mask)
         if self.native_autograd and za.is_cuda:
-            return autograd.ensemble_apply(sel, za)
-        return layers.QEnsemble.apply_params(sel, za)
+            return autograd.ensemble_apply(sel, za, q_mask)
+        return layers.QEnsemble.apply_params(sel, za, q_mask)
 
-    def Q(self, z, a, task, return_type="min"):
+    def Q(self, z, a, task, return_type="min", q_mask=None):
+        """reference world_model.py:186-216 on the online ensemble.  q_mask [num_q, ..., mlp_dim]: the first layer's dropout
+        multipliers; None: drawn under the conditions of `_q_mask` (train mode, `native_dropout`, cfg.dropout > 0, GPU), else no
+        dropout."""
         assert return_type in {"min", "avg", "all"}
         if self.cfg.multitask:
             z = self.task_emb(z, task)
         za = torch.cat([z, a], dim=-1)
+        q_mask = self._q_mask(self.cfg.num_q, za, q_mask)
         if self.native_autograd and za.is_cuda:
-            out = autograd.ensemble_apply(self._Qs.params, za)
+            out = autograd.ensemble_apply(self._Qs.params, za, q_mask)
+        elif q_mask is not None:
+            out = layers.QEnsemble.apply_params(self._Qs.params, za, q_mask)
         else:
             out = self._Qs(za)
         if return_type == "all":
