@@ -8,13 +8,7 @@
 // Table: the episodes with at least S = slice_len live steps, as {first_logical, len}, in a ring of capacity / S + 1 entries:
 // appended at the tail, shrunk or popped at the head only (eviction always strikes the oldest steps).
 #pragma once
-#include <stdint.h>
-#ifndef __host__  // the host compiler of the test
-#define __host__
-#endif
-#ifndef __device__
-#define __device__
-#endif
+#include "seed_route.h"  // <math.h>, <stdint.h> and the __host__ / __device__ shim for the host compiler of the test
 
 enum { BUF_MAX_FIELDS = 8, BUF_THREADS = 256 };
 enum { BUF_CHUNK_UNITS = 768 };   // accesses per workgroup of a split row: 3 per thread, all loads in flight before the stores

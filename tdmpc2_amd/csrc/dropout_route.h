@@ -9,14 +9,7 @@
 // One thread per quad, DROP_THREADS per workgroup, at most DROP_MAX_BLOCKS workgroups: thread t of workgroup b takes quads
 // b * DROP_THREADS + t, + grid * DROP_THREADS, ... below drop_quads(n).
 #pragma once
-#include <math.h>
-#include <stdint.h>
-#ifndef __host__  // the host compiler of the test
-#define __host__
-#endif
-#ifndef __device__
-#define __device__
-#endif
+#include "seed_route.h"  // <math.h>, <stdint.h> and the __host__ / __device__ shim for the host compiler of the test
 
 // 2048 workgroups of 256 threads: 8 per compute unit of an MI355X, 2^21 elements (8 MiB) in one pass
 enum { DROP_THREADS = 256, DROP_MAX_BLOCKS = 2048 };

@@ -59,7 +59,7 @@ int tdmpc2_loss_forward(const tdmpc2_loss_desc *desc, const float *z_pred, const
     LsFwdParams fp{};
     fp.d = d;
     fp.g = ls_grid(d, false, 0);
-    if (fp.g.first[LS_KINDS] > 0x7fffffffull) return fail(TDMPC2_ERR_UNSUPPORTED, "loss_forward: more than 2^31 workgroups in one launch");
+    if (int rc = grid_fits(fp.g.first[LS_KINDS], "loss_forward")) return rc;
     if (!ws) return fail(TDMPC2_ERR_INVALID, "loss_forward: null workspace");
     if (ws_bytes < ls_ws_bytes(d))
         return fail(TDMPC2_ERR_INVALID, "loss_forward: workspace of %llu bytes is too small, %llu needed (tdmpc2_loss_workspace_bytes)",
@@ -96,7 +96,7 @@ int tdmpc2_loss_backward(const tdmpc2_loss_desc *desc, const float *z_pred, cons
     LsBwdParams bp{};
     bp.d = d;
     bp.g = ls_grid(d, true, want);
-    if (bp.g.first[LS_KINDS] > 0x7fffffffull) return fail(TDMPC2_ERR_UNSUPPORTED, "loss_backward: more than 2^31 workgroups in one launch");
+    if (int rc = grid_fits(bp.g.first[LS_KINDS], "loss_backward")) return rc;
     bp.z_pred = z_pred; bp.next_z = next_z; bp.reward_logits = reward_logits; bp.reward = reward; bp.q_logits = q_logits;
     bp.td_target = td_target; bp.term_logit = term_logit; bp.terminated = terminated; bp.grad_total = grad_total;
     for (int k = 0; k < LS_KINDS; ++k)

@@ -2,7 +2,7 @@
 // It shares nothing with a planner handle: the re-pack of the planner's weights stays tdmpc2_plan_refresh_weights, issued after
 // the step.  Every decision (layout, chunks, the order of the norm, grids, the device block) is optim_route.h's; this file checks
 // arguments, then launches.  A step allocates nothing, copies nothing from the host and never synchronises: it can be captured.
-#include "handle.h"
+#include "launch.h"  // handle.h + grid_fits
 #include "optim_route.h"
 
 namespace {
@@ -80,7 +80,7 @@ int tdmpc2_optim_create(const tdmpc2_optim_cfg *cfg, tdmpc2_optim_t **out) {
     *out = nullptr;
     if (int rc = opt_validate(cfg, "optim_create")) return rc;
     const uint64_t arena = opt_arena(cfg, nullptr), chunks = opt_chunks(arena);
-    if (chunks > 0x7fffffffull) return fail(TDMPC2_ERR_UNSUPPORTED, "optim_create: more than 2^31 workgroups in one launch");
+    if (int rc = grid_fits(chunks, "optim_create")) return rc;
     tdmpc2_optim *o = new (std::nothrow) tdmpc2_optim();
     if (!o) return fail(TDMPC2_ERR_HIP, "optim_create: out of host memory");
     o->device = cfg->device;

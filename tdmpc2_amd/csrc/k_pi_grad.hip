@@ -36,11 +36,6 @@ int pg_mask(const PgDesc &d, const void *mask, const char *what) {
                     d.multitask ? "required" : "NULL on a single-task model", d.multitask);
     return 0;
 }
-
-int pg_grid_fits(uint64_t blocks, const char *what) {
-    if (blocks > 0x7fffffffull) return fail(TDMPC2_ERR_UNSUPPORTED, "%s: more than 2^31 workgroups in one launch", what);
-    return 0;
-}
 }  // namespace
 
 extern "C" {
@@ -52,7 +47,7 @@ int tdmpc2_pigrad_head_forward(const tdmpc2_pigrad_desc *desc, const float *pi_o
     if (!pi_out || !eps || !action || !entropy || !scaled_entropy)
         return fail(TDMPC2_ERR_INVALID, "pigrad_head_forward: null pi_out, eps, action, entropy or scaled_entropy");
     if (int rc = pg_mask(d, action_mask, "pigrad_head_forward")) return rc;
-    if (int rc = pg_grid_fits(pg_head_grid(d), "pigrad_head_forward")) return rc;
+    if (int rc = grid_fits(pg_head_grid(d), "pigrad_head_forward")) return rc;
     PgHeadParams hp{};
     hp.d = d;
     hp.pi_out = pi_out; hp.eps = eps; hp.mask = action_mask; hp.action = action; hp.entropy = entropy; hp.se = scaled_entropy;
@@ -70,7 +65,7 @@ int tdmpc2_pigrad_head_backward(const tdmpc2_pigrad_desc *desc, const float *pi_
     if (!d_action && !d_scaled_entropy)
         return fail(TDMPC2_ERR_INVALID, "pigrad_head_backward: d_action and d_scaled_entropy are both null: no incoming gradient");
     if (!d_pi_out) return fail(TDMPC2_ERR_INVALID, "pigrad_head_backward: d_pi_out is null: nothing to compute");
-    if (int rc = pg_grid_fits(pg_head_grid(d), "pigrad_head_backward")) return rc;
+    if (int rc = grid_fits(pg_head_grid(d), "pigrad_head_backward")) return rc;
     PgHeadParams hp{};
     hp.d = d;
     hp.pi_out = pi_out; hp.eps = eps; hp.mask = action_mask; hp.d_action = d_action; hp.d_se = d_scaled_entropy; hp.d_pi_out = d_pi_out;
@@ -83,7 +78,7 @@ int tdmpc2_pigrad_value_forward(const tdmpc2_pigrad_desc *desc, const float *q_l
     PgDesc d;
     if (int rc = pg_desc(desc, d, "pigrad_value_forward")) return rc;
     if (!q_logits || !q) return fail(TDMPC2_ERR_INVALID, "pigrad_value_forward: null q_logits or q");
-    if (int rc = pg_grid_fits(pg_value_grid(d), "pigrad_value_forward")) return rc;
+    if (int rc = grid_fits(pg_value_grid(d), "pigrad_value_forward")) return rc;
     PgValueParams vp{};
     vp.d = d;
     vp.q_logits = q_logits; vp.q = q;
@@ -117,7 +112,7 @@ int tdmpc2_pigrad_loss_backward(const tdmpc2_pigrad_desc *desc, const float *q_l
     PgBwdParams bp{};
     bp.d = d;
     bp.g = pg_bwd_grid(d, want);
-    if (int rc = pg_grid_fits(bp.g.first[PG_KINDS], "pigrad_loss_backward")) return rc;
+    if (int rc = grid_fits(bp.g.first[PG_KINDS], "pigrad_loss_backward")) return rc;
     bp.q_logits = q_logits; bp.scale = scale; bp.grad_total = grad_total; bp.d_q_logits = d_q_logits; bp.d_se = d_scaled_entropy;
     for (int t = 0; t < d.steps; ++t) {
         bp.coef_q[t] = pg_coef_q(d, t);

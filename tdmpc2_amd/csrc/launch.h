@@ -4,6 +4,7 @@
 #include "handle.h"
 #include "pixel_batch_route.h"
 #include "policy_route.h"
+#include "seed_route.h"  // at file scope before refresh_route.h (below, inside tdk) includes it for its __host__ / __device__ shim
 
 // ---- policy prior (k_policy.hip: policy_kernels.cuh, routes in policy_route.h)
 struct PolLayerDev {
@@ -53,6 +54,12 @@ struct PixbParams {
 };
 
 namespace tdk {
+
+// the refusal of a launch whose grid would not fit a dim3's x (used with LAUNCH_CHECK of handle.h)
+inline int grid_fits(uint64_t blocks, const char *what) {
+    if (blocks > 0x7fffffffull) return fail(TDMPC2_ERR_UNSUPPORTED, "%s: more than 2^31 workgroups in one launch", what);
+    return 0;
+}
 
 #include "model_params.h"  // model rollout / losses (k_model.hip, model_layered.cuh in k_layered.hip)
 

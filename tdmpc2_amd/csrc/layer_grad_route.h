@@ -15,13 +15,7 @@
 // 3.5 times more than a library GEMM's blocked sums; with the partials a long reduction stays beside one.  No reduction is split
 // between workgroups: the order of an element's sum never depends on the grid or on the other rows of the call.
 #pragma once
-#include <stdint.h>
-#ifndef __host__  // the host compiler of the test
-#define __host__
-#endif
-#ifndef __device__
-#define __device__
-#endif
+#include "seed_route.h"  // <math.h>, <stdint.h> and the __host__ / __device__ shim for the host compiler of the test
 
 enum { LG_LINEAR = 0, LG_MISH = 1, LG_SIMNORM = 2 };
 enum { LG_FWD = 0, LG_DX = 1, LG_DW = 2 };

@@ -36,16 +36,6 @@ __device__ __forceinline__ ModelLossArgs ls_loss_args(const LsDesc &d) {
     return a;
 }
 
-// max and sum of exp(x - max) of one row of logits by one wavefront (the order of model_row_stats); every lane gets both
-__device__ __forceinline__ void ls_row_max_sum(const float *rp, int lane, int num_bins, float &m, float &es) {
-    m = -INFINITY;
-    for (int j = lane; j < num_bins; j += 64) m = fmaxf(m, rp[j]);
-    m = group_max<64>(m);
-    es = 0.f;
-    for (int j = lane; j < num_bins; j += 64) es += expf(rp[j] - m);
-    es = group_sum<64>(es);
-}
-
 // launch 1 of the forward: the per-row terms
 __global__ __launch_bounds__(LS_THREADS) void k_ls_rows(const LsFwdParams p) {
     int kind;
@@ -75,7 +65,7 @@ __global__ __launch_bounds__(LS_THREADS) void k_ls_rows(const LsFwdParams p) {
     const bool q = kind == LS_K_Q;
     const float *rp = (q ? p.q_logits : p.reward_logits) + row * (uint64_t)p.d.num_bins;
     float m, es;
-    ls_row_max_sum(rp, lane, p.d.num_bins, m, es);
+    row_max_sum(rp, lane, p.d.num_bins, m, es);
     if (lane != 0) return;
     const float lse = m + logf(es);
     const float target = (q ? p.td_target : p.reward)[ls_target_of(p.d, row)];
@@ -83,22 +73,7 @@ __global__ __launch_bounds__(LS_THREADS) void k_ls_rows(const LsFwdParams p) {
     p.ws[ls_ws_index(p.d, q ? LS_Q0 : LS_REW, row)] = model_soft_ce(rp, lse, target, ls_loss_args(p.d));
 }
 
-// ls_ordered_sum of loss_grad_route.h on the workgroup's LS_THREADS threads
-__device__ __forceinline__ float ls_block_sum(const float *src, uint64_t n, float *red) {
-    float s = 0.f;
-    for (uint64_t i = threadIdx.x; i < n; i += LS_THREADS) s = s + src[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = LS_THREADS / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + w];
-        __syncthreads();
-    }
-    const float r = red[0];
-    __syncthreads();
-    return r;
-}
-
-// launch 2 of the forward: tdmpc2/tdmpc2.py:285-304 from the per-row terms.  One workgroup.
+// launch 2 of the forward: tdmpc2/tdmpc2.py:285-304 from the per-row terms.  One workgroup; block_sum is ls_ordered_sum.
 __global__ __launch_bounds__(LS_THREADS) void k_ls_tail(const LsTailParams p) {
     __shared__ float red[LS_THREADS];
     const int T = p.d.steps, Q = p.d.num_q;
@@ -107,11 +82,11 @@ __global__ __launch_bounds__(LS_THREADS) void k_ls_tail(const LsTailParams p) {
     float cons = 0.f, rew = 0.f, val = 0.f, term = 0.f;
     for (int t = 0; t < T; ++t) {
         const uint64_t r0 = (uint64_t)t * B;
-        const float c_t = ls_block_sum(p.ws + ls_ws_index(p.d, LS_CONS, r0), B, red) / (fB * (float)p.d.latent_dim);
-        const float r_t = ls_block_sum(p.ws + ls_ws_index(p.d, LS_REW, r0), B, red) / fB;
+        const float c_t = block_sum(p.ws + ls_ws_index(p.d, LS_CONS, r0), B, red) / (fB * (float)p.d.latent_dim);
+        const float r_t = block_sum(p.ws + ls_ws_index(p.d, LS_REW, r0), B, red) / fB;
         float v_t = 0.f;
-        for (int i = 0; i < Q; ++i) v_t += ls_block_sum(p.ws + ls_ws_index(p.d, LS_Q0 + i, r0), B, red) / fB;
-        const float e_t = p.d.episodic ? ls_block_sum(p.ws + ls_ws_index(p.d, LS_TERM, r0), B, red) / fB : 0.f;
+        for (int i = 0; i < Q; ++i) v_t += block_sum(p.ws + ls_ws_index(p.d, LS_Q0 + i, r0), B, red) / fB;
+        const float e_t = p.d.episodic ? block_sum(p.ws + ls_ws_index(p.d, LS_TERM, r0), B, red) / fB : 0.f;
         cons += c_t * p.rho_pow[t];
         rew += r_t * p.rho_pow[t];
         val += v_t * p.rho_pow[t];
@@ -169,7 +144,7 @@ __global__ __launch_bounds__(LS_THREADS) void k_ls_bwd(const LsBwdParams p) {
     const float *rp = (q ? p.q_logits : p.reward_logits) + row * (uint64_t)NB;
     float *out = (q ? p.d_q_logits : p.d_reward_logits) + row * (uint64_t)NB;
     float m, es;
-    ls_row_max_sum(rp, lane, NB, m, es);
+    row_max_sum(rp, lane, NB, m, es);
     // the two-hot row of math.py:58-71, as model_soft_ce picks it: weights 1 - off at i0 and off at i1
     const float target = (q ? p.td_target : p.reward)[ls_target_of(p.d, row)];
     const float s = symlog_f(target);

@@ -28,16 +28,9 @@
 // Seeds.  Per step, computed in fp64 from the widened fp32 hyperparameters and rounded once (ls_coef); the kernel multiplies the
 // one fp32 factor g = *grad_total in front: c = g * coef.
 #pragma once
-#include <math.h>
-#include <stdint.h>
-#ifndef __host__  // the host compiler of the test
-#define __host__
-#endif
-#ifndef __device__
-#define __device__
-#endif
+#include "seed_route.h"
 
-enum { LS_THREADS = 256, LS_WAVES = 4, LS_ROWS = 4, LS_ELEMS = 1024, LS_MAXT = 8 };
+enum { LS_THREADS = SEED_THREADS, LS_WAVES = 4, LS_ROWS = 4, LS_ELEMS = 1024, LS_MAXT = 8 };
 enum { LS_CONS = 0, LS_REW = 1, LS_TERM = 2, LS_Q0 = 3 };                     // workspace slots
 enum { LS_K_CONS = 0, LS_K_REW = 1, LS_K_Q = 2, LS_K_TERM = 3, LS_KINDS = 4 };  // kinds of work, in grid order
 enum { LS_WANT_Z = 1, LS_WANT_REW = 2, LS_WANT_Q = 4, LS_WANT_TERM = 8 };       // backward outputs that are not NULL
@@ -58,7 +51,7 @@ __host__ __device__ inline int ls_check(const LsDesc &d) {
 }
 
 // ---- sizes
-__host__ __device__ inline uint64_t ls_tb(const LsDesc &d) { return (uint64_t)d.steps * (uint64_t)d.batch; }
+__host__ __device__ inline uint64_t ls_tb(const LsDesc &d) { return seed_tb(d); }
 __host__ __device__ inline uint64_t ls_ws_floats(const LsDesc &d) { return (uint64_t)(LS_Q0 + d.num_q) * ls_tb(d); }
 __host__ __device__ inline uint64_t ls_ws_bytes(const LsDesc &d) { return ls_ws_floats(d) * sizeof(float); }
 __host__ __device__ inline uint64_t ls_ws_index(const LsDesc &d, int slot, uint64_t row) { return (uint64_t)slot * ls_tb(d) + row; }
@@ -78,33 +71,19 @@ __host__ __device__ inline uint64_t ls_units_per_block(int kind, bool backward) 
 }
 
 // ---- grids
-struct LsGrid {
-    uint64_t first[LS_KINDS + 1];  // first workgroup of each kind; first[LS_KINDS] = workgroups of the launch
-};
+using LsGrid = SeedGrid<LS_KINDS>;
 // forward: every kind (want ignored); backward: the kinds in `want` (LS_WANT_*)
 __host__ __device__ inline LsGrid ls_grid(const LsDesc &d, bool backward, int want) {
-    LsGrid g{};
-    uint64_t at = 0;
-    for (int k = 0; k < LS_KINDS; ++k) {
-        g.first[k] = at;
-        if (backward && !((want >> k) & 1)) continue;
-        const uint64_t per = ls_units_per_block(k, backward);
-        at += (ls_units(d, k, backward) + (per - 1)) / per;
-    }
-    g.first[LS_KINDS] = at;
-    return g;
+    return seed_grid<LS_KINDS>(backward ? want : ~0, [&](int k) { return ls_units(d, k, backward); },
+                               [&](int k) { return ls_units_per_block(k, backward); });
 }
-// workgroup `block` (< first[LS_KINDS]) -> its kind and its index inside the kind
 __host__ __device__ inline void ls_decode(const LsGrid &g, uint64_t block, int &kind, uint64_t &local) {
-    kind = 0;
-    for (int k = 1; k < LS_KINDS; ++k)
-        if (block >= g.first[k]) kind = k;
-    local = block - g.first[kind];
+    seed_decode(g, block, kind, local);
 }
 // the step of a row (LS_K_REW, LS_K_Q, forward LS_K_CONS) or element (LS_K_TERM, backward LS_K_CONS: of d_z_pred)
 __host__ __device__ inline int ls_step_of(const LsDesc &d, int kind, bool backward, uint64_t unit) {
     if (kind == LS_K_CONS && backward) return (int)(unit / ((uint64_t)d.batch * (uint64_t)d.latent_dim));
-    return (int)((unit / (uint64_t)d.batch) % (uint64_t)d.steps);
+    return seed_step_of(d, unit);
 }
 // the element of reward / td_target / terminated a row reads
 __host__ __device__ inline uint64_t ls_target_of(const LsDesc &d, uint64_t row) { return row % ls_tb(d); }
@@ -117,7 +96,7 @@ __host__ __device__ inline uint64_t ls_row(uint64_t local, int thread) { return 
 __host__ __device__ inline uint64_t ls_term_elem(uint64_t local, int thread) { return local * LS_THREADS + (uint64_t)thread; }
 
 // ---- constants of a call
-__host__ inline float ls_rho_pow(const LsDesc &d, int t) { return (float)pow((double)d.rho, (double)t); }
+__host__ inline float ls_rho_pow(const LsDesc &d, int t) { return seed_rho_pow(d, t); }
 // the per-step factor of a kind's seeds without g
 __host__ inline float ls_coef(const LsDesc &d, int kind, int t) {
     const double w = pow((double)d.rho, (double)t), T = d.steps, B = d.batch;
@@ -130,14 +109,4 @@ __host__ inline float ls_coef(const LsDesc &d, int kind, int t) {
 }
 
 // ---- the order of the step sums, restated serially (the kernel runs the same additions on LS_THREADS threads)
-__host__ inline float ls_ordered_sum(const float *src, uint64_t n) {
-    float red[LS_THREADS];
-    for (int i = 0; i < LS_THREADS; ++i) {
-        float s = 0.0f;
-        for (uint64_t k = (uint64_t)i; k < n; k += LS_THREADS) s = s + src[k];
-        red[i] = s;
-    }
-    for (int w = LS_THREADS / 2; w > 0; w >>= 1)
-        for (int i = 0; i < w; ++i) red[i] = red[i] + red[i + w];
-    return red[0];
-}
+__host__ inline float ls_ordered_sum(const float *src, uint64_t n) { return seed_ordered_sum(src, n); }

@@ -58,6 +58,37 @@ __device__ __forceinline__ float model_soft_ce(const float *rp, float lse, float
 // binary_cross_entropy_with_logits of one element, the stable form: max(x, 0) - x y + log(1 + exp(-|x|))
 __device__ __forceinline__ float model_bce(float x, float y) { return fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x))); }
 
+// ---- shared by the seed units (k_loss_grad.hip, k_pi_grad.hip)
+// max and sum of exp(x - max) of one row of logits by one wavefront (the order of model_row_stats); every lane gets both
+__device__ __forceinline__ float row_max(const float *rp, int lane, int num_bins) {
+    float m = -INFINITY;
+    for (int j = lane; j < num_bins; j += 64) m = fmaxf(m, rp[j]);
+    return group_max<64>(m);
+}
+__device__ __forceinline__ void row_max_sum(const float *rp, int lane, int num_bins, float &m, float &es) {
+    m = row_max(rp, lane, num_bins);
+    es = 0.f;
+    for (int j = lane; j < num_bins; j += 64) es += expf(rp[j] - m);
+    es = group_sum<64>(es);
+}
+// seed_ordered_sum of seed_route.h on a workgroup of 256 threads: block_tree takes each thread's partial, block_sum forms it from src
+__device__ __forceinline__ float block_tree(float s, float *red) {
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + w];
+        __syncthreads();
+    }
+    const float r = red[0];
+    __syncthreads();
+    return r;
+}
+__device__ __forceinline__ float block_sum(const float *src, uint64_t n, float *red) {
+    float s = 0.f;
+    for (uint64_t i = threadIdx.x; i < n; i += 256) s = s + src[i];
+    return block_tree(s, red);
+}
+
 // ---------------------------------------------------------------- generic kernels (instantiated by k_model.hip's generic unit)
 #ifdef MODEL_GENERIC_KERNELS
 // one wavefront per row

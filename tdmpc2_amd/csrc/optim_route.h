@@ -21,13 +21,7 @@
 // opt_norm_depth counts the longest chain of additions an element's square passes through (D of the a-priori bound: every term is
 // non-negative, so |norm - norm64| <= (D + 2) 2^-24 norm64 -- D + 1 roundings on the sum of squares, halved by the root, one for it).
 #pragma once
-#include <stdint.h>
-#ifndef __host__  // the host compiler of the test
-#define __host__
-#endif
-#ifndef __device__
-#define __device__
-#endif
+#include "seed_route.h"  // <math.h>, <stdint.h> and the __host__ / __device__ shim for the host compiler of the test
 
 enum { OPT_THREADS = 256, OPT_WAVES = 4 };
 enum { OPT_QUAD = 4 };                                           // floats per 16-byte access

@@ -159,24 +159,7 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_value(const PgValueParams p) 
 }
 
 // ---------------------------------------------------------------- the loss
-// pg_step_sum / pg_ordered_sum of pi_grad_route.h on the workgroup's PG_THREADS threads
-__device__ __forceinline__ float pg_block_tree(float s, float *red) {
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = PG_THREADS / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + w];
-        __syncthreads();
-    }
-    const float r = red[0];
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ float pg_block_sum(const float *src, uint64_t n, float *red) {
-    float s = 0.f;
-    for (uint64_t i = threadIdx.x; i < n; i += PG_THREADS) s = s + src[i];
-    return pg_block_tree(s, red);
-}
-
+// pg_step_sum / pg_ordered_sum of pi_grad_route.h on the workgroup's PG_THREADS threads: block_tree / block_sum of model_rows.cuh
 __global__ __launch_bounds__(PG_THREADS) void k_pg_loss(const PgLossParams p) {
     __shared__ float red[PG_THREADS];
     const uint64_t B = (uint64_t)p.d.batch;
@@ -186,12 +169,12 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_loss(const PgLossParams p) {
         const float *q = p.q + (uint64_t)t * B, *se = p.se + (uint64_t)t * B;
         float s = 0.f;
         for (uint64_t i = threadIdx.x; i < B; i += PG_THREADS) s = s + pg_term(q[i], se[i], p.d.entropy_coef, scale);
-        const float m = pg_block_tree(s, red) / (float)p.d.batch;
+        const float m = block_tree(s, red) / (float)p.d.batch;
         loss = pg_loss_step(loss, m, p.rho_pow[t]);
         if (p.step_means && threadIdx.x == 0) p.step_means[t] = m;
     }
-    const float ent = pg_block_sum(p.entropy, pg_tb(p.d), red);
-    const float sent = pg_block_sum(p.se, pg_tb(p.d), red);
+    const float ent = block_sum(p.entropy, pg_tb(p.d), red);
+    const float sent = block_sum(p.se, pg_tb(p.d), red);
     if (threadIdx.x != 0) return;
     const float rows = (float)p.d.steps * (float)p.d.batch;
     p.losses[0] = loss / (float)p.d.steps;
@@ -217,9 +200,7 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_loss_bwd(const PgBwdParams p)
     if (row >= pg_units(p.d, PG_K_Q)) return;
     const float *rp = p.q_logits + row * (uint64_t)NB;
     float *out = p.d_q_logits + row * (uint64_t)NB;
-    float m = -INFINITY;
-    for (int j = lane; j < NB; j += 64) m = fmaxf(m, rp[j]);
-    m = group_max<64>(m);
+    const float m = row_max(rp, lane, NB);
     // The sums of exp and of exp * bin in fp64, rounded once into x: symexp'(x) = exp|x| turns an ulp of x (1e-6 at |x| = 8) into a
     // relative error of the whole row's seeds, and the fp32 sums of model_row_stats are good to about an ulp -- restated on the
     // CPU in that order against the fixture: 1.2e-6 of the tensor's maximum where the gate of tests/test_gpu_pi_grad.py is 1.3e-6.

@@ -24,16 +24,9 @@
 // Seeds.  Per step, computed in fp64 from the widened fp32 hyperparameters and rounded once (pg_coef_q, pg_coef_se, both negative);
 // the kernel multiplies the one fp32 factor g = *grad_total in front: c = g * coef.
 #pragma once
-#include <math.h>
-#include <stdint.h>
-#ifndef __host__  // the host compiler of the test
-#define __host__
-#endif
-#ifndef __device__
-#define __device__
-#endif
+#include "seed_route.h"
 
-enum { PG_THREADS = 256, PG_ROWS = 4, PG_HEAD_LANES = 8, PG_HEAD_ROWS = 32, PG_MAXT = 16, PG_MAXA = 64, PG_MAXBINS = 4096 };
+enum { PG_THREADS = SEED_THREADS, PG_ROWS = 4, PG_HEAD_LANES = 8, PG_HEAD_ROWS = 32, PG_MAXT = 16, PG_MAXA = 64, PG_MAXBINS = 4096 };
 enum { PG_K_Q = 0, PG_K_SE = 1, PG_KINDS = 2 };  // kinds of work of loss_backward, in grid order
 enum { PG_WANT_Q = 1, PG_WANT_SE = 2 };          // its outputs that are not NULL
 
@@ -53,7 +46,7 @@ __host__ __device__ inline int pg_check(const PgDesc &d) {
 }
 
 // ---- sizes and grids
-__host__ __device__ inline uint64_t pg_tb(const PgDesc &d) { return (uint64_t)d.steps * (uint64_t)d.batch; }
+__host__ __device__ inline uint64_t pg_tb(const PgDesc &d) { return seed_tb(d); }
 __host__ __device__ inline uint64_t pg_head_grid(const PgDesc &d) { return (pg_tb(d) + (PG_HEAD_ROWS - 1)) / PG_HEAD_ROWS; }
 __host__ __device__ inline uint64_t pg_value_grid(const PgDesc &d) { return (pg_tb(d) + (PG_ROWS - 1)) / PG_ROWS; }
 // the row of a thread of the head kernels and its first column; both may lie past the rows / the row's A
@@ -68,31 +61,15 @@ __host__ __device__ inline uint64_t pg_se_elem(uint64_t local, int thread) { ret
 
 __host__ __device__ inline uint64_t pg_units(const PgDesc &d, int kind) { return kind == PG_K_Q ? 2 * pg_tb(d) : pg_tb(d); }
 __host__ __device__ inline uint64_t pg_units_per_block(int kind) { return kind == PG_K_Q ? PG_ROWS : PG_THREADS; }
-struct PgGrid {
-    uint64_t first[PG_KINDS + 1];  // first workgroup of each kind; first[PG_KINDS] = workgroups of the launch
-};
+using PgGrid = SeedGrid<PG_KINDS>;
 __host__ __device__ inline PgGrid pg_bwd_grid(const PgDesc &d, int want) {
-    PgGrid g{};
-    uint64_t at = 0;
-    for (int k = 0; k < PG_KINDS; ++k) {
-        g.first[k] = at;
-        if (!((want >> k) & 1)) continue;
-        const uint64_t per = pg_units_per_block(k);
-        at += (pg_units(d, k) + (per - 1)) / per;
-    }
-    g.first[PG_KINDS] = at;
-    return g;
+    return seed_grid<PG_KINDS>(want, [&](int k) { return pg_units(d, k); }, [](int k) { return pg_units_per_block(k); });
 }
 __host__ __device__ inline void pg_decode(const PgGrid &g, uint64_t block, int &kind, uint64_t &local) {
-    kind = 0;
-    for (int k = 1; k < PG_KINDS; ++k)
-        if (block >= g.first[k]) kind = k;
-    local = block - g.first[kind];
+    seed_decode(g, block, kind, local);
 }
 // the step of a row of PG_K_Q or an element of PG_K_SE
-__host__ __device__ inline int pg_step_of(const PgDesc &d, uint64_t unit) {
-    return (int)((unit / (uint64_t)d.batch) % (uint64_t)d.steps);
-}
+__host__ __device__ inline int pg_step_of(const PgDesc &d, uint64_t unit) { return seed_step_of(d, unit); }
 
 // ---- bin k of torch.linspace(vmin, vmax, num_bins) in fp32, as the planner's handle forms its table (tdmpc2_plan.hip): the float
 // step, the product and the sum in fp64, rounded once; the upper half counted down from vmax
@@ -103,7 +80,7 @@ __host__ __device__ inline float pg_bin(const PgDesc &d, int k) {
 }
 
 // ---- constants of a call
-__host__ inline float pg_rho_pow(const PgDesc &d, int t) { return (float)pow((double)d.rho, (double)t); }
+__host__ inline float pg_rho_pow(const PgDesc &d, int t) { return seed_rho_pow(d, t); }
 // the per-step factors of the seeds without g
 __host__ inline float pg_coef_q(const PgDesc &d, int t) {
     return (float)(-pow((double)d.rho, (double)t) / (2.0 * (double)d.steps * (double)d.batch));
@@ -132,27 +109,9 @@ __host__ __device__ inline float pg_loss_step(float loss, float m, float w) {
 }
 
 // ---- the order of the sums, restated serially (the kernel runs the same additions on PG_THREADS threads)
-__host__ inline float pg_ordered_sum(const float *src, uint64_t n) {
-    float red[PG_THREADS];
-    for (int i = 0; i < PG_THREADS; ++i) {
-        float s = 0.0f;
-        for (uint64_t k = (uint64_t)i; k < n; k += PG_THREADS) s = s + src[k];
-        red[i] = s;
-    }
-    for (int w = PG_THREADS / 2; w > 0; w >>= 1)
-        for (int i = 0; i < w; ++i) red[i] = red[i] + red[i + w];
-    return red[0];
-}
+__host__ inline float pg_ordered_sum(const float *src, uint64_t n) { return seed_ordered_sum(src, n); }
 __host__ inline float pg_step_sum(const float *q, const float *se, uint64_t n, float entropy_coef, float scale) {
-    float red[PG_THREADS];
-    for (int i = 0; i < PG_THREADS; ++i) {
-        float s = 0.0f;
-        for (uint64_t k = (uint64_t)i; k < n; k += PG_THREADS) s = s + pg_term(q[k], se[k], entropy_coef, scale);
-        red[i] = s;
-    }
-    for (int w = PG_THREADS / 2; w > 0; w >>= 1)
-        for (int i = 0; i < w; ++i) red[i] = red[i] + red[i + w];
-    return red[0];
+    return seed_ordered_sum(n, [=](uint64_t k) { return pg_term(q[k], se[k], entropy_coef, scale); });
 }
 // losses [3] and step_means [T] (or null) of tdmpc2_pigrad_loss_forward, serially
 __host__ inline void pg_loss_serial(const PgDesc &d, const float *q, const float *entropy, const float *se, float scale, float *losses,

@@ -13,12 +13,7 @@
 //              prior's fp32 copy
 // The dependency max -> scale -> pack crosses launch boundaries: no workgroup waits for another, no float atomics.
 #pragma once
-#ifndef __host__  // the host compiler of the test
-#define __host__
-#endif
-#ifndef __device__
-#define __device__
-#endif
+#include "seed_route.h"  // <math.h>, <stdint.h> and the __host__ / __device__ shim for the host compiler of the test
 
 enum { RO_RESET = 0, RO_SCAN = 1, RO_SCALES = 2, RO_PACK = 3, REFRESH_MAX_OPS = 4 };
 enum { RF_NETS = 6, RF_MAX_ENC = 6, RF_THREADS = 256 };

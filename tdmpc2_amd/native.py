@@ -19,36 +19,6 @@ _lib = None
 
 ABI_VERSION = 14
 
-# every symbol include/tdmpc2_plan.h declares (tests check the .so exports all of them)
-ABI_SYMBOLS = [
-    "tdmpc2_plan_abi_version", "tdmpc2_last_error", "tdmpc2_plan_create", "tdmpc2_plan_destroy",
-    "tdmpc2_plan_device_bytes", "tdmpc2_plan_path", "tdmpc2_plan_precision", "tdmpc2_plan_bind_weights", "tdmpc2_plan_run", "tdmpc2_plan_estimate_value",
-    "tdmpc2_plan_estimate_value_trace", "tdmpc2_plan_refit", "tdmpc2_plan_set_tuning", "tdmpc2_plan_set_profiling",
-    "tdmpc2_plan_profile_read", "tdmpc2_plan_bind_encoder", "tdmpc2_plan_encode", "tdmpc2_plan_run_obs",
-    "tdmpc2_plan_policy_value", "tdmpc2_plan_td_target", "tdmpc2_plan_policy_value_mt", "tdmpc2_plan_td_target_mt",
-    "tdmpc2_plan_packed_size", "tdmpc2_plan_export_packed", "tdmpc2_plan_import_packed",
-    "tdmpc2_plan_shard_begin", "tdmpc2_plan_shard_values", "tdmpc2_plan_shard_refit",
-    "tdmpc2_plan_export_noise", "tdmpc2_plan_call_counter", "tdmpc2_plan_set_call_counter", "tdmpc2_plan_take_fault",
-    "tdmpc2_plan_fault_info", "tdmpc2_plan_fault_word",
-    "tdmpc2_plan_bind_pixel_encoder", "tdmpc2_plan_encode_pix", "tdmpc2_plan_run_pix",
-    "tdmpc2_plan_bind_policy", "tdmpc2_plan_pi", "tdmpc2_plan_act_pi", "tdmpc2_plan_act_pi_pix",
-    "tdmpc2_plan_model_rollout", "tdmpc2_plan_model_rollout_mt", "tdmpc2_plan_model_losses", "tdmpc2_plan_model_losses_mt",
-    "tdmpc2_plan_policy_loss", "tdmpc2_plan_policy_loss_mt", "tdmpc2_plan_running_scale", "tdmpc2_plan_termination_stats",
-    "tdmpc2_plan_refresh_weights", "tdmpc2_plan_soft_update_target",
-    "tdmpc2_plan_pix_batch_reserve", "tdmpc2_plan_encode_pix_batch",
-    "tdmpc2_buffer_create", "tdmpc2_buffer_destroy", "tdmpc2_buffer_add", "tdmpc2_buffer_load", "tdmpc2_buffer_sample",
-    "tdmpc2_buffer_stats", "tdmpc2_buffer_set_call_counter",
-    "tdmpc2_layer_workspace_bytes", "tdmpc2_layer_forward", "tdmpc2_layer_backward",
-    "tdmpc2_optim_layout", "tdmpc2_optim_create", "tdmpc2_optim_destroy", "tdmpc2_optim_step", "tdmpc2_optim_get_step",
-    "tdmpc2_optim_set_step",
-    "tdmpc2_loss_workspace_bytes", "tdmpc2_loss_forward", "tdmpc2_loss_backward",
-]
-# include/tdmpc2_pi_grad.h: the policy-loss unit, a header of its own beside ABI 14 (whose version and symbols stay as they are)
-PI_GRAD_SYMBOLS = ("tdmpc2_pigrad_head_forward", "tdmpc2_pigrad_head_backward", "tdmpc2_pigrad_value_forward",
-                   "tdmpc2_pigrad_loss_forward", "tdmpc2_pigrad_loss_backward")
-# include/tdmpc2_dropout.h: the dropout-mask unit, again a header of its own beside ABI 14
-DROPOUT_SYMBOLS = ("tdmpc2_dropout_mask",)
-
 NET_DYNAMICS, NET_REWARD, NET_PI, NET_Q, NET_TERMINATION, NET_TARGET_Q = range(6)
 PATH_AUTO, PATH_FUSED, PATH_LAYERED = range(3)  # enum tdmpc2_path
 PREC_AUTO, PREC_FP32, PREC_SPLIT_F16 = range(3)  # enum tdmpc2_precision
@@ -189,6 +159,102 @@ class Debug(C.Structure):
                 ("std", C.c_void_p), ("actions", C.c_void_p)]
 
 
+# The prototypes, one ordered table per header: name -> argtypes (restype int), or (argtypes, restype) where it is not int.
+# _open declares them all; tests/test_abi_prototypes.py counts each entry against its declaration.
+_P, _vp, _i32, _u32, _u64, _f32, _sz = C.POINTER, C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_float, C.c_size_t
+_bind = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]
+_PLAN_H = {  # include/tdmpc2_plan.h
+    "tdmpc2_plan_abi_version": [],
+    "tdmpc2_last_error": ([], C.c_char_p),
+    "tdmpc2_plan_create": [_P(PlanCfg), _P(_vp)],
+    "tdmpc2_plan_destroy": ([_vp], None),
+    "tdmpc2_plan_device_bytes": ([_vp], _u64),
+    "tdmpc2_plan_path": [_vp],
+    "tdmpc2_plan_precision": [_vp],
+    "tdmpc2_plan_bind_weights": _bind,
+    "tdmpc2_plan_run": [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _P(Noise), _u64, _vp, _P(Debug), _vp],
+    "tdmpc2_plan_estimate_value": [_vp, _i32] + [_vp] * 9,
+    "tdmpc2_plan_estimate_value_trace": [_vp, _i32] + [_vp] * 11,
+    "tdmpc2_plan_refit": [_vp, _i32] + [_vp] * 8,
+    "tdmpc2_plan_set_tuning": [_vp, _i32, _i32],
+    "tdmpc2_plan_set_profiling": [_vp, _i32],
+    "tdmpc2_plan_profile_read": [_vp, _P(_f32), _P(_i32)],
+    "tdmpc2_plan_bind_encoder": _bind,
+    "tdmpc2_plan_encode": [_vp, _i32, _vp, _i32, _vp, _vp, _vp],
+    "tdmpc2_plan_run_obs": [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _P(Noise), _u64, _vp, _vp],
+    "tdmpc2_plan_policy_value": [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _u64, _vp, _vp, _vp],
+    "tdmpc2_plan_td_target": [_vp, _i32, _vp, _vp, _vp, _f32, _vp, _vp, _u64, _vp, _vp],
+    "tdmpc2_plan_policy_value_mt": [_vp, _i32, _vp, _P(TaskTables), _i32, _i32, _vp, _vp, _u64, _vp, _vp, _vp],
+    "tdmpc2_plan_td_target_mt": [_vp, _i32, _vp, _vp, _vp, _f32, _P(TaskTables), _vp, _vp, _u64, _vp, _vp],
+    "tdmpc2_plan_packed_size": [_vp, _P(_u64)],
+    "tdmpc2_plan_export_packed": [_vp, _vp, _u64, _vp],
+    "tdmpc2_plan_import_packed": [_vp, _vp, _u64, _vp],
+    "tdmpc2_plan_shard_begin": [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _P(Noise), _u64, _vp],
+    "tdmpc2_plan_shard_values": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _P(Noise), _u64, _vp, _vp],
+    "tdmpc2_plan_shard_refit": [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _P(Noise), _u64, _vp, _P(Debug), _vp],
+    "tdmpc2_plan_export_noise": [_vp, _i32, _i32, _u64, _u32, _P(Noise), _vp],
+    "tdmpc2_plan_call_counter": [_vp, _P(_u32)],
+    "tdmpc2_plan_set_call_counter": [_vp, _u32],
+    "tdmpc2_plan_take_fault": [_vp, _P(_i32)],
+    "tdmpc2_plan_fault_info": [_vp, _P(FaultInfo)],
+    "tdmpc2_plan_fault_word": [_vp, _vp, _vp],
+    "tdmpc2_plan_bind_pixel_encoder": [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp],
+    "tdmpc2_plan_encode_pix": [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp],
+    "tdmpc2_plan_run_pix": [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _P(Noise), _u64, _vp, _vp],
+    "tdmpc2_plan_bind_policy": [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp],
+    "tdmpc2_plan_pi": [_vp, _i32, _vp, _vp, _vp, _vp, _u64, _P(PolicyOut), _vp],
+    "tdmpc2_plan_act_pi": [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _u64, _P(PolicyOut), _vp],
+    "tdmpc2_plan_act_pi_pix": [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _u64, _P(PolicyOut), _vp],
+    "tdmpc2_plan_model_rollout": [_vp, _i32, _i32, _vp, _vp, _i32, _P(ModelOut), _vp],
+    "tdmpc2_plan_model_rollout_mt": [_vp, _i32, _i32, _vp, _vp, _P(TaskTables), _i32, _P(ModelOut), _vp],
+    "tdmpc2_plan_model_losses": [_vp, _i32, _i32, _vp, _vp, _i32, _P(ModelTargets), _P(ModelOut), _vp, _vp, _vp],
+    "tdmpc2_plan_model_losses_mt": [_vp, _i32, _i32, _vp, _vp, _P(TaskTables), _i32, _P(ModelTargets), _P(ModelOut), _vp, _vp, _vp],
+    "tdmpc2_plan_policy_loss": [_vp, _i32, _i32, _vp, _vp, _vp, _u64, _P(PolicyLossIn), _vp, _P(PolicyLossOut), _vp, _vp],
+    "tdmpc2_plan_policy_loss_mt": [_vp, _i32, _i32, _vp, _P(TaskTables), _vp, _vp, _u64, _P(PolicyLossIn), _vp, _P(PolicyLossOut), _vp,
+                                   _vp],
+    "tdmpc2_plan_running_scale": [_vp, _i32, _vp, _f32, _vp, _vp, _vp],
+    "tdmpc2_plan_termination_stats": [_vp, _i32, _vp, _vp, _vp, _vp],
+    "tdmpc2_plan_refresh_weights": [_vp, _P(WeightTable), _vp],
+    "tdmpc2_plan_soft_update_target": [_vp, _P(WeightTable), _P(_vp * 4), _f32, _vp],
+    "tdmpc2_plan_pix_batch_reserve": [_vp, _i32, _vp],
+    "tdmpc2_plan_encode_pix_batch": [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp],
+    "tdmpc2_buffer_create": [_P(BufferCfg), _P(_vp)],
+    "tdmpc2_buffer_destroy": ([_vp], None),
+    "tdmpc2_buffer_add": [_vp, _u32, _P(_vp), _vp],
+    "tdmpc2_buffer_load": [_vp, _u64, _u32, _P(_vp), _vp],
+    "tdmpc2_buffer_sample": [_vp, _i32, _P(_vp), _vp, _u64, _vp],
+    "tdmpc2_buffer_stats": [_vp, _P(BufferInfo), _vp],
+    "tdmpc2_buffer_set_call_counter": [_vp, _u32, _vp],
+    "tdmpc2_layer_workspace_bytes": [_P(LayerDesc), _P(_sz)],
+    "tdmpc2_layer_forward": [_P(LayerDesc)] + [_vp] * 10,
+    "tdmpc2_layer_backward": [_P(LayerDesc)] + [_vp] * 14 + [_sz, _vp],
+    "tdmpc2_optim_layout": [_P(OptimCfg), _P(C.c_int64), _P(C.c_int64)],
+    "tdmpc2_optim_create": [_P(OptimCfg), _P(_vp)],
+    "tdmpc2_optim_destroy": ([_vp], None),
+    "tdmpc2_optim_step": [_vp, _vp, _vp, _vp, _i32, _vp, _vp],
+    "tdmpc2_optim_get_step": [_vp, _P(C.c_int64), _vp],
+    "tdmpc2_optim_set_step": [_vp, C.c_int64, _vp],
+    "tdmpc2_loss_workspace_bytes": [_P(LossDesc), _P(_sz)],
+    "tdmpc2_loss_forward": [_P(LossDesc)] + [_vp] * 11 + [_sz, _vp],
+    "tdmpc2_loss_backward": [_P(LossDesc)] + [_vp] * 14,
+}
+# include/tdmpc2_pi_grad.h: the policy-loss unit, a header of its own beside ABI 14 (whose version and symbols stay as they are);
+# the pointers after the descriptor, the stream included
+_PI_GRAD_H = {"tdmpc2_pigrad_" + name: [_P(PiGradDesc)] + [_vp] * nptr for name, nptr in
+              (("head_forward", 7), ("head_backward", 7), ("value_forward", 3), ("loss_forward", 7), ("loss_backward", 6))}
+# include/tdmpc2_dropout.h: the dropout-mask unit, again a header of its own beside ABI 14
+_DROPOUT_H = {"tdmpc2_dropout_mask": [_P(DropoutDesc), _vp, _vp, _vp]}
+PROTOTYPES = {"tdmpc2_plan.h": _PLAN_H, "tdmpc2_pi_grad.h": _PI_GRAD_H, "tdmpc2_dropout.h": _DROPOUT_H}  # by header under include/
+ABI_SYMBOLS = list(_PLAN_H)  # every symbol include/tdmpc2_plan.h declares (tests check the .so exports all of them)
+PI_GRAD_SYMBOLS = tuple(_PI_GRAD_H)
+DROPOUT_SYMBOLS = tuple(_DROPOUT_H)
+
+
+def signature(sig):
+    """(argtypes, restype) of a PROTOTYPES entry."""
+    return sig if isinstance(sig, tuple) else (sig, C.c_int)
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -226,155 +292,10 @@ def _open(path):
         raise NativeError(f"{path} not found: build it with tdmpc2_amd/csrc/build.sh "
                           "(or __graft_entry__.build()); there is no CPU fallback for the planner")
     lib = C.CDLL(path)
-    vp, i32, u64 = C.c_void_p, C.c_int, C.c_uint64
-    lib.tdmpc2_plan_abi_version.restype = i32
-    lib.tdmpc2_last_error.restype = C.c_char_p
-    lib.tdmpc2_plan_create.argtypes = [C.POINTER(PlanCfg), C.POINTER(vp)]
-    lib.tdmpc2_plan_create.restype = i32
-    lib.tdmpc2_plan_destroy.argtypes = [vp]
-    lib.tdmpc2_plan_destroy.restype = None
-    lib.tdmpc2_plan_device_bytes.argtypes = [vp]
-    lib.tdmpc2_plan_device_bytes.restype = u64
-    lib.tdmpc2_plan_path.argtypes = [vp]
-    lib.tdmpc2_plan_path.restype = i32
-    lib.tdmpc2_plan_precision.argtypes = [vp]
-    lib.tdmpc2_plan_precision.restype = i32
-    lib.tdmpc2_plan_bind_weights.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, i32, vp]
-    lib.tdmpc2_plan_bind_weights.restype = i32
-    lib.tdmpc2_plan_run.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, C.POINTER(Noise), u64, vp,
-                                    C.POINTER(Debug), vp]
-    lib.tdmpc2_plan_run.restype = i32
-    lib.tdmpc2_plan_bind_encoder.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, i32, vp]
-    lib.tdmpc2_plan_bind_encoder.restype = i32
-    lib.tdmpc2_plan_encode.argtypes = [vp, i32, vp, i32, vp, vp, vp]
-    lib.tdmpc2_plan_encode.restype = i32
-    lib.tdmpc2_plan_run_obs.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, C.POINTER(Noise), u64, vp, vp]
-    lib.tdmpc2_plan_run_obs.restype = i32
-    lib.tdmpc2_plan_bind_pixel_encoder.argtypes = [vp, i32, vp, vp, i32, i32, i32, vp]
-    lib.tdmpc2_plan_bind_pixel_encoder.restype = i32
-    lib.tdmpc2_plan_encode_pix.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
-    lib.tdmpc2_plan_encode_pix.restype = i32
-    lib.tdmpc2_plan_pix_batch_reserve.argtypes = [vp, i32, vp]
-    lib.tdmpc2_plan_pix_batch_reserve.restype = i32
-    lib.tdmpc2_plan_encode_pix_batch.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
-    lib.tdmpc2_plan_encode_pix_batch.restype = i32
-    lib.tdmpc2_plan_run_pix.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, C.POINTER(Noise), u64, vp, vp]
-    lib.tdmpc2_plan_run_pix.restype = i32
-    lib.tdmpc2_plan_bind_policy.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, vp]
-    lib.tdmpc2_plan_bind_policy.restype = i32
-    lib.tdmpc2_plan_pi.argtypes = [vp, i32, vp, vp, vp, vp, u64, C.POINTER(PolicyOut), vp]
-    lib.tdmpc2_plan_pi.restype = i32
-    lib.tdmpc2_plan_act_pi.argtypes = [vp, i32, vp, i32, vp, vp, vp, i32, u64, C.POINTER(PolicyOut), vp]
-    lib.tdmpc2_plan_act_pi.restype = i32
-    lib.tdmpc2_plan_act_pi_pix.argtypes = [vp, i32, vp, i32, i32, vp, vp, i32, u64, C.POINTER(PolicyOut), vp]
-    lib.tdmpc2_plan_act_pi_pix.restype = i32
-    lib.tdmpc2_plan_policy_value.argtypes = [vp, i32, vp, i32, i32, vp, vp, u64, vp, vp, vp]
-    lib.tdmpc2_plan_policy_value.restype = i32
-    lib.tdmpc2_plan_td_target.argtypes = [vp, i32, vp, vp, vp, C.c_float, vp, vp, u64, vp, vp]
-    lib.tdmpc2_plan_td_target.restype = i32
-    lib.tdmpc2_plan_policy_value_mt.argtypes = [vp, i32, vp, C.POINTER(TaskTables), i32, i32, vp, vp, u64, vp, vp, vp]
-    lib.tdmpc2_plan_policy_value_mt.restype = i32
-    lib.tdmpc2_plan_td_target_mt.argtypes = [vp, i32, vp, vp, vp, C.c_float, C.POINTER(TaskTables), vp, vp, u64, vp, vp]
-    lib.tdmpc2_plan_td_target_mt.restype = i32
-    lib.tdmpc2_plan_model_rollout_mt.argtypes = [vp, i32, i32, vp, vp, C.POINTER(TaskTables), i32, C.POINTER(ModelOut), vp]
-    lib.tdmpc2_plan_model_rollout_mt.restype = i32
-    lib.tdmpc2_plan_model_losses_mt.argtypes = [vp, i32, i32, vp, vp, C.POINTER(TaskTables), i32, C.POINTER(ModelTargets),
-                                                C.POINTER(ModelOut), vp, vp, vp]
-    lib.tdmpc2_plan_model_losses_mt.restype = i32
-    lib.tdmpc2_plan_policy_loss_mt.argtypes = [vp, i32, i32, vp, C.POINTER(TaskTables), vp, vp, u64, C.POINTER(PolicyLossIn), vp,
-                                               C.POINTER(PolicyLossOut), vp, vp]
-    lib.tdmpc2_plan_policy_loss_mt.restype = i32
-    lib.tdmpc2_plan_policy_loss.argtypes = [vp, i32, i32, vp, vp, vp, u64, C.POINTER(PolicyLossIn), vp, C.POINTER(PolicyLossOut), vp, vp]
-    lib.tdmpc2_plan_policy_loss.restype = i32
-    lib.tdmpc2_plan_running_scale.argtypes = [vp, i32, vp, C.c_float, vp, vp, vp]
-    lib.tdmpc2_plan_running_scale.restype = i32
-    lib.tdmpc2_plan_termination_stats.argtypes = [vp, i32, vp, vp, vp, vp]
-    lib.tdmpc2_plan_termination_stats.restype = i32
-    lib.tdmpc2_plan_refresh_weights.argtypes = [vp, C.POINTER(WeightTable), vp]
-    lib.tdmpc2_plan_refresh_weights.restype = i32
-    lib.tdmpc2_plan_soft_update_target.argtypes = [vp, C.POINTER(WeightTable), C.POINTER(C.c_void_p * 4), C.c_float, vp]
-    lib.tdmpc2_plan_soft_update_target.restype = i32
-    lib.tdmpc2_plan_packed_size.argtypes = [vp, C.POINTER(u64)]
-    lib.tdmpc2_plan_packed_size.restype = i32
-    lib.tdmpc2_plan_export_packed.argtypes = [vp, vp, u64, vp]
-    lib.tdmpc2_plan_export_packed.restype = i32
-    lib.tdmpc2_plan_import_packed.argtypes = [vp, vp, u64, vp]
-    lib.tdmpc2_plan_import_packed.restype = i32
-    lib.tdmpc2_plan_shard_begin.argtypes = [vp, i32, vp, vp, vp, vp, vp, C.POINTER(Noise), u64, vp]
-    lib.tdmpc2_plan_shard_begin.restype = i32
-    lib.tdmpc2_plan_shard_values.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, C.POINTER(Noise), u64, vp, vp]
-    lib.tdmpc2_plan_shard_values.restype = i32
-    lib.tdmpc2_plan_shard_refit.argtypes = [vp, i32, i32, vp, vp, vp, i32, C.POINTER(Noise), u64, vp, C.POINTER(Debug), vp]
-    lib.tdmpc2_plan_shard_refit.restype = i32
-    lib.tdmpc2_plan_estimate_value.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.tdmpc2_plan_estimate_value.restype = i32
-    lib.tdmpc2_plan_estimate_value_trace.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.tdmpc2_plan_estimate_value_trace.restype = i32
-    lib.tdmpc2_plan_refit.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.tdmpc2_plan_refit.restype = i32
-    lib.tdmpc2_plan_export_noise.argtypes = [vp, i32, i32, u64, C.c_uint32, C.POINTER(Noise), vp]
-    lib.tdmpc2_plan_export_noise.restype = i32
-    lib.tdmpc2_plan_call_counter.argtypes = [vp, C.POINTER(C.c_uint32)]
-    lib.tdmpc2_plan_call_counter.restype = i32
-    lib.tdmpc2_plan_set_call_counter.argtypes = [vp, C.c_uint32]
-    lib.tdmpc2_plan_set_call_counter.restype = i32
-    lib.tdmpc2_plan_take_fault.argtypes = [vp, C.POINTER(i32)]
-    lib.tdmpc2_plan_take_fault.restype = i32
-    lib.tdmpc2_plan_fault_word.argtypes = [vp, vp, vp]
-    lib.tdmpc2_plan_fault_word.restype = i32
-    lib.tdmpc2_plan_fault_info.argtypes = [vp, C.POINTER(FaultInfo)]
-    lib.tdmpc2_plan_fault_info.restype = i32
-    lib.tdmpc2_plan_set_tuning.argtypes = [vp, i32, i32]
-    lib.tdmpc2_plan_set_tuning.restype = i32
-    lib.tdmpc2_plan_set_profiling.argtypes = [vp, i32]
-    lib.tdmpc2_plan_set_profiling.restype = i32
-    lib.tdmpc2_plan_profile_read.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
-    lib.tdmpc2_plan_profile_read.restype = i32
-    lib.tdmpc2_buffer_create.argtypes = [C.POINTER(BufferCfg), C.POINTER(vp)]
-    lib.tdmpc2_buffer_create.restype = i32
-    lib.tdmpc2_buffer_destroy.argtypes = [vp]
-    lib.tdmpc2_buffer_destroy.restype = None
-    lib.tdmpc2_buffer_add.argtypes = [vp, C.c_uint32, C.POINTER(vp), vp]
-    lib.tdmpc2_buffer_add.restype = i32
-    lib.tdmpc2_buffer_load.argtypes = [vp, u64, C.c_uint32, C.POINTER(vp), vp]
-    lib.tdmpc2_buffer_load.restype = i32
-    lib.tdmpc2_buffer_sample.argtypes = [vp, C.c_int32, C.POINTER(vp), vp, u64, vp]
-    lib.tdmpc2_buffer_sample.restype = i32
-    lib.tdmpc2_buffer_stats.argtypes = [vp, C.POINTER(BufferInfo), vp]
-    lib.tdmpc2_buffer_stats.restype = i32
-    lib.tdmpc2_buffer_set_call_counter.argtypes = [vp, C.c_uint32, vp]
-    lib.tdmpc2_buffer_set_call_counter.restype = i32
-    lib.tdmpc2_layer_workspace_bytes.argtypes = [C.POINTER(LayerDesc), C.POINTER(C.c_size_t)]
-    lib.tdmpc2_layer_workspace_bytes.restype = i32
-    lib.tdmpc2_layer_forward.argtypes = [C.POINTER(LayerDesc)] + [vp] * 10
-    lib.tdmpc2_layer_forward.restype = i32
-    lib.tdmpc2_layer_backward.argtypes = [C.POINTER(LayerDesc)] + [vp] * 14 + [C.c_size_t, vp]
-    lib.tdmpc2_layer_backward.restype = i32
-    i64p = C.POINTER(C.c_int64)
-    lib.tdmpc2_optim_layout.argtypes = [C.POINTER(OptimCfg), i64p, i64p]
-    lib.tdmpc2_optim_layout.restype = i32
-    lib.tdmpc2_optim_create.argtypes = [C.POINTER(OptimCfg), C.POINTER(vp)]
-    lib.tdmpc2_optim_create.restype = i32
-    lib.tdmpc2_optim_destroy.argtypes = [vp]
-    lib.tdmpc2_optim_destroy.restype = None
-    lib.tdmpc2_optim_step.argtypes = [vp, vp, vp, vp, i32, vp, vp]
-    lib.tdmpc2_optim_step.restype = i32
-    lib.tdmpc2_optim_get_step.argtypes = [vp, i64p, vp]
-    lib.tdmpc2_optim_get_step.restype = i32
-    lib.tdmpc2_optim_set_step.argtypes = [vp, C.c_int64, vp]
-    lib.tdmpc2_optim_set_step.restype = i32
-    lib.tdmpc2_loss_workspace_bytes.argtypes = [C.POINTER(LossDesc), C.POINTER(C.c_size_t)]
-    lib.tdmpc2_loss_workspace_bytes.restype = i32
-    lib.tdmpc2_loss_forward.argtypes = [C.POINTER(LossDesc)] + [vp] * 11 + [C.c_size_t, vp]
-    lib.tdmpc2_loss_forward.restype = i32
-    lib.tdmpc2_loss_backward.argtypes = [C.POINTER(LossDesc)] + [vp] * 14
-    lib.tdmpc2_loss_backward.restype = i32
-    for name, nptr in zip(PI_GRAD_SYMBOLS, (7, 7, 3, 7, 6)):  # pointers after the descriptor, the stream included
-        fn = getattr(lib, name)
-        fn.argtypes = [C.POINTER(PiGradDesc)] + [vp] * nptr
-        fn.restype = i32
-    lib.tdmpc2_dropout_mask.argtypes = [C.POINTER(DropoutDesc), vp, vp, vp]
-    lib.tdmpc2_dropout_mask.restype = i32
+    for table in PROTOTYPES.values():
+        for name, sig in table.items():
+            fn = getattr(lib, name)
+            fn.argtypes, fn.restype = signature(sig)
     if lib.tdmpc2_plan_abi_version() != ABI_VERSION:
         raise NativeError(f"ABI version mismatch: library {lib.tdmpc2_plan_abi_version()}, binding {ABI_VERSION}")
     return lib
@@ -1460,51 +1381,58 @@ def layer_desc(kind: int, groups: int, rows: int, in_dim: int, out_dim: int, sha
                      shared_x=int(bool(shared_x)), simnorm_dim=int(simnorm_dim), ln_eps=float(ln_eps))
 
 
-def _layer_check(rc: int):
+_UNIT_COUNTER = dict(layer="LAYER_CALLS", loss="LOSS_CALLS", pigrad="PI_GRAD_CALLS", dropout="DROPOUT_CALLS")
+
+
+def _unit_check(tag: str, rc: int):
     if rc != 0:
-        raise NativeError(f"tdmpc2_layer error {rc}: {load_library().tdmpc2_last_error().decode()}")
+        raise NativeError(f"tdmpc2_{tag} error {rc}: {load_library().tdmpc2_last_error().decode()}")
 
 
-def layer_workspace_bytes(desc: LayerDesc) -> int:
-    n = C.c_size_t()
-    _layer_check(load_library().tdmpc2_layer_workspace_bytes(C.byref(desc), C.byref(n)))
-    return int(n.value)
-
-
-def _layer_tensors(what, device, **ts):
+def _unit_call(tag: str, symbol: str, desc, first, want, tail, **ts):
+    """The one call path of the stateless units (layer, loss, pigrad, dropout): `first` names the device; every tensor of `ts` (the
+    C order after the descriptor; None = absent, a c_void_p = a pointer its caller has checked) is contiguous fp32 on it and holds
+    what `want` (name -> element count, or None: the library sees pointers only) asks for; then the unit's counter, the call on the
+    current stream with `tail` between the tensors and the stream, and the library's error."""
+    what, device = symbol[len("tdmpc2_"):], first.device
+    if device.type != "cuda":
+        raise NativeError(f"{what} runs on an MI355X only (device {device}); there is no CPU fallback")
     for name, t in ts.items():
-        if t is None:
+        if t is None or type(t) is C.c_void_p:
             continue
         if t.device != device or t.dtype != torch.float32 or not t.is_contiguous():
             raise NativeError(f"{what}: {name} must be a contiguous fp32 tensor on {device} (got {t.dtype}, {t.device}, "
                               f"contiguous={t.is_contiguous()})")
+    for name, t in ts.items() if want else ():
+        if t is not None and t.numel() != want[name]:
+            raise NativeError(f"{what}: {name} holds {t.numel()} floats, the descriptor asks for {want[name]}")
+    globals()[_UNIT_COUNTER[tag]] += 1
+    with torch.cuda.device(device):
+        ptrs = [t if t is None or type(t) is C.c_void_p else t.data_ptr() for t in ts.values()]
+        rc = getattr(load_library(), symbol)(C.byref(desc), *ptrs, *tail, torch.cuda.current_stream(device).cuda_stream)
+    _unit_check(tag, rc)
+
+
+def _nbytes(t) -> int:
+    return 0 if t is None else t.numel() * t.element_size()
+
+
+def layer_workspace_bytes(desc: LayerDesc) -> int:
+    n = C.c_size_t()
+    _unit_check("layer", load_library().tdmpc2_layer_workspace_bytes(C.byref(desc), C.byref(n)))
+    return int(n.value)
 
 
 def layer_forward(desc: LayerDesc, x, w, b, ln_w=None, ln_b=None, mask=None, y=None, pre=None, stat=None):
     """tdmpc2_layer_forward on the current stream; tensors are contiguous fp32 on one GPU (checked), outputs are written in place."""
-    global LAYER_CALLS
-    if x.device.type != "cuda":
-        raise NativeError(f"layer_forward runs on an MI355X only (device {x.device}); there is no CPU fallback")
-    _layer_tensors("layer_forward", x.device, x=x, w=w, b=b, ln_w=ln_w, ln_b=ln_b, mask=mask, y=y, pre=pre, stat=stat)
-    LAYER_CALLS += 1
-    with torch.cuda.device(x.device):
-        _layer_check(load_library().tdmpc2_layer_forward(C.byref(desc), _ptr(x), _ptr(w), _ptr(b), _ptr(ln_w), _ptr(ln_b), _ptr(mask),
-                                                         _ptr(y), _ptr(pre), _ptr(stat), torch.cuda.current_stream(x.device).cuda_stream))
+    _unit_call("layer", "tdmpc2_layer_forward", desc, x, None, (), x=x, w=w, b=b, ln_w=ln_w, ln_b=ln_b, mask=mask, y=y, pre=pre,
+               stat=stat)
 
 
 def layer_backward(desc: LayerDesc, x, w, ln_w, ln_b, pre, stat, mask, dy, dx=None, dw=None, db=None, dln_w=None, dln_b=None, ws=None):
     """tdmpc2_layer_backward on the current stream; `ws` is a uint8 tensor of at least layer_workspace_bytes(desc) bytes."""
-    global LAYER_CALLS
-    if dy.device.type != "cuda":
-        raise NativeError(f"layer_backward runs on an MI355X only (device {dy.device}); there is no CPU fallback")
-    _layer_tensors("layer_backward", dy.device, x=x, w=w, ln_w=ln_w, ln_b=ln_b, pre=pre, stat=stat, mask=mask, dy=dy, dx=dx, dw=dw,
-                   db=db, dln_w=dln_w, dln_b=dln_b)
-    LAYER_CALLS += 1
-    with torch.cuda.device(dy.device):
-        _layer_check(load_library().tdmpc2_layer_backward(
-            C.byref(desc), _ptr(x), _ptr(w), _ptr(ln_w), _ptr(ln_b), _ptr(pre), _ptr(stat), _ptr(mask), _ptr(dy), _ptr(dx), _ptr(dw),
-            _ptr(db), _ptr(dln_w), _ptr(dln_b), _ptr(ws), 0 if ws is None else ws.numel() * ws.element_size(),
-            torch.cuda.current_stream(dy.device).cuda_stream))
+    _unit_call("layer", "tdmpc2_layer_backward", desc, dy, None, (_ptr(ws), _nbytes(ws)), x=x, w=w, ln_w=ln_w, ln_b=ln_b, pre=pre,
+               stat=stat, mask=mask, dy=dy, dx=dx, dw=dw, db=db, dln_w=dln_w, dln_b=dln_b)
 
 
 # ---------------------------------------------------------------- optimiser step (tdmpc2_optim_*)
@@ -1607,65 +1535,37 @@ def loss_desc(steps: int, batch: int, latent_dim: int, num_q: int, num_bins: int
                     termination_coef=float(termination_coef))
 
 
-def _loss_check(rc: int):
-    if rc != 0:
-        raise NativeError(f"tdmpc2_loss error {rc}: {load_library().tdmpc2_last_error().decode()}")
-
-
 def loss_workspace_bytes(desc: LossDesc) -> int:
     n = C.c_size_t()
-    _loss_check(load_library().tdmpc2_loss_workspace_bytes(C.byref(desc), C.byref(n)))
+    _unit_check("loss", load_library().tdmpc2_loss_workspace_bytes(C.byref(desc), C.byref(n)))
     return int(n.value)
 
 
-def _loss_shapes(what, desc: LossDesc, **ts):
+def _loss_want(desc: LossDesc) -> dict:
     """Element counts of the layouts of include/tdmpc2_plan.h (the library sees pointers only)."""
     T, B, L, Q, NB = desc.steps, desc.batch, desc.latent_dim, desc.num_q, desc.num_bins
-    want = dict(z_pred=T * B * L, next_z=T * B * L, reward_logits=T * B * NB, reward=T * B, q_logits=Q * T * B * NB, td_target=T * B,
+    return dict(z_pred=T * B * L, next_z=T * B * L, reward_logits=T * B * NB, reward=T * B, q_logits=Q * T * B * NB, td_target=T * B,
                 term_logit=T * B, terminated=T * B, d_z_pred=T * B * L, d_reward_logits=T * B * NB, d_q_logits=Q * T * B * NB,
                 d_term_logit=T * B, losses=5, step_means=4 * T, grad_total=1)
-    for name, t in ts.items():
-        if t is not None and t.numel() != want[name]:
-            raise NativeError(f"{what}: {name} holds {t.numel()} floats, the descriptor asks for {want[name]}")
 
 
 def loss_forward(desc: LossDesc, z_pred, next_z, reward_logits, reward, q_logits, td_target, term_logit=None, terminated=None,
                  losses=None, step_means=None, ws=None):
     """tdmpc2_loss_forward on the current stream; tensors are contiguous fp32 on one GPU (checked); `losses` [5] and `step_means`
     [4, steps] (optional) are written in place; `ws` is a uint8 tensor of at least loss_workspace_bytes(desc) bytes."""
-    global LOSS_CALLS
-    if z_pred.device.type != "cuda":
-        raise NativeError(f"loss_forward runs on an MI355X only (device {z_pred.device}); there is no CPU fallback")
-    ts = dict(z_pred=z_pred, next_z=next_z, reward_logits=reward_logits, reward=reward, q_logits=q_logits, td_target=td_target,
-              term_logit=term_logit, terminated=terminated, losses=losses, step_means=step_means)
-    _layer_tensors("loss_forward", z_pred.device, **ts)
-    _loss_shapes("loss_forward", desc, **ts)
-    LOSS_CALLS += 1
-    with torch.cuda.device(z_pred.device):
-        _loss_check(load_library().tdmpc2_loss_forward(
-            C.byref(desc), _ptr(z_pred), _ptr(next_z), _ptr(reward_logits), _ptr(reward), _ptr(q_logits), _ptr(td_target),
-            _ptr(term_logit), _ptr(terminated), _ptr(losses), _ptr(step_means), _ptr(ws),
-            0 if ws is None else ws.numel() * ws.element_size(), torch.cuda.current_stream(z_pred.device).cuda_stream))
+    _unit_call("loss", "tdmpc2_loss_forward", desc, z_pred, _loss_want(desc), (_ptr(ws), _nbytes(ws)), z_pred=z_pred, next_z=next_z,
+               reward_logits=reward_logits, reward=reward, q_logits=q_logits, td_target=td_target, term_logit=term_logit,
+               terminated=terminated, losses=losses, step_means=step_means)
 
 
 def loss_backward(desc: LossDesc, z_pred, next_z, reward_logits, reward, q_logits, td_target, term_logit=None, terminated=None,
                   grad_total=None, d_z_pred=None, d_reward_logits=None, d_q_logits=None, d_term_logit=None):
     """tdmpc2_loss_backward on the current stream; `grad_total` is a one-element fp32 tensor on the device or None (= 1); the
     outputs that are not None are overwritten."""
-    global LOSS_CALLS
-    if z_pred.device.type != "cuda":
-        raise NativeError(f"loss_backward runs on an MI355X only (device {z_pred.device}); there is no CPU fallback")
-    ts = dict(z_pred=z_pred, next_z=next_z, reward_logits=reward_logits, reward=reward, q_logits=q_logits, td_target=td_target,
-              term_logit=term_logit, terminated=terminated, grad_total=grad_total, d_z_pred=d_z_pred,
-              d_reward_logits=d_reward_logits, d_q_logits=d_q_logits, d_term_logit=d_term_logit)
-    _layer_tensors("loss_backward", z_pred.device, **ts)
-    _loss_shapes("loss_backward", desc, **ts)
-    LOSS_CALLS += 1
-    with torch.cuda.device(z_pred.device):
-        _loss_check(load_library().tdmpc2_loss_backward(
-            C.byref(desc), _ptr(z_pred), _ptr(next_z), _ptr(reward_logits), _ptr(reward), _ptr(q_logits), _ptr(td_target),
-            _ptr(term_logit), _ptr(terminated), _ptr(grad_total), _ptr(d_z_pred), _ptr(d_reward_logits), _ptr(d_q_logits),
-            _ptr(d_term_logit), torch.cuda.current_stream(z_pred.device).cuda_stream))
+    _unit_call("loss", "tdmpc2_loss_backward", desc, z_pred, _loss_want(desc), (), z_pred=z_pred, next_z=next_z,
+               reward_logits=reward_logits, reward=reward, q_logits=q_logits, td_target=td_target, term_logit=term_logit,
+               terminated=terminated, grad_total=grad_total, d_z_pred=d_z_pred, d_reward_logits=d_reward_logits, d_q_logits=d_q_logits,
+               d_term_logit=d_term_logit)
 
 
 # ---------------------------------------------------------------- policy loss seeds (tdmpc2_pigrad_*, include/tdmpc2_pi_grad.h)
@@ -1679,58 +1579,44 @@ def pigrad_desc(steps: int, batch: int, action_dim: int, num_bins: int, multitas
                       entropy_coef=float(entropy_coef), log_std_min=float(log_std_min), log_std_dif=float(log_std_dif))
 
 
-def _pigrad_call(what: str, desc: PiGradDesc, first, **ts):
-    """Device, dtype, contiguity and element counts of the layouts of include/tdmpc2_pi_grad.h (the library sees pointers only),
-    then the call on the current stream."""
-    global PI_GRAD_CALLS
-    if first.device.type != "cuda":
-        raise NativeError(f"{what} runs on an MI355X only (device {first.device}); there is no CPU fallback")
+def _pigrad_want(desc: PiGradDesc) -> dict:
+    """Element counts of the layouts of include/tdmpc2_pi_grad.h (the library sees pointers only)."""
     T, B, A, NB = desc.steps, desc.batch, desc.action_dim, desc.num_bins
-    want = dict(pi_out=T * B * 2 * A, eps=T * B * A, action_mask=B * A, action=T * B * A, entropy=T * B, scaled_entropy=T * B,
+    return dict(pi_out=T * B * 2 * A, eps=T * B * A, action_mask=B * A, action=T * B * A, entropy=T * B, scaled_entropy=T * B,
                 d_action=T * B * A, d_scaled_entropy=T * B, d_pi_out=T * B * 2 * A, q_logits=2 * T * B * NB, q=T * B, scale=1,
                 losses=3, step_means=T, grad_total=1, d_q_logits=2 * T * B * NB)
-    _layer_tensors(what, first.device, **ts)
-    for name, t in ts.items():
-        if t is not None and t.numel() != want[name]:
-            raise NativeError(f"{what}: {name} holds {t.numel()} floats, the descriptor asks for {want[name]}")
-    PI_GRAD_CALLS += 1
-    with torch.cuda.device(first.device):
-        rc = getattr(load_library(), "tdmpc2_" + what)(C.byref(desc), *[_ptr(t) for t in ts.values()],
-                                                         torch.cuda.current_stream(first.device).cuda_stream)
-    if rc != 0:
-        raise NativeError(f"tdmpc2_pigrad error {rc}: {load_library().tdmpc2_last_error().decode()}")
 
 
 def pigrad_head_forward(desc: PiGradDesc, pi_out, eps, action_mask=None, action=None, entropy=None, scaled_entropy=None):
     """tdmpc2_pigrad_head_forward: pi_out [T, B, 2A], eps [T, B, A], action_mask [B, A] (multitask) -> action [T, B, A], entropy and
     scaled_entropy [T, B], written in place."""
-    _pigrad_call("pigrad_head_forward", desc, pi_out, pi_out=pi_out, eps=eps, action_mask=action_mask, action=action, entropy=entropy,
-                 scaled_entropy=scaled_entropy)
+    _unit_call("pigrad", "tdmpc2_pigrad_head_forward", desc, pi_out, _pigrad_want(desc), (), pi_out=pi_out, eps=eps,
+               action_mask=action_mask, action=action, entropy=entropy, scaled_entropy=scaled_entropy)
 
 
 def pigrad_head_backward(desc: PiGradDesc, pi_out, eps, action_mask=None, d_action=None, d_scaled_entropy=None, d_pi_out=None):
     """tdmpc2_pigrad_head_backward: the incoming gradients (None = zero, not both) -> d_pi_out [T, B, 2A], overwritten."""
-    _pigrad_call("pigrad_head_backward", desc, pi_out, pi_out=pi_out, eps=eps, action_mask=action_mask, d_action=d_action,
-                 d_scaled_entropy=d_scaled_entropy, d_pi_out=d_pi_out)
+    _unit_call("pigrad", "tdmpc2_pigrad_head_backward", desc, pi_out, _pigrad_want(desc), (), pi_out=pi_out, eps=eps,
+               action_mask=action_mask, d_action=d_action, d_scaled_entropy=d_scaled_entropy, d_pi_out=d_pi_out)
 
 
 def pigrad_value_forward(desc: PiGradDesc, q_logits, q):
     """tdmpc2_pigrad_value_forward: q_logits [2, T, B, NB] -> q [T, B] = the average of two_hot_inv of the two heads."""
-    _pigrad_call("pigrad_value_forward", desc, q_logits, q_logits=q_logits, q=q)
+    _unit_call("pigrad", "tdmpc2_pigrad_value_forward", desc, q_logits, _pigrad_want(desc), (), q_logits=q_logits, q=q)
 
 
 def pigrad_loss_forward(desc: PiGradDesc, q, entropy, scaled_entropy, scale, losses, step_means=None):
     """tdmpc2_pigrad_loss_forward: -> losses [3] (pi_loss, mean entropy, mean scaled_entropy) and step_means [T] (optional); `scale`
     is a one-element fp32 tensor on the device (RunningScale.value)."""
-    _pigrad_call("pigrad_loss_forward", desc, q, q=q, entropy=entropy, scaled_entropy=scaled_entropy, scale=scale, losses=losses,
-                 step_means=step_means)
+    _unit_call("pigrad", "tdmpc2_pigrad_loss_forward", desc, q, _pigrad_want(desc), (), q=q, entropy=entropy,
+               scaled_entropy=scaled_entropy, scale=scale, losses=losses, step_means=step_means)
 
 
 def pigrad_loss_backward(desc: PiGradDesc, q_logits, scale, grad_total=None, d_q_logits=None, d_scaled_entropy=None):
     """tdmpc2_pigrad_loss_backward: `grad_total` is a one-element fp32 tensor on the device or None (= 1); the outputs that are not
     None are overwritten."""
-    _pigrad_call("pigrad_loss_backward", desc, q_logits, q_logits=q_logits, scale=scale, grad_total=grad_total, d_q_logits=d_q_logits,
-                 d_scaled_entropy=d_scaled_entropy)
+    _unit_call("pigrad", "tdmpc2_pigrad_loss_backward", desc, q_logits, _pigrad_want(desc), (), q_logits=q_logits, scale=scale,
+               grad_total=grad_total, d_q_logits=d_q_logits, d_scaled_entropy=d_scaled_entropy)
 
 
 # ---------------------------------------------------------------- dropout masks (tdmpc2_dropout_mask, include/tdmpc2_dropout.h)
@@ -1749,18 +1635,10 @@ def dropout_mask(desc: DropoutDesc, state, out):
     """tdmpc2_dropout_mask on the current stream: `out` (contiguous fp32 on the GPU, at least desc.n elements, 16-byte aligned) is
     overwritten with dropout's multipliers.  `state`: None (the descriptor's call counter is used) or two int32 words on the same
     device holding the counter, which the call advances by one in stream order.  No host read, no synchronisation."""
-    global DROPOUT_CALLS
-    if out.device.type != "cuda":
-        raise NativeError(f"dropout_mask runs on an MI355X only (device {out.device}); there is no CPU fallback")
-    _layer_tensors("dropout_mask", out.device, mask=out)
     if out.numel() < desc.n:
         raise NativeError(f"dropout_mask: mask holds {out.numel()} floats, the descriptor asks for {desc.n}")
     if state is not None and (state.device != out.device or state.dtype != torch.int32 or state.numel() != 2
                               or not state.is_contiguous()):
         raise NativeError(f"dropout_mask: state must be two contiguous int32 words on {out.device} (got {state.dtype}, {state.device}, "
                           f"{state.numel()} elements)")
-    DROPOUT_CALLS += 1
-    with torch.cuda.device(out.device):
-        rc = load_library().tdmpc2_dropout_mask(C.byref(desc), _ptr(state), _ptr(out), torch.cuda.current_stream(out.device).cuda_stream)
-    if rc != 0:
-        raise NativeError(f"tdmpc2_dropout error {rc}: {load_library().tdmpc2_last_error().decode()}")
+    _unit_call("dropout", "tdmpc2_dropout_mask", desc, out, None, (), state=_ptr(state), mask=out)

@@ -6,9 +6,10 @@ import collections
 import ctypes
 import math
 import os
-import subprocess
 
 import numpy as np
+
+from tests import route_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SITE_BUFFER = 8
@@ -190,30 +191,14 @@ UPDATE_KEYS = ("cursor", "floor", "head", "count", "shrink", "shrink_first", "sh
 
 
 def build_route(tmpdir):
-    src = os.path.join(str(tmpdir), "buffer_route_shim.cpp")
-    with open(src, "w") as f:
-        f.write(SHIM)
-    so = os.path.join(str(tmpdir), "libbuffer_route_shim.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-shared", "-fPIC", "-I", os.path.join(ROOT, "tdmpc2_amd", "csrc"), src, "-o", so],
-                   check=True)
-    lib = ctypes.CDLL(so)
     u32, u64, vp = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p
-    lib.ring_new.argtypes, lib.ring_new.restype = [u64, u32], vp
-    lib.ring_free.argtypes = [vp]
-    lib.ring_write.argtypes = [vp, u64, u32, ctypes.POINTER(u64)]
-    lib.ring_state.argtypes = [vp, ctypes.POINTER(u64)]
-    lib.ring_entry.argtypes = [vp, u32, ctypes.POINTER(u64)]
-    lib.pushed_entry.argtypes = [u64, u32, u64, u32, ctypes.POINTER(u64)]
-    lib.table_cap.argtypes, lib.table_cap.restype = [u64, u32], u32
-    lib.draw_episode.argtypes, lib.draw_episode.restype = [u32, u32], u32
-    lib.draw_start.argtypes, lib.draw_start.restype = [u32, u32, u32], u32
-    lib.access_width.argtypes, lib.access_width.restype = [u32, u64], u32
-    lib.field_grid.argtypes = [u32, u64, u64, ctypes.POINTER(u32)]
-    lib.decode.argtypes = [u32, u64, u64, u32, ctypes.POINTER(u64)]
-    lib.field_bases.argtypes, lib.field_bases.restype = [u64, ctypes.c_int, ctypes.POINTER(u32), ctypes.POINTER(u64)], u64
-    lib.offset.argtypes, lib.offset.restype = [u64, u64, u32], u64
-    lib.constants.argtypes = [ctypes.POINTER(u32)]
-    return lib
+    return route_shim.build_shim(tmpdir, "buffer_route", SHIM, dict(
+        ring_new=([u64, u32], vp), ring_free=[vp], ring_write=[vp, u64, u32, ctypes.POINTER(u64)], ring_state=[vp, ctypes.POINTER(u64)],
+        ring_entry=[vp, u32, ctypes.POINTER(u64)], pushed_entry=[u64, u32, u64, u32, ctypes.POINTER(u64)], table_cap=([u64, u32], u32),
+        draw_episode=([u32, u32], u32), draw_start=([u32, u32, u32], u32), access_width=([u32, u64], u32),
+        field_grid=[u32, u64, u64, ctypes.POINTER(u32)], decode=[u32, u64, u64, u32, ctypes.POINTER(u64)],
+        field_bases=([u64, ctypes.c_int, ctypes.POINTER(u32), ctypes.POINTER(u64)], u64), offset=([u64, u64, u32], u64),
+        constants=[ctypes.POINTER(u32)]), ("-O2",))
 
 
 class RouteRing:

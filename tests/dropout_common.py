@@ -8,10 +8,10 @@ Nothing here comes from a HIP result, and nothing here reads the reference tree.
 import ctypes
 import math
 import os
-import subprocess
 
 import numpy as np
 
+from tests import route_shim
 from tests.optim_common import FLOOR, MARGIN, rel_err  # noqa: F401  (the measured gate of DESIGN 3.4h)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -195,7 +195,6 @@ int main(int argc, char **argv) {
     return bad ? 1 : 0;
 }
 """
-CXX = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-ffp-contract=off", "-I", os.path.join(ROOT, "tdmpc2_amd", "csrc")]
 
 
 class Desc(ctypes.Structure):  # DropDesc = tdmpc2_dropout_desc
@@ -209,36 +208,16 @@ def desc_of(n, p, seed=0, call=0):
 
 
 def build_route(tmpdir):
-    src = os.path.join(str(tmpdir), "dropout_route_shim.cpp")
-    with open(src, "w") as f:
-        f.write(SHIM)
-    so = os.path.join(str(tmpdir), "libdropout_route_shim.so")
-    subprocess.run([*CXX, "-shared", "-fPIC", src, "-o", so], check=True)
-    lib = ctypes.CDLL(so)
     dp, u64, i32 = ctypes.POINTER(Desc), ctypes.c_uint64, ctypes.c_int32
-    lib.constants.argtypes = [ctypes.POINTER(i32)]
-    lib.check.argtypes = [dp]
-    lib.thr.argtypes, lib.thr.restype = [ctypes.c_float], ctypes.c_uint32
-    lib.keep.argtypes, lib.keep.restype = [ctypes.c_float], ctypes.c_float
-    for name in ("grid", "quad_stride", "quad_of", "bump", "cover"):
-        getattr(lib, name).argtypes, getattr(lib, name).restype = [u64], u64
-    lib.first_quad.argtypes, lib.first_quad.restype = [u64, i32], u64
-    lib.lane_of.argtypes = [u64]
-    lib.quad_elems.argtypes = [u64, u64]
-    lib.serial.argtypes, lib.serial.restype = [dp, u64, u64], ctypes.c_float
-    lib.fill.argtypes = [dp, u64, u64, u64, ctypes.POINTER(ctypes.c_float)]
-    return lib
+    return route_shim.build_shim(tmpdir, "dropout_route", SHIM, dict(
+        constants=[ctypes.POINTER(i32)], check=[dp], thr=([ctypes.c_float], ctypes.c_uint32), keep=([ctypes.c_float], ctypes.c_float),
+        first_quad=([u64, i32], u64), lane_of=[u64], quad_elems=[u64, u64], serial=([dp, u64, u64], ctypes.c_float),
+        fill=[dp, u64, u64, u64, ctypes.POINTER(ctypes.c_float)],
+        **{name: ([u64], u64) for name in ("grid", "quad_stride", "quad_of", "bump", "cover")}))
 
 
 def build_walk(tmpdir, sanitize=False):
-    """The shim and MAIN as one stand-alone program -> its path.  sanitize: built with -fsanitize=address,undefined."""
-    src = os.path.join(str(tmpdir), "dropout_route_walk.cpp")
-    with open(src, "w") as f:
-        f.write(SHIM + MAIN)
-    exe = os.path.join(str(tmpdir), "dropout_route_walk")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else []
-    subprocess.run([*CXX, *flags, src, "-o", exe], check=True)
-    return exe
+    return route_shim.build_walk(tmpdir, "dropout_route", SHIM + MAIN, sanitize)
 
 
 def walk_input(path):

@@ -9,9 +9,11 @@
 import ctypes
 import functools
 import os
-import subprocess
 
 import numpy as np
+
+from tests import route_shim
+from tests.route_shim import rel_err  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LINEAR, MISH, SIMNORM = 0, 1, 2
@@ -219,12 +221,6 @@ def torch_grads(c, dtype, device="cpu"):
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
-def rel_err(got, ref):
-    """e(T) = max |T - T64| / max |T64|."""
-    den = float(np.abs(ref).max())
-    return float(np.abs(got.astype(np.float64) - ref).max()) / (den if den > 0 else 1.0)
-
-
 @functools.lru_cache(maxsize=None)
 def measured_reference(kind, shape, style, mask):
     """Computed once per case and shared: (case, fp64 closed form, e(T) of torch's CPU fp32 autograd per tensor)."""
@@ -317,25 +313,11 @@ def desc_words(kind, G, R, K, N, shared=False, sd=0):
 
 
 def build_route(tmpdir, extra_flags=()):
-    src = os.path.join(str(tmpdir), "layer_grad_route_shim.cpp")
-    with open(src, "w") as f:
-        f.write(SHIM)
-    so = os.path.join(str(tmpdir), "liblayer_grad_route_shim.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-shared", "-fPIC", *extra_flags, "-I", os.path.join(ROOT, "tdmpc2_amd", "csrc"),
-                    src, "-o", so], check=True)
-    lib = ctypes.CDLL(so)
     i32p, u64, u64p = ctypes.POINTER(ctypes.c_int32), ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)
-    lib.check.argtypes = [i32p]
-    lib.gemm.argtypes = [ctypes.c_int, i32p, u64p]
-    lib.cover.argtypes, lib.cover.restype = [ctypes.c_int, i32p, ctypes.POINTER(ctypes.c_uint32), u64], u64
-    lib.chain.argtypes = [ctypes.c_int, i32p]
-    lib.offsets.argtypes = [ctypes.c_int, i32p, u64, u64, u64, u64, u64p]
-    lib.off3.argtypes, lib.off3.restype = [u64] * 5, u64
-    lib.ws.argtypes = [i32p, u64p]
-    lib.col_part.argtypes = [ctypes.c_int]
-    lib.grids.argtypes = [i32p, u64p]
-    lib.constants.argtypes = [i32p]
-    return lib
+    return route_shim.build_shim(tmpdir, "layer_grad_route", SHIM, dict(
+        check=[i32p], gemm=[ctypes.c_int, i32p, u64p], cover=([ctypes.c_int, i32p, ctypes.POINTER(ctypes.c_uint32), u64], u64),
+        chain=[ctypes.c_int, i32p], offsets=[ctypes.c_int, i32p, u64, u64, u64, u64, u64p], off3=([u64] * 5, u64), ws=[i32p, u64p],
+        col_part=[ctypes.c_int], grids=[i32p, u64p], constants=[i32p]), ("-O2", *extra_flags))
 
 
 def route_gemm(lib, which, words):

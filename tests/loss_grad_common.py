@@ -11,11 +11,12 @@ Hyperparameters are fp32 in the C ABI.  `hyper` returns the doubles the library 
 reference gets those, so the gates measure arithmetic and not the representation of 0.1 in fp32."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
+from tests import route_shim
 from tests.optim_common import FLOOR, MARGIN, rel_err, widen  # noqa: F401  (the measured gate of DESIGN 3.4h)
+from tests.route_shim import gate, ordered_sum_model  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "loss_seeds.npz")
@@ -259,11 +260,6 @@ def torch_ref(x, case, h, dtype, th=None):
     return out
 
 
-def gate(got, ref64, yard32):
-    """e and the bound MARGIN * max(e_torch32, FLOOR) of one tensor."""
-    return rel_err(got, ref64), MARGIN * max(rel_err(yard32, ref64), FLOOR)
-
-
 # ---------------------------------------------------------------- tdmpc2_amd/csrc/loss_grad_route.h behind a C shim
 SHIM = r"""
 #include <string.h>
@@ -387,7 +383,6 @@ int main(int argc, char **argv) {
 }
 """
 CONSTANT_KEYS = ("THREADS", "WAVES", "ROWS", "ELEMS", "MAXT", "CONS", "REW", "TERM", "Q0", "KINDS", "DESC_BYTES", "GRID_BYTES")
-CXX = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-ffp-contract=off", "-I", os.path.join(ROOT, "tdmpc2_amd", "csrc")]
 
 
 class Desc(ctypes.Structure):  # LsDesc = tdmpc2_loss_desc
@@ -404,37 +399,17 @@ def desc_of(case, h=None, **over):
 
 
 def build_route(tmpdir):
-    src = os.path.join(str(tmpdir), "loss_grad_route_shim.cpp")
-    with open(src, "w") as f:
-        f.write(SHIM)
-    so = os.path.join(str(tmpdir), "libloss_grad_route_shim.so")
-    subprocess.run([*CXX, "-shared", "-fPIC", src, "-o", so], check=True)
-    lib = ctypes.CDLL(so)
     dp, u64, i32 = ctypes.POINTER(Desc), ctypes.c_uint64, ctypes.c_int32
-    lib.constants.argtypes = [ctypes.POINTER(i32)]
-    lib.check.argtypes = [dp]
-    lib.ws_floats.argtypes, lib.ws_floats.restype = [dp], u64
-    lib.ws_index.argtypes, lib.ws_index.restype = [dp, i32, u64], u64
-    lib.grid.argtypes = [dp, i32, i32, ctypes.POINTER(u64)]
-    lib.decode.argtypes = [dp, i32, i32, u64, ctypes.POINTER(i32), ctypes.POINTER(u64)]
-    lib.unit_info.argtypes = [dp, i32, i32, u64, ctypes.POINTER(i32), ctypes.POINTER(u64)]
-    lib.coef.argtypes, lib.coef.restype = [dp, i32, i32], ctypes.c_float
-    lib.rho_pow.argtypes, lib.rho_pow.restype = [dp, i32], ctypes.c_float
-    lib.ordered_sum.argtypes, lib.ordered_sum.restype = [ctypes.POINTER(ctypes.c_float), u64], ctypes.c_float
-    lib.elem.argtypes, lib.elem.restype = [u64, i32, i32], u64
-    lib.cover.argtypes, lib.cover.restype = [dp, i32, i32], u64
-    return lib
+    return route_shim.build_shim(tmpdir, "loss_grad_route", SHIM, dict(
+        constants=[ctypes.POINTER(i32)], check=[dp], ws_floats=([dp], u64), ws_index=([dp, i32, u64], u64),
+        grid=[dp, i32, i32, ctypes.POINTER(u64)], decode=[dp, i32, i32, u64, ctypes.POINTER(i32), ctypes.POINTER(u64)],
+        unit_info=[dp, i32, i32, u64, ctypes.POINTER(i32), ctypes.POINTER(u64)], coef=([dp, i32, i32], ctypes.c_float),
+        rho_pow=([dp, i32], ctypes.c_float), ordered_sum=([ctypes.POINTER(ctypes.c_float), u64], ctypes.c_float),
+        elem=([u64, i32, i32], u64), cover=([dp, i32, i32], u64)))
 
 
 def build_walk(tmpdir, sanitize=False):
-    """The shim and MAIN as one stand-alone program -> its path.  sanitize: built with -fsanitize=address,undefined."""
-    src = os.path.join(str(tmpdir), "loss_grad_route_walk.cpp")
-    with open(src, "w") as f:
-        f.write(SHIM + MAIN)
-    exe = os.path.join(str(tmpdir), "loss_grad_route_walk")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else []
-    subprocess.run([*CXX, *flags, src, "-o", exe], check=True)
-    return exe
+    return route_shim.build_walk(tmpdir, "loss_grad_route", SHIM + MAIN, sanitize)
 
 
 def walk_input(path):
@@ -444,19 +419,3 @@ def walk_input(path):
     with open(path, "wb") as f:
         f.write(np.asarray(words, np.int32).tobytes())
     return path
-
-
-def ordered_sum_model(src):
-    """ls_ordered_sum in numpy: thread-strided partials from 0 in rising order, then the in-place halving tree."""
-    src = np.asarray(src, np.float32)
-    rounds = -(-src.size // 256)
-    p = np.zeros(rounds * 256, np.float32)
-    p[:src.size] = src
-    red = np.zeros(256, np.float32)
-    for k in range(rounds):
-        red = red + p[k * 256:(k + 1) * 256]
-    w = 128
-    while w > 0:
-        red[:w] = red[:w] + red[w:2 * w]
-        w //= 2
-    return red[0]

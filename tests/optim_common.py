@@ -9,13 +9,13 @@ Hyperparameters are fp32 in the C ABI.  `widen` gives the doubles the library co
 fp64 references of the measured gates get those, so the gates measure arithmetic and not the representation of 0.999 in fp32."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -24  # unit roundoff of fp32
-MARGIN, FLOOR = 4.0, 2.0 ** -23  # the measured gate of DESIGN 3.4h: e <= MARGIN * max(e_torch32, FLOOR)
+from tests import route_shim
+from tests.route_shim import FLOOR, MARGIN, rel_err  # noqa: F401  (the measured gate of DESIGN 3.4h)
 THREADS, QUADS_PER_THREAD, CHUNK = 256, 2, 2048  # OPT_* of optim_route.h (test_optim_route.py checks them against the header)
 
 
@@ -123,13 +123,6 @@ def emulate_step(st, params, grads, groups, lrs, beta1, beta2, eps, max_norm, dt
                 g[:] = 0
             assert p.dtype == f and m.dtype == f and v.dtype == f and d.dtype == f
     return norm
-
-
-def rel_err(got, ref):
-    """e(T) = max |T - T64| / max |T64| (tests/layer_grad_common.py)."""
-    ref = np.asarray(ref, np.float64)
-    den = float(np.abs(ref).max())
-    return float(np.abs(np.asarray(got, np.float64) - ref).max()) / (den if den > 0 else 1.0)
 
 
 def torch_steps(params0, grads_per_step, groups, lrs, beta1, beta2, eps, max_norm, dtype):
@@ -290,38 +283,18 @@ int main(int argc, char **argv) {
 """
 CONSTANT_KEYS = ("THREADS", "WAVES", "QUAD", "QUADS_PER_THREAD", "CHUNK_QUADS", "CHUNK", "ALIGN", "SEG_BYTES")
 BLOCK_KEYS = ("segs_off", "chunk_seg_off", "lr_off", "state_off", "ss_off", "partial_off", "bytes")
-CXX = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-ffp-contract=off", "-I", os.path.join(ROOT, "tdmpc2_amd", "csrc")]
 
 
 def build_route(tmpdir):
-    src = os.path.join(str(tmpdir), "optim_route_shim.cpp")
-    with open(src, "w") as f:
-        f.write(SHIM)
-    so = os.path.join(str(tmpdir), "liboptim_route_shim.so")
-    subprocess.run([*CXX, "-shared", "-fPIC", src, "-o", so], check=True)
-    lib = ctypes.CDLL(so)
     i64p, u64, i32 = ctypes.POINTER(ctypes.c_int64), ctypes.c_uint64, ctypes.c_int32
-    lib.constants.argtypes = [ctypes.POINTER(i32)]
-    lib.layout.argtypes, lib.layout.restype = [ctypes.c_int64, i64p, i64p], u64
-    lib.chunks.argtypes, lib.chunks.restype = [u64], u64
-    lib.depth.argtypes, lib.depth.restype = [u64], u64
-    lib.cover_chunk.argtypes, lib.cover_chunk.restype = [u64, u64, ctypes.POINTER(ctypes.c_uint8)], u64
-    lib.seg_walk.argtypes, lib.seg_walk.restype = [i32, i64p, u64, ctypes.POINTER(i32)], u64
-    lib.block.argtypes = [u64, u64, u64, ctypes.POINTER(u64)]
-    lib.check_hyper.argtypes = [ctypes.c_float] * 4
-    lib.check_seg.argtypes = [ctypes.c_int64, i32, i32, ctypes.c_int]
-    return lib
+    return route_shim.build_shim(tmpdir, "optim_route", SHIM, dict(
+        constants=[ctypes.POINTER(i32)], layout=([ctypes.c_int64, i64p, i64p], u64), chunks=([u64], u64), depth=([u64], u64),
+        cover_chunk=([u64, u64, ctypes.POINTER(ctypes.c_uint8)], u64), seg_walk=([i32, i64p, u64, ctypes.POINTER(i32)], u64),
+        block=[u64, u64, u64, ctypes.POINTER(u64)], check_hyper=[ctypes.c_float] * 4, check_seg=[ctypes.c_int64, i32, i32, ctypes.c_int]))
 
 
 def build_walk(tmpdir, sanitize=False):
-    """The shim and MAIN as one stand-alone program -> its path.  sanitize: built with -fsanitize=address,undefined."""
-    src = os.path.join(str(tmpdir), "optim_route_walk.cpp")
-    with open(src, "w") as f:
-        f.write(SHIM + MAIN)
-    exe = os.path.join(str(tmpdir), "optim_route_walk")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else []
-    subprocess.run([*CXX, *flags, src, "-o", exe], check=True)
-    return exe
+    return route_shim.build_walk(tmpdir, "optim_route", SHIM + MAIN, sanitize)
 
 
 def walk_input(path):

@@ -15,11 +15,12 @@ fixture carries such a row at 101 bins, where neither torch's fp64 sum nor the l
 none."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
+from tests import route_shim
 from tests.optim_common import FLOOR, MARGIN, rel_err, widen  # noqa: F401  (the measured gate of DESIGN 3.4h)
+from tests.route_shim import gate, ordered_sum_model  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "pi_grad.npz")
@@ -240,11 +241,6 @@ def torch_ref(x, case, h, scale, dtype, g=1.0):
                 d_scaled_entropy=n(se.grad)[..., 0], d_q_logits=n(ql.grad), d_pi_out=n(y.grad))
 
 
-def gate(got, ref64, yard32):
-    """e and the bound MARGIN * max(e_torch32, FLOOR) of one tensor."""
-    return rel_err(got, ref64), MARGIN * max(rel_err(yard32, ref64), FLOOR)
-
-
 # ---------------------------------------------------------------- tdmpc2_amd/csrc/pi_grad_route.h behind a C shim
 SHIM = r"""
 #include <string.h>
@@ -371,7 +367,6 @@ int main(int argc, char **argv) {
 }
 """
 CONSTANT_KEYS = ("THREADS", "ROWS", "HEAD_LANES", "HEAD_ROWS", "MAXT", "MAXA", "MAXBINS", "KINDS", "DESC_BYTES", "GRID_BYTES")
-CXX = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-ffp-contract=off", "-I", os.path.join(ROOT, "tdmpc2_amd", "csrc")]
 ROUTE_SIZES = ((1, 1), (3, 9), (9, 33))  # (T, B): B T of 1, 27, 297
 
 
@@ -389,37 +384,16 @@ def desc_of(case, h=None, **over):
 
 
 def build_route(tmpdir):
-    src = os.path.join(str(tmpdir), "pi_grad_route_shim.cpp")
-    with open(src, "w") as f:
-        f.write(SHIM)
-    so = os.path.join(str(tmpdir), "libpi_grad_route_shim.so")
-    subprocess.run([*CXX, "-shared", "-fPIC", src, "-o", so], check=True)
-    lib = ctypes.CDLL(so)
     dp, u64, i32, fp = ctypes.POINTER(Desc), ctypes.c_uint64, ctypes.c_int32, ctypes.POINTER(ctypes.c_float)
-    lib.constants.argtypes = [ctypes.POINTER(i32)]
-    lib.check.argtypes = [dp]
-    lib.head_grid.argtypes, lib.head_grid.restype = [dp], u64
-    lib.value_grid.argtypes, lib.value_grid.restype = [dp], u64
-    lib.bwd_grid.argtypes = [dp, i32, ctypes.POINTER(u64)]
-    lib.step_of.argtypes = [dp, u64]
-    lib.mask_row.argtypes, lib.mask_row.restype = [dp, u64], u64
-    for name in ("bin", "rho_pow", "coef_q", "coef_se"):
-        getattr(lib, name).argtypes, getattr(lib, name).restype = [dp, i32], ctypes.c_float
-    lib.ordered_sum.argtypes, lib.ordered_sum.restype = [fp, u64], ctypes.c_float
-    lib.loss_serial.argtypes = [dp, fp, fp, fp, ctypes.c_float, fp, fp]
-    lib.cover.argtypes, lib.cover.restype = [dp], u64
-    return lib
+    return route_shim.build_shim(tmpdir, "pi_grad_route", SHIM, dict(
+        constants=[ctypes.POINTER(i32)], check=[dp], head_grid=([dp], u64), value_grid=([dp], u64), bwd_grid=[dp, i32, ctypes.POINTER(u64)],
+        step_of=[dp, u64], mask_row=([dp, u64], u64), ordered_sum=([fp, u64], ctypes.c_float),
+        loss_serial=[dp, fp, fp, fp, ctypes.c_float, fp, fp], cover=([dp], u64),
+        **{name: ([dp, i32], ctypes.c_float) for name in ("bin", "rho_pow", "coef_q", "coef_se")}))
 
 
 def build_walk(tmpdir, sanitize=False):
-    """The shim and MAIN as one stand-alone program -> its path.  sanitize: built with -fsanitize=address,undefined."""
-    src = os.path.join(str(tmpdir), "pi_grad_route_walk.cpp")
-    with open(src, "w") as f:
-        f.write(SHIM + MAIN)
-    exe = os.path.join(str(tmpdir), "pi_grad_route_walk")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else []
-    subprocess.run([*CXX, *flags, src, "-o", exe], check=True)
-    return exe
+    return route_shim.build_walk(tmpdir, "pi_grad_route", SHIM + MAIN, sanitize)
 
 
 def walk_input(path):
@@ -430,22 +404,6 @@ def walk_input(path):
     with open(path, "wb") as f:
         f.write(np.asarray(words, np.int32).tobytes())
     return path
-
-
-def ordered_sum_model(src):
-    """pg_ordered_sum in numpy: thread-strided partials from 0 in rising order, then the in-place halving tree."""
-    src = np.asarray(src, np.float32)
-    rounds = -(-src.size // 256)
-    p = np.zeros(rounds * 256, np.float32)
-    p[:src.size] = src
-    red = np.zeros(256, np.float32)
-    for k in range(rounds):
-        red = red + p[k * 256:(k + 1) * 256]
-    w = 128
-    while w > 0:
-        red[:w] = red[:w] + red[w:2 * w]
-        w //= 2
-    return red[0]
 
 
 def loss_model(q, entropy, se, h, scale):
