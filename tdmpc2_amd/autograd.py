@@ -127,6 +127,45 @@ class DropoutMasks:
         self.state.copy_(torch.tensor(words, dtype=torch.int32))
 
 
+class Draws:
+    """A device-side stream of a training step's draws (tdmpc2_draw_noise): standard normals and an ordered pair of distinct Q heads
+    per call, Philox keyed by (`seed`, native.DRAW_KEY_HI) -- `DropoutMasks` keys the same counter layout with (seed, 0), so the two
+    streams of one cfg.seed never coincide -- and counted by two words on the device that every `draw` advances by one in stream
+    order.  Nothing here reads the device or synchronises, so a draw can be captured in a graph, and every replay then draws afresh."""
+
+    def __init__(self, seed: int, device):
+        self.seed = int(seed) & 0xFFFFFFFF
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise native.NativeError(f"Draws draws on an MI355X only (device {self.device}); there is no CPU fallback")
+        self.state = torch.zeros(2, dtype=torch.int32, device=self.device)  # the call counter (lo, hi)
+
+    @property
+    def key(self) -> int:
+        """The 64-bit Philox key: seed in the low word, native.DRAW_KEY_HI in the high word."""
+        return (native.DRAW_KEY_HI << 32) | self.seed
+
+    def draw(self, shape, num_q: int):
+        """-> (eps fp32 [shape] of standard normals, qidx int32 [2]: two distinct heads out of num_q), fresh tensors from torch's
+        allocator, both from one call counter.  A shape of no elements draws the pair alone (the library takes n == 0 only with a
+        NULL normal buffer) and still advances the counter."""
+        eps = torch.empty(tuple(int(s) for s in shape), dtype=torch.float32, device=self.device)
+        qidx = torch.empty(2, dtype=torch.int32, device=self.device)
+        native.draw_noise(native.draw_desc(eps.numel(), num_q, self.key), self.state, eps if eps.numel() else None, qidx)
+        return eps, qidx
+
+    def state_dict(self):
+        """The seed and the counter (one device read): enough to resume the stream.  Not part of the reference's checkpoint."""
+        lo, hi = (int(v) & 0xFFFFFFFF for v in self.state.tolist())
+        return {"seed": self.seed, "counter": (hi << 32) | lo}
+
+    def load_state_dict(self, sd):
+        self.seed = int(sd["seed"]) & 0xFFFFFFFF
+        c = int(sd["counter"]) & 0xFFFFFFFFFFFFFFFF
+        words = [w - (1 << 32) if w >= (1 << 31) else w for w in (c & 0xFFFFFFFF, c >> 32)]
+        self.state.copy_(torch.tensor(words, dtype=torch.int32))
+
+
 def ensemble_apply(params, x, mask=None):
     """`QEnsemble.apply_params(params, x, mask)` for a `layers.StackedMLPParams`: x [..., K] -> [n, ..., out]; the first layer reads
     the one x for every member (shared_x), so its dx is the sum over members.  mask: None, or the dropout multipliers of the first

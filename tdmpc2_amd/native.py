@@ -154,6 +154,11 @@ class DropoutDesc(C.Structure):  # struct tdmpc2_dropout_desc (include/tdmpc2_dr
                 ("call_hi", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class DrawDesc(C.Structure):  # struct tdmpc2_draw_desc (include/tdmpc2_draw.h)
+    _fields_ = [("n", C.c_int64), ("num_q", C.c_int32), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("call_lo", C.c_uint32),
+                ("call_hi", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class Debug(C.Structure):
     _fields_ = [("value", C.c_void_p), ("elite_idx", C.c_void_p), ("score", C.c_void_p), ("mean", C.c_void_p),
                 ("std", C.c_void_p), ("actions", C.c_void_p)]
@@ -244,10 +249,14 @@ _PI_GRAD_H = {"tdmpc2_pigrad_" + name: [_P(PiGradDesc)] + [_vp] * nptr for name,
               (("head_forward", 7), ("head_backward", 7), ("value_forward", 3), ("loss_forward", 7), ("loss_backward", 6))}
 # include/tdmpc2_dropout.h: the dropout-mask unit, again a header of its own beside ABI 14
 _DROPOUT_H = {"tdmpc2_dropout_mask": [_P(DropoutDesc), _vp, _vp, _vp]}
-PROTOTYPES = {"tdmpc2_plan.h": _PLAN_H, "tdmpc2_pi_grad.h": _PI_GRAD_H, "tdmpc2_dropout.h": _DROPOUT_H}  # by header under include/
+# include/tdmpc2_draw.h: the draw unit (normals and a pair of Q heads), a header of its own as well
+_DRAW_H = {"tdmpc2_draw_noise": [_P(DrawDesc), _vp, _vp, _vp, _vp]}
+PROTOTYPES = {"tdmpc2_plan.h": _PLAN_H, "tdmpc2_pi_grad.h": _PI_GRAD_H, "tdmpc2_dropout.h": _DROPOUT_H,
+              "tdmpc2_draw.h": _DRAW_H}  # by header under include/
 ABI_SYMBOLS = list(_PLAN_H)  # every symbol include/tdmpc2_plan.h declares (tests check the .so exports all of them)
 PI_GRAD_SYMBOLS = tuple(_PI_GRAD_H)
 DROPOUT_SYMBOLS = tuple(_DROPOUT_H)
+DRAW_SYMBOLS = tuple(_DRAW_H)
 
 
 def signature(sig):
@@ -1381,7 +1390,8 @@ def layer_desc(kind: int, groups: int, rows: int, in_dim: int, out_dim: int, sha
                      shared_x=int(bool(shared_x)), simnorm_dim=int(simnorm_dim), ln_eps=float(ln_eps))
 
 
-_UNIT_COUNTER = dict(layer="LAYER_CALLS", loss="LOSS_CALLS", pigrad="PI_GRAD_CALLS", dropout="DROPOUT_CALLS")
+_UNIT_COUNTER = dict(layer="LAYER_CALLS", loss="LOSS_CALLS", pigrad="PI_GRAD_CALLS", dropout="DROPOUT_CALLS",
+                     draw="DRAW_CALLS")
 
 
 def _unit_check(tag: str, rc: int):
@@ -1390,7 +1400,7 @@ def _unit_check(tag: str, rc: int):
 
 
 def _unit_call(tag: str, symbol: str, desc, first, want, tail, **ts):
-    """The one call path of the stateless units (layer, loss, pigrad, dropout): `first` names the device; every tensor of `ts` (the
+    """The one call path of the stateless units (layer, loss, pigrad, dropout, draw): `first` names the device; every tensor of `ts` (the
     C order after the descriptor; None = absent, a c_void_p = a pointer its caller has checked) is contiguous fp32 on it and holds
     what `want` (name -> element count, or None: the library sees pointers only) asks for; then the unit's counter, the call on the
     current stream with `tail` between the tensors and the stream, and the library's error."""
@@ -1642,3 +1652,34 @@ def dropout_mask(desc: DropoutDesc, state, out):
         raise NativeError(f"dropout_mask: state must be two contiguous int32 words on {out.device} (got {state.dtype}, {state.device}, "
                           f"{state.numel()} elements)")
     _unit_call("dropout", "tdmpc2_dropout_mask", desc, out, None, (), state=_ptr(state), mask=out)
+
+
+# ---------------------------------------------------------------- draws of a training step (tdmpc2_draw_noise, include/tdmpc2_draw.h)
+DRAW_CALLS = 0  # library calls made through the wrapper below, kept like DROPOUT_CALLS
+DRAW_KEY_HI = 0x44524157  # "DRAW": the high key word of autograd.Draws, which keeps its stream apart from DropoutMasks' (seed, 0)
+
+
+def draw_desc(n: int, num_q: int = 0, seed: int = 0, call: int = 0) -> DrawDesc:
+    """n normals and (where the call is given a pair buffer) a pair out of num_q heads; `seed` is the 64-bit Philox key, `call` the
+    64-bit call counter (read only when the call is given no device counter)."""
+    seed, call = int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFFFFFFFFFF
+    return DrawDesc(n=int(n), num_q=int(num_q), seed_lo=seed & 0xFFFFFFFF, seed_hi=seed >> 32, call_lo=call & 0xFFFFFFFF,
+                    call_hi=call >> 32, reserved=0)
+
+
+def draw_noise(desc: DrawDesc, state, normal=None, pair=None):
+    """tdmpc2_draw_noise on the current stream: `normal` (contiguous fp32 on the GPU, at least desc.n elements, 16-byte aligned; None
+    with desc.n == 0) is overwritten with standard normals and `pair` (two contiguous int32 words on the same device, or None) with
+    an ordered pair of distinct heads out of desc.num_q.  `state`: None (the descriptor's call counter is used) or two int32 words
+    on the same device holding the counter, which the call advances by one in stream order.  No host read, no synchronisation."""
+    first = normal if normal is not None else pair
+    if first is None:
+        raise NativeError("draw_noise: both outputs are None")
+    if normal is not None and normal.numel() < desc.n:
+        raise NativeError(f"draw_noise: normal holds {normal.numel()} floats, the descriptor asks for {desc.n}")
+    for name, t in (("state", state), ("pair", pair)):
+        if t is not None and (t.device != first.device or t.dtype != torch.int32 or t.numel() != 2 or not t.is_contiguous()):
+            raise NativeError(f"draw_noise: {name} must be two contiguous int32 words on {first.device} (got {t.dtype}, {t.device}, "
+                              f"{t.numel()} elements)")
+    # (the call path checks fp32 tensors; state and pair go as pointers the checks above cover)
+    _unit_call("draw", "tdmpc2_draw_noise", desc, first, None, (), state=_ptr(state), normal=normal, pair=_ptr(pair))

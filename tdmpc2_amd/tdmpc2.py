@@ -64,6 +64,11 @@ class TDMPC2(torch.nn.Module):
         # True: sync_planner_weights() re-packs an existing handle from the model's own parameter tensors in at most four launches
         # (tdmpc2_plan_refresh_weights: no copies, no stream synchronisation); off by default -- the per-layer binds
         self.native_refresh = False
+        # True: the draws of a training step (the policy noise and the two Q heads of the TD target and of `update_pi`) are made in the
+        # library from a counter on the device (autograd.Draws, tdmpc2_draw_noise), so the step reads no host seed and no framework
+        # generator; off by default -- the host seed and torch's generator, as before
+        self.native_draws = False
+        self._draws = None  # made by the first read of `draws`
         self._reuse_shift = False
         self._planner: Optional[NativePlanner] = None
         self._optim = self._pi_optim = None  # made by the first read of `optim` / `pi_optim`: nothing for a planning-only user
@@ -97,6 +102,14 @@ class TDMPC2(torch.nn.Module):
     @native_dropout.setter
     def native_dropout(self, on: bool):
         self.model.native_dropout = bool(on)
+
+    @property
+    def draws(self):
+        """The draw stream of the training step (autograd.Draws keyed by cfg.seed), made on this device at first use."""
+        if self._draws is None:
+            from . import autograd
+            self._draws = autograd.Draws(int(getattr(self.cfg, "seed", 0)), self.device)
+        return self._draws
 
     # ------------------------------------------------------------------ checkpoint I/O
     def save(self, fp):
@@ -150,10 +163,16 @@ class TDMPC2(torch.nn.Module):
         self._planner.bind_policy(sd)
 
     def sync_planner_weights(self):
-        """Re-pack the model's current weights into the planner (after load / a training step)."""
+        """Re-pack the model's current weights into the planner (after load / a training step).  Reads log_std_min / log_std_dif
+        from the device (two host reads): a handle made with other constants is dropped and rebuilt by the next planner() call."""
         if self._planner is not None and self._planner_log_std != self._log_std():
             self._planner.close()
             self._planner = None  # rebuilt (with the new constants and weights) by the next planner() call
+        self._repack_planner()
+
+    def _repack_planner(self):
+        """`sync_planner_weights` without the comparison of the handle's constants: no device read, no synchronisation.  What an
+        optimiser step needs -- log_std_min / log_std_dif are buffers that no optimiser holds."""
         if self._planner is not None and self.native_refresh:
             self._planner.refresh_state_dict(self._refresh_state_dict())  # the policy prior's copy included, when bound
             if self.native_pixel_encoder and self.cfg.obs == "rgb":
@@ -199,12 +218,13 @@ class TDMPC2(torch.nn.Module):
         return self._pi_optim
 
     def optimizer_step(self, which: str = "model"):
-        """clip_grad_norm_ + step + zero_grad of `optim` ("model") or `pi_optim` ("pi") in the library, then `sync_planner_weights()`
-        so that the planner's packed weights follow.  Returns the gradient norm (0-d device tensor)."""
+        """clip_grad_norm_ + step + zero_grad of `optim` ("model") or `pi_optim` ("pi") in the library, then the re-pack of
+        `sync_planner_weights()` so that the planner's packed weights follow -- without its comparison of log_std_min / log_std_dif,
+        which are buffers no optimiser steps: the call makes no host read of them.  Returns the gradient norm (0-d device tensor)."""
         if which not in ("model", "pi"):
             raise ValueError(f"optimizer_step: which must be 'model' or 'pi', got {which!r}")
         norm = (self.optim if which == "model" else self.pi_optim).step()
-        self.sync_planner_weights()
+        self._repack_planner()
         return norm
 
     def soft_update_target_Q(self):
@@ -451,6 +471,9 @@ class TDMPC2(torch.nn.Module):
             discount = self.discount
         if pi_eps is not None:
             pi_eps = pi_eps.reshape(-1, pi_eps.shape[-1]).to(self.device, torch.float32).contiguous()
+        # The host seed is passed by value.  With `native_draws` `_update_model` gives both `pi_eps` and `qidx`, so the kernels read
+        # no bit of it -- but the stream that plan() / act() share still advances once per training step, and a capture of this
+        # call would bake the value in: harmless only as long as both draws are given.
         self._seed += 1
         td = self.planner().td_target(z2, r2, t2, discount, pi_eps=pi_eps, qidx=qidx, seed=self._seed, **kw)
         return td.reshape(*lead, 1)
@@ -548,7 +571,8 @@ class TDMPC2(torch.nn.Module):
         """The model half of `_update` (reference tdmpc2.py:260-310: everything but `update_pi` and the target-Q soft update), every
         piece in the library: obs [H+1, B, *], action [H, B, A], reward / terminated [H, B, 1], task [B].  In order:
           1. under no_grad, next_z = encode(obs[1:]) and the TD target (`_td_target`, or `td_targets` [H, B, 1] as given; `pi_eps` /
-             `qidx` pin its noise and heads; the target used stays readable as `last_td_targets`);
+             `qidx` pin its noise and heads, which with `native_draws` come from one `draws.draw([H, B, A], num_q)` made on every
+             call, else from the host seed; the target used stays readable as `last_td_targets`);
           2. model.train();
           3. the rollout through `model.next`, then `Q(..., 'all')`, `reward` and (episodic) `termination` under `native_autograd`;
           4. `autograd.model_loss` and `total.backward()`;
@@ -578,6 +602,10 @@ class TDMPC2(torch.nn.Module):
         if task is not None:
             task = torch.as_tensor(task, device=self.device)
         self.optim  # noqa: B018  (made before backward: every .grad is then a view into its gradient arena)
+        if self.native_draws:  # one draw, whatever is pinned: the counter is a function of the step count; a pin overrides its value
+            eps, pair = self.draws.draw((H, B, cfg.action_dim), cfg.num_q)
+            pi_eps = eps if pi_eps is None else pi_eps
+            qidx = pair if qidx is None else qidx
         with torch.no_grad():
             next_z = self.model.encode(obs[1:], task)
             if td_targets is None:
@@ -614,7 +642,8 @@ class TDMPC2(torch.nn.Module):
           1. action, info = model.pi(zs, task): the MLP through the trainable layer, its tail through `autograd.PiHeadFn`
              (`pi_eps` [H+1, B, A] pins the noise, else torch.randn_like draws it);
           2. `model.Q_pair` on the online parameters, detached: the two heads `qidx` (drawn with torch.randperm on the device when
-             not given), the reference's Q(..., 'avg', detach=True);
+             not given), the reference's Q(..., 'avg', detach=True); with `native_draws` the noise and the heads that are not
+             pinned come from one `draws.draw([H+1, B, A], num_q)`, made on every call;
           3. `scale.update(qs[0])`, 4. the rho-weighted loss at the updated scale (both inside `autograd.pi_loss`);
           5. `pi_loss.backward()`: the seeds of the loss, the Q pair's dx, the head and `_pi`'s layers, all in HIP;
           6. `optimizer_step("pi")`: clip at cfg.grad_clip_norm, Adam with eps 1e-5, zero_grad and the planner's re-pack.
@@ -636,6 +665,10 @@ class TDMPC2(torch.nn.Module):
             task = torch.as_tensor(task, device=self.device)
         if pi_eps is not None:
             pi_eps = pi_eps.to(self.device, torch.float32)
+        if self.native_draws:  # one draw, whatever is pinned (see _update_model)
+            eps, pair = self.draws.draw((*zs.shape[:2], cfg.action_dim), cfg.num_q)
+            pi_eps = eps if pi_eps is None else pi_eps
+            qidx = pair if qidx is None else qidx
         if qidx is None:
             qidx = torch.randperm(cfg.num_q, device=self.device)[:2]
         self.pi_optim  # noqa: B018  (made before backward: every .grad of _pi is then a view into its gradient arena)
@@ -655,7 +688,8 @@ class TDMPC2(torch.nn.Module):
         pi_scale).  With `native_dropout` (and cfg.dropout > 0) the two train-mode Q passes drop as the reference's do: one `_update`
         makes exactly two mask draws, the value-loss pass first, then `update_pi`'s pair; the TD target draws none (the target
         ensemble is in eval mode in the reference too).  With the flag off there is no dropout, and equality with the reference holds
-        for cfg.dropout == 0.
+        for cfg.dropout == 0.  With `native_draws` one `_update` makes exactly two draws from `draws`, the TD target's first, then
+        `update_pi`'s, whatever is pinned: no host seed and no framework generator is read.
         `pins` (parity tests): a dict with any of td_pi_eps [H, B, A] / td_qidx (the TD target's noise and heads), td_targets
         [H, B, 1] (the target itself), pi_eps [H+1, B, A] / qidx (`update_pi`'s), q_mask [num_q, H, B, mlp_dim] (the value-loss
         pass's dropout multipliers) and pi_q_mask [2, H+1, B, mlp_dim] (`update_pi`'s); None: every draw is made as before."""
