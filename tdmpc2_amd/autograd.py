@@ -5,7 +5,9 @@ HIP; `mlp_apply` and `ensemble_apply` walk the modules of tdmpc2_amd/layers.py t
 `WorldModel.next / reward / pi / Q` computes every MLP gradient in the library.  `ModelLossFn` / `model_loss` are the four losses of
 `TDMPC2._update` and the gradient seeds of their total (tdmpc2_loss_forward / tdmpc2_loss_backward).  `PiHeadFn`, `PiLossFn` / `pi_loss`
 are `update_pi` between its layers (tdmpc2_pigrad_*, include/tdmpc2_pi_grad.h): the Gaussian head after `_pi`'s MLP, and two_hot_inv of
-the two drawn Q heads, the running scale and the rho-weighted loss.  There is no fallback: a CPU tensor is an error.
+the two drawn Q heads, the running scale and the rho-weighted loss.  `TaskConcatFn` / `task_concat` are the task conditioning of a
+multitask model (tdmpc2_task_*, include/tdmpc2_task.h): the embedding lookup with max_norm and the concatenation [x | emb | a] that
+feeds a network's first layer, with their backward.  There is no fallback: a CPU tensor is an error.
 """
 from __future__ import annotations
 
@@ -324,3 +326,60 @@ def pi_loss(cfg, q_logits, entropy, scaled_entropy, scale_module, update_scale=T
     desc = pi_desc(cfg, T, B, cfg.action_dim, NB, 0.0, 0.0)  # (the value and loss calls read neither log_std constant)
     return PiLossFn.apply(desc, q_logits, entropy.detach().to(torch.float32), scaled_entropy.to(torch.float32), scale_module,
                           bool(update_scale))  # (entropy only feeds a mean of the info dict)
+
+
+class TaskConcatFn(torch.autograd.Function):
+    """out = [x | weight[ids] | a], the first-layer input of a multitask model's networks (WorldModel.task_emb and the torch.cat of
+    its callers), through tdmpc2_task_forward / tdmpc2_task_backward (include/tdmpc2_task.h).  The forward renormalises the rows of
+    `weight` that `ids` names in place, on `weight.data`, as F.embedding(max_norm=...) does: the renorm is not differentiated.  Saves
+    `ids` alone.  The backward asks the library only for the gradients autograd needs: dtable (summed in the header's fixed order,
+    the whole table written), dx and da (copies)."""
+
+    @staticmethod
+    def forward(ctx, weight, ids, x, a, desc):
+        R, W = desc.steps * desc.batch, desc.x_dim + desc.task_dim + desc.a_dim
+        xc = x.detach().to(torch.float32).contiguous()
+        ac = None if a is None else a.detach().to(torch.float32).contiguous()
+        out = torch.empty((R, W), dtype=torch.float32, device=x.device)
+        native.task_forward(desc, weight.data, ids, xc, ac, out)
+        ctx.desc, ctx.x_shape, ctx.a_shape = desc, x.shape, None if a is None else a.shape
+        ctx.save_for_backward(ids)
+        return out.view(*x.shape[:-1], W)
+
+    @staticmethod
+    def backward(ctx, dout):
+        (ids,) = ctx.saved_tensors
+        desc = ctx.desc
+        need_w, _, need_x, need_a = ctx.needs_input_grad[:4]
+        need_a = need_a and ctx.a_shape is not None
+        if not (need_w or need_x or need_a):
+            return None, None, None, None, None
+        dev = dout.device
+        dtable = torch.empty((desc.num_tasks, desc.task_dim), dtype=torch.float32, device=dev) if need_w else None
+        dx = torch.empty(ctx.x_shape, dtype=torch.float32, device=dev) if need_x else None
+        da = torch.empty(ctx.a_shape, dtype=torch.float32, device=dev) if need_a else None
+        native.task_backward(desc, ids, dout.detach().to(torch.float32).contiguous(), dx, da, dtable)
+        return dtable, None, dx, da, None
+
+
+def task_concat(weight, ids, x, a=None, max_norm=1.0):
+    """[x | weight[ids] | a] in one library call (two launches with the renorm), differentiable in weight, x and a.  weight
+    [num_tasks, T] (contiguous fp32, renormalised in place when max_norm > 0); x [S, B, D] with ids [B] or one id, or x [N, D] with
+    ids [N] or one id -- the three branches of WorldModel.task_emb; a, when given, shaped as x but for its last dimension; ids an
+    int, or an int32 / int64 tensor (anything else is converted to int64).  There is no fallback: a CPU tensor is an error."""
+    if isinstance(ids, int):
+        ids = torch.tensor([ids], device=x.device)
+    if ids.dtype not in (torch.int32, torch.int64):
+        ids = ids.long()
+    ids = ids.reshape(-1).contiguous()
+    if x.dim() not in (2, 3) or (a is not None and a.shape[:-1] != x.shape[:-1]):
+        raise native.NativeError(f"task_concat: x [S, B, D] or [N, D] and a shaped alike (got {tuple(x.shape)}, "
+                                 f"{None if a is None else tuple(a.shape)})")
+    steps, batch = (int(x.shape[0]), int(x.shape[1])) if x.dim() == 3 else (1, int(x.shape[0]))
+    if ids.numel() not in (1, batch):
+        raise native.NativeError(f"task_concat: {ids.numel()} ids for {batch} batch columns")
+    if weight.dtype != torch.float32 or not weight.is_contiguous() or weight.dim() != 2:
+        raise native.NativeError("task_concat: weight must be a contiguous fp32 [num_tasks, T] tensor")
+    desc = native.task_desc(steps, batch, ids.numel(), ids.element_size(), weight.shape[0], x.shape[-1], weight.shape[1],
+                            0 if a is None else a.shape[-1], max_norm if max_norm is not None else 0.0)
+    return TaskConcatFn.apply(weight, ids, x, a, desc)

@@ -159,6 +159,11 @@ class DrawDesc(C.Structure):  # struct tdmpc2_draw_desc (include/tdmpc2_draw.h)
                 ("call_hi", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class TaskDesc(C.Structure):  # struct tdmpc2_task_desc (include/tdmpc2_task.h)
+    _fields_ = [(n, C.c_int32) for n in ("steps", "batch", "ids_len", "id_bytes", "num_tasks", "x_dim", "task_dim", "a_dim")] + \
+               [("max_norm", C.c_float), ("reserved", C.c_uint32)]
+
+
 class Debug(C.Structure):
     _fields_ = [("value", C.c_void_p), ("elite_idx", C.c_void_p), ("score", C.c_void_p), ("mean", C.c_void_p),
                 ("std", C.c_void_p), ("actions", C.c_void_p)]
@@ -251,12 +256,16 @@ _PI_GRAD_H = {"tdmpc2_pigrad_" + name: [_P(PiGradDesc)] + [_vp] * nptr for name,
 _DROPOUT_H = {"tdmpc2_dropout_mask": [_P(DropoutDesc), _vp, _vp, _vp]}
 # include/tdmpc2_draw.h: the draw unit (normals and a pair of Q heads), a header of its own as well
 _DRAW_H = {"tdmpc2_draw_noise": [_P(DrawDesc), _vp, _vp, _vp, _vp]}
+# include/tdmpc2_task.h: the task unit (embedding renorm, the [x | emb | a] gather and their backward), a header of its own too
+_TASK_H = {"tdmpc2_task_forward": [_P(TaskDesc)] + [_vp] * 6, "tdmpc2_task_backward": [_P(TaskDesc)] + [_vp] * 6,
+           "tdmpc2_task_renorm": [_P(TaskDesc)] + [_vp] * 3}
 PROTOTYPES = {"tdmpc2_plan.h": _PLAN_H, "tdmpc2_pi_grad.h": _PI_GRAD_H, "tdmpc2_dropout.h": _DROPOUT_H,
-              "tdmpc2_draw.h": _DRAW_H}  # by header under include/
+              "tdmpc2_draw.h": _DRAW_H, "tdmpc2_task.h": _TASK_H}  # by header under include/
 ABI_SYMBOLS = list(_PLAN_H)  # every symbol include/tdmpc2_plan.h declares (tests check the .so exports all of them)
 PI_GRAD_SYMBOLS = tuple(_PI_GRAD_H)
 DROPOUT_SYMBOLS = tuple(_DROPOUT_H)
 DRAW_SYMBOLS = tuple(_DRAW_H)
+TASK_SYMBOLS = tuple(_TASK_H)
 
 
 def signature(sig):
@@ -1391,7 +1400,7 @@ def layer_desc(kind: int, groups: int, rows: int, in_dim: int, out_dim: int, sha
 
 
 _UNIT_COUNTER = dict(layer="LAYER_CALLS", loss="LOSS_CALLS", pigrad="PI_GRAD_CALLS", dropout="DROPOUT_CALLS",
-                     draw="DRAW_CALLS")
+                     draw="DRAW_CALLS", task="TASK_CALLS")
 
 
 def _unit_check(tag: str, rc: int):
@@ -1400,7 +1409,7 @@ def _unit_check(tag: str, rc: int):
 
 
 def _unit_call(tag: str, symbol: str, desc, first, want, tail, **ts):
-    """The one call path of the stateless units (layer, loss, pigrad, dropout, draw): `first` names the device; every tensor of `ts` (the
+    """The one call path of the stateless units (layer, loss, pigrad, dropout, draw, task): `first` names the device; every tensor of `ts` (the
     C order after the descriptor; None = absent, a c_void_p = a pointer its caller has checked) is contiguous fp32 on it and holds
     what `want` (name -> element count, or None: the library sees pointers only) asks for; then the unit's counter, the call on the
     current stream with `tail` between the tensors and the stream, and the library's error."""
@@ -1414,7 +1423,7 @@ def _unit_call(tag: str, symbol: str, desc, first, want, tail, **ts):
             raise NativeError(f"{what}: {name} must be a contiguous fp32 tensor on {device} (got {t.dtype}, {t.device}, "
                               f"contiguous={t.is_contiguous()})")
     for name, t in ts.items() if want else ():
-        if t is not None and t.numel() != want[name]:
+        if t is not None and type(t) is not C.c_void_p and t.numel() != want[name]:
             raise NativeError(f"{what}: {name} holds {t.numel()} floats, the descriptor asks for {want[name]}")
     globals()[_UNIT_COUNTER[tag]] += 1
     with torch.cuda.device(device):
@@ -1683,3 +1692,57 @@ def draw_noise(desc: DrawDesc, state, normal=None, pair=None):
                               f"{t.numel()} elements)")
     # (the call path checks fp32 tensors; state and pair go as pointers the checks above cover)
     _unit_call("draw", "tdmpc2_draw_noise", desc, first, None, (), state=_ptr(state), normal=normal, pair=_ptr(pair))
+
+
+# ---------------------------------------------------------------- task conditioning (tdmpc2_task_*, include/tdmpc2_task.h)
+TASK_CALLS = 0  # library calls made through the wrappers below (forward + backward + renorm), kept like DRAW_CALLS
+
+
+def task_desc(steps: int, batch: int, ids_len: int, id_bytes: int, num_tasks: int, x_dim: int, task_dim: int, a_dim: int = 0,
+              max_norm: float = 1.0) -> TaskDesc:
+    """R = steps * batch rows [x_dim | task_dim | a_dim]; row t * batch + b reads ids[0] (ids_len 1) or ids[b] (ids_len batch);
+    max_norm <= 0: the forward does not renorm."""
+    return TaskDesc(steps=int(steps), batch=int(batch), ids_len=int(ids_len), id_bytes=int(id_bytes), num_tasks=int(num_tasks),
+                    x_dim=int(x_dim), task_dim=int(task_dim), a_dim=int(a_dim), max_norm=float(max_norm), reserved=0)
+
+
+def _task_ids(what: str, desc: TaskDesc, ids, device):
+    """The id list as a checked pointer: contiguous int32 or int64 (as desc.id_bytes says) on `device`, desc.ids_len elements."""
+    if device.type != "cuda":
+        raise NativeError(f"{what} runs on an MI355X only (device {device}); there is no CPU fallback")
+    want = {4: torch.int32, 8: torch.int64}.get(desc.id_bytes)
+    if ids.device != device or ids.dtype != want or ids.numel() != desc.ids_len or not ids.is_contiguous():
+        raise NativeError(f"{what}: ids must be {desc.ids_len} contiguous {want} words on {device} (got {ids.dtype}, {ids.device}, "
+                          f"{ids.numel()} elements)")
+    return _ptr(ids)
+
+
+def _task_want(desc: TaskDesc) -> dict:
+    """Element counts of the layouts of include/tdmpc2_task.h (the library sees pointers only)."""
+    R, D, T, A = desc.steps * desc.batch, desc.x_dim, desc.task_dim, desc.a_dim
+    W = D + T + A
+    return dict(table=desc.num_tasks * T, x=R * D, a=R * A, out=R * W, dout=R * W, dx=R * D, da=R * A, dtable=desc.num_tasks * T)
+
+
+def task_forward(desc: TaskDesc, table, ids, x, a=None, out=None):
+    """tdmpc2_task_forward on the current stream: `table` [num_tasks, T] is renormalised in place (the rows `ids` names, when
+    desc.max_norm > 0), then out [R, D + T + A] = [x | table[id] | a] is written.  Tensors are contiguous fp32 on one GPU."""
+    _unit_call("task", "tdmpc2_task_forward", desc, table, _task_want(desc), (), table=table,
+               ids=_task_ids("task_forward", desc, ids, table.device), x=x, a=a, out=out)
+
+
+def task_backward(desc: TaskDesc, ids, dout, dx=None, da=None, dtable=None):
+    """tdmpc2_task_backward on the current stream: dx [R, D] and da [R, A] are copies of dout's blocks, dtable [num_tasks, T] the
+    sum of dout's embedding block per task in the header's fixed order (zeros for a task no row names).  The outputs that are not
+    None are overwritten."""
+    if dx is None and da is None and dtable is None:
+        raise NativeError("task_backward: all three outputs are None")
+    _unit_call("task", "tdmpc2_task_backward", desc, dout, _task_want(desc), (),
+               ids=_task_ids("task_backward", desc, ids, dout.device), dout=dout, dx=dx,
+               da=da, dtable=dtable)
+
+
+def task_renorm(desc: TaskDesc, table, ids):
+    """tdmpc2_task_renorm on the current stream: the forward's renorm alone."""
+    _unit_call("task", "tdmpc2_task_renorm", desc, table, _task_want(desc), (), table=table,
+               ids=_task_ids("task_renorm", desc, ids, table.device))

@@ -104,6 +104,17 @@ class TDMPC2(torch.nn.Module):
         self.model.native_dropout = bool(on)
 
     @property
+    def native_task_emb(self) -> bool:
+        """True: on a multitask model the first-layer inputs of encode (state), next, reward, Q, Q_pair and pi come from the library's
+        task unit, forward and backward (WorldModel.native_task_emb).  The training methods need `native_autograd` as before; the
+        no-grad methods (planning, acting, the TD target) do not read the flag."""
+        return self.model.native_task_emb
+
+    @native_task_emb.setter
+    def native_task_emb(self, on: bool):
+        self.model.native_task_emb = bool(on)
+
+    @property
     def draws(self):
         """The draw stream of the training step (autograd.Draws keyed by cfg.seed), made on this device at first use."""
         if self._draws is None:

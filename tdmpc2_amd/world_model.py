@@ -101,6 +101,10 @@ class WorldModel(nn.Module):
         # train mode; off by default -- no dropout in any mode
         self.native_dropout = False
         self._q_masks = None  # made by the first read of `q_masks`
+        # True (multitask, the input on the GPU): encode (state observations), next, reward, Q, Q_pair and pi build their first-layer
+        # input [x | task_emb | a] with one library call each (autograd.task_concat, tdmpc2_task_forward: the max_norm renorm, the
+        # lookup and the concatenations; its backward in tdmpc2_task_backward); off by default -- nn.Embedding and torch.cat
+        self.native_task_emb = False
         self._log_std_host = None  # host copies of log_std_min / log_std_dif for the library's policy head (made at first use)
         self.apply(self._weight_init)
         self._register_state_dict_hook(self._add_meta_keys)
@@ -161,6 +165,15 @@ class WorldModel(nn.Module):
             emb = emb.repeat(x.shape[0], 1)
         return torch.cat([x, emb], dim=-1)
 
+    def _net_in(self, x, task, a=None):
+        """The first-layer input of a network: [x | task_emb(task) | a] on multitask models, [x | a] otherwise.  With
+        `native_task_emb` and the input on the GPU the multitask form is one `autograd.task_concat` call."""
+        if self.cfg.multitask:
+            if self.native_task_emb and x.is_cuda:
+                return autograd.task_concat(self._task_emb.weight, task, x, a, self._task_emb.max_norm)
+            x = self.task_emb(x, task)
+        return x if a is None else torch.cat([x, a], dim=-1)
+
     def _mlp(self, seq, x):
         if self.native_autograd and x.is_cuda:
             return autograd.mlp_apply(seq, x)
@@ -168,8 +181,8 @@ class WorldModel(nn.Module):
 
     def encode(self, obs, task):
         """reference world_model.py:103-112, including the [T, B, C, H, W] pixel-sequence branch."""
-        if self.cfg.multitask:
-            obs = self.task_emb(obs, task)
+        if self.cfg.multitask:  # (rgb observations keep the module's lookup)
+            obs = self._net_in(obs, task) if self.cfg.obs == "state" else self.task_emb(obs, task)
         if self.cfg.obs == "rgb" and obs.ndim == 5:
             return torch.stack([self._encoder[self.cfg.obs](o) for o in obs])
         if self.cfg.obs == "state":
@@ -177,14 +190,10 @@ class WorldModel(nn.Module):
         return self._encoder[self.cfg.obs](obs)
 
     def next(self, z, a, task):
-        if self.cfg.multitask:
-            z = self.task_emb(z, task)
-        return self._mlp(self._dynamics, torch.cat([z, a], dim=-1))
+        return self._mlp(self._dynamics, self._net_in(z, task, a))
 
     def reward(self, z, a, task):
-        if self.cfg.multitask:
-            z = self.task_emb(z, task)
-        return self._mlp(self._reward, torch.cat([z, a], dim=-1))
+        return self._mlp(self._reward, self._net_in(z, task, a))
 
     def termination(self, z, task, unnormalized=False):
         """reference world_model.py:132-141 (episodic models only)."""
@@ -199,9 +208,7 @@ class WorldModel(nn.Module):
         `native_autograd` and the input on the GPU everything after the MLP runs in the library (autograd.PiHeadFn, forward and
         backward): the same expression, so the action stream is unchanged in distribution, but its bits differ from torch's (the
         library's tanh / exp / log and its order of the row sums)."""
-        if self.cfg.multitask:
-            z = self.task_emb(z, task)
-        out = self._mlp(self._pi, z)
+        out = self._mlp(self._pi, self._net_in(z, task))
         if self.native_autograd and out.is_cuda:
             return self._pi_native(out, task, eps)
         eps = torch.randn_like(out[..., : out.shape[-1] // 2]) if eps is None else eps
@@ -273,9 +280,7 @@ class WorldModel(nn.Module):
         the two heads; None: drawn for the two heads only under the conditions of `_q_mask` (the members' masks are independent, so
         this is the reference's distribution), else no dropout."""
         from types import SimpleNamespace
-        if self.cfg.multitask:
-            z = self.task_emb(z, task)
-        za = torch.cat([z, a], dim=-1)
+        za = self._net_in(z, task, a)
         idx = torch.as_tensor(qidx, device=za.device).long().reshape(2)
         pick = lambda t: t.detach().index_select(0, idx)  # noqa: E731
 
@@ -295,9 +300,7 @@ class WorldModel(nn.Module):
         multipliers; None: drawn under the conditions of `_q_mask` (train mode, `native_dropout`, cfg.dropout > 0, GPU), else no
         dropout."""
         assert return_type in {"min", "avg", "all"}
-        if self.cfg.multitask:
-            z = self.task_emb(z, task)
-        za = torch.cat([z, a], dim=-1)
+        za = self._net_in(z, task, a)
         q_mask = self._q_mask(self.cfg.num_q, za, q_mask)
         if self.native_autograd and za.is_cuda:
             out = autograd.ensemble_apply(self._Qs.params, za, q_mask)

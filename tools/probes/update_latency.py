@@ -13,10 +13,15 @@ median of the rounds and their spread.  Also recorded: the library calls of the 
 A step replayed from a graph is not measured: capturing the whole step is not part of the package.
 `--count-launches` is a run of its own: one `update(buffer)` with `native_draws` on under torch.profiler's device trace, the count of
 its device activities (kernels, copies and fills, the library's launches included) merged into the file the first run wrote.
+`--multitask` is the multitask arm, a file of its own: the `mt5` model (30 tasks, task_dim 64), H 3, B 256, the same flags and
+`native_draws` on, `native_task_emb` off and on toggled between rounds by the same protocol; with `--count-launches` the device
+activities of one step with the flag off and of one with it on.
 Measured, not gated: the script always exits 0.  MI355X box:
 
     python tools/probes/update_latency.py                    # writes profiles/update_latency.json
     python tools/probes/update_latency.py --count-launches   # adds the launches per step to it
+    python tools/probes/update_latency.py --multitask                    # writes profiles/update_latency_mt.json
+    python tools/probes/update_latency.py --multitask --count-launches   # adds both launch counts to it
 """
 import argparse
 import json
@@ -58,26 +63,29 @@ def _interleaved(fns, calls):
             for k, v in rounds.items()}
 
 
-def _buffer(cfg, dev):
+def _buffer(cfg, dev, episodes=8):
     from tdmpc2_amd import Buffer
 
     A, od = cfg.action_dim, cfg.obs_shape["state"][0]
     rng = np.random.default_rng(17)
     buf = Buffer(cfg, device=dev, seed=5)
-    for _ in range(8):
+    for e in range(episodes):
         T = 501
-        buf.add({"obs": torch.as_tensor(rng.standard_normal((T, od)).astype(np.float32)),
-                 "action": torch.as_tensor(rng.uniform(-1, 1, (T, A)).astype(np.float32)),
-                 "reward": torch.as_tensor(rng.standard_normal(T).astype(np.float32))})
+        td = {"obs": torch.as_tensor(rng.standard_normal((T, od)).astype(np.float32)),
+              "action": torch.as_tensor(rng.uniform(-1, 1, (T, A)).astype(np.float32)),
+              "reward": torch.as_tensor(rng.standard_normal(T).astype(np.float32))}
+        if cfg.multitask:  # one task per episode, every task of the set
+            td["task"] = torch.full((T,), e % len(cfg.tasks), dtype=torch.int64)
+        buf.add(td)
     return buf
 
 
-def _agent_and_buffer():
+def _agent_and_buffer(name="c2"):
     from tdmpc2_amd import TDMPC2
     from tdmpc2_amd.config import named_config
 
     dev = torch.device("cuda", 0)
-    cfg = named_config("c2", dropout=P, batch_size=B, buffer_size=10_000)
+    cfg = named_config(name, dropout=P, batch_size=B, buffer_size=20_000)
     torch.manual_seed(5)
     agent = TDMPC2(cfg, device=dev)
     with torch.no_grad():
@@ -85,7 +93,7 @@ def _agent_and_buffer():
             p.add_(torch.randn_like(p) * 0.02)
     agent.native_autograd = agent.native_refresh = agent.native_dropout = True
     agent.planner()
-    return agent, cfg, _buffer(cfg, dev)
+    return agent, cfg, _buffer(cfg, dev, len(cfg.tasks) if cfg.multitask else 8)
 
 
 def measure_update():
@@ -158,12 +166,95 @@ def count_launches():
             "most_frequent": [[k[:80], n] for k, n in names.most_common(12)]}
 
 
+UNIT_COUNTERS = ("LAYER_CALLS", "LOSS_CALLS", "PI_GRAD_CALLS", "DROPOUT_CALLS", "DRAW_CALLS", "TASK_CALLS")
+
+
+def measure_update_mt():
+    """The multitask step (`mt5`, H 3, B 256) with `native_task_emb` off and on, interleaved on one agent."""
+    from tdmpc2_amd import native
+
+    agent, cfg, buf = _agent_and_buffer("mt5")
+    agent.native_draws = True
+
+    def run(on):
+        def fn():
+            agent.native_task_emb = on
+            agent.update(buf)
+        return fn
+
+    ways = {"task_emb_off": run(False), "task_emb_on": run(True)}
+    res = _interleaved(ways, CALLS)
+    for k, fn in ways.items():
+        before = {n: getattr(native, n) for n in UNIT_COUNTERS}
+        fn()
+        torch.cuda.synchronize()
+        res["unit_calls_per_step_" + k] = {n: getattr(native, n) - before[n] for n in UNIT_COUNTERS}
+    res["task_emb_on_over_off"] = round(res["task_emb_on"]["median_us"] / res["task_emb_off"]["median_us"], 4)
+    res["shape"] = {"H": cfg.horizon, "B": B, "A": cfg.action_dim, "num_q": cfg.num_q, "mlp_dim": cfg.mlp_dim, "tasks": len(cfg.tasks),
+                    "task_dim": cfg.task_dim}
+    return res
+
+
+def count_launches_mt():
+    """Device activities of one eager multitask `update(buffer)` with `native_task_emb` off, then on (one agent, one process)."""
+    from collections import Counter
+
+    from torch.profiler import ProfilerActivity, profile
+
+    agent, _, buf = _agent_and_buffer("mt5")
+    agent.native_draws = True
+    out = {}
+    for key, on in (("task_emb_off", False), ("task_emb_on", True)):
+        agent.native_task_emb = on
+        for _ in range(WARM):
+            agent.update(buf)
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            agent.update(buf)
+            torch.cuda.synchronize()
+        names = Counter(e.name for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA)
+        copies = sum(n for k, n in names.items() if k.lower().startswith(("memcpy", "memset")) or "copybuffer" in k.lower() or "fillbuffer" in k.lower())
+        total = sum(names.values())
+        out[key] = {"device_activities": total, "of_which_copies_and_fills": copies, "kernels": total - copies,
+                    "task_unit_kernels": sum(n for k, n in names.items() if "k_task_" in k), "distinct_names": len(names),
+                    "most_frequent": [[k[:80], n] for k, n in names.most_common(12)]}
+    out["fewer_with_the_flag_on"] = out["task_emb_off"]["device_activities"] - out["task_emb_on"]["device_activities"]
+    return out
+
+
+def main_mt(a):
+    path = a.out or os.path.join(ROOT, "profiles", "update_latency_mt.json")
+    out = {}
+    if a.count_launches and os.path.exists(path):
+        with open(path) as f:
+            out = json.load(f)
+    key, fn = ("launches_of_one_update", count_launches_mt) if a.count_launches else ("update", measure_update_mt)
+    if not a.count_launches:
+        out = {"device": torch.cuda.get_device_name(0), "rounds": ROUNDS, "gated": False,
+               "per_round": f"{CALLS} back-to-back repetitions between two device events after {WARM} warm-ups, per repetition",
+               "graph_replay": "not measured: capturing the whole step is not part of the package"}
+    try:
+        out[key] = fn()
+    except Exception as e:  # measured, not gated
+        out[key] = {"not_measured": f"{type(e).__name__}: {str(e)[:300]}"}
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "update_latency.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--count-launches", action="store_true")
+    ap.add_argument("--multitask", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "the probe measures on the GPU: there is nothing to report without one"
+    if a.multitask:
+        return main_mt(a)
+    a.out = a.out or os.path.join(ROOT, "profiles", "update_latency.json")
     if a.count_launches:
         out = {}
         if os.path.exists(a.out):
