@@ -7,7 +7,9 @@ HIP; `mlp_apply` and `ensemble_apply` walk the modules of tdmpc2_amd/layers.py t
 are `update_pi` between its layers (tdmpc2_pigrad_*, include/tdmpc2_pi_grad.h): the Gaussian head after `_pi`'s MLP, and two_hot_inv of
 the two drawn Q heads, the running scale and the rho-weighted loss.  `TaskConcatFn` / `task_concat` are the task conditioning of a
 multitask model (tdmpc2_task_*, include/tdmpc2_task.h): the embedding lookup with max_norm and the concatenation [x | emb | a] that
-feeds a network's first layer, with their backward.  There is no fallback: a CPU tensor is an error.
+feeds a network's first layer, with their backward.  `PixelEncoderFn` / `pixel_encode` are the rgb encoder of `layers.conv`
+(tdmpc2_pixgrad_*, include/tdmpc2_pixel_grad.h): the batch route's forward with its activations kept, and the backward of the four
+convolutions.  There is no fallback: a CPU tensor is an error.
 """
 from __future__ import annotations
 
@@ -383,3 +385,86 @@ def task_concat(weight, ids, x, a=None, max_norm=1.0):
     desc = native.task_desc(steps, batch, ids.numel(), ids.element_size(), weight.shape[0], x.shape[-1], weight.shape[1],
                             0 if a is None else a.shape[-1], max_norm if max_norm is not None else 0.0)
     return TaskConcatFn.apply(weight, ids, x, a, desc)
+
+
+PIXEL_PASS_IMAGES = 256  # images per pass of a pixel_encode call that saves nothing for a backward
+
+
+class PixelEncoderFn(torch.autograd.Function):
+    """z = SimNorm(conv stack(preprocess(ShiftAug(obs)))) for obs [n, cin, 64, 64] (uint8 or fp32 pixel levels) under the integer
+    shifts `shift` int32 [n, 2], through tdmpc2_pixgrad_forward / tdmpc2_pixgrad_backward.  Saves obs, shift, the four weights and
+    `acts` (the post-ReLU outputs of layers 0..2 and z); the backward writes dW / db of the layers that need them.  obs and shift get
+    no gradient."""
+
+    @staticmethod
+    def forward(ctx, obs, shift, *params):
+        n, cin, C = int(obs.shape[0]), int(obs.shape[1]), int(params[0].shape[0])
+        desc = native.pixgrad_desc(n, cin, C, 0 if obs.dtype == torch.uint8 else 1)
+        tab = native.pixgrad_shift_table(obs.device)
+        Ws = [w.detach().contiguous() for w in params[0::2]]
+        bs = [b.detach().contiguous() for b in params[1::2]]
+        ab, fb, _ = native.pixgrad_workspace_bytes(desc)
+        acts = torch.empty(ab // 4, dtype=torch.float32, device=obs.device)  # torch's caching allocator
+        fwd_ws = torch.empty(fb // 4, dtype=torch.float32, device=obs.device)
+        native.pixgrad_forward(desc, obs, shift, tab, Ws, bs, fwd_ws, acts)
+        ctx.desc = desc
+        ctx.save_for_backward(obs, shift, tab, acts, *Ws)
+        return acts[acts.numel() - n * 16 * C:].view(n, 16 * C).clone()
+
+    @staticmethod
+    def backward(ctx, dz):
+        obs, shift, tab, acts, *Ws = ctx.saved_tensors
+        desc = ctx.desc
+        need = [ctx.needs_input_grad[2 + 2 * l] or ctx.needs_input_grad[3 + 2 * l] for l in range(4)]
+        dW = [torch.empty_like(w) if nd else None for w, nd in zip(Ws, need)]
+        db = [torch.empty(desc.C, dtype=torch.float32, device=dz.device) if nd else None for nd in need]
+        if any(need):
+            bwd_ws = torch.empty(native.pixgrad_workspace_bytes(desc)[2] // 4, dtype=torch.float32, device=dz.device)
+            native.pixgrad_backward(desc, obs, shift, tab, Ws, acts, dz.detach().to(torch.float32).contiguous(), bwd_ws, dW, db)
+        grads = []
+        for l in range(4):
+            grads += [dW[l] if ctx.needs_input_grad[2 + 2 * l] else None, db[l] if ctx.needs_input_grad[3 + 2 * l] else None]
+        return (None, None, *grads)
+
+
+def _pixel_params(seq):
+    convs = [seq[i] for i in (2, 4, 6, 8)] if len(seq) == 11 else []
+    ok = (len(convs) == 4 and isinstance(seq[0], layers.ShiftAug) and seq[0].pad == 3 and isinstance(seq[-1], layers.SimNorm)
+          and seq[-1].dim == 8 and all(type(m) is nn.Conv2d and m.bias is not None for m in convs)
+          and [(m.kernel_size[0], m.stride[0]) for m in convs] == [(7, 2), (5, 2), (3, 2), (3, 1)])
+    if not ok:
+        raise native.NativeError("pixel_encode: seq must be layers.conv(..., act=SimNorm(8)): ShiftAug(3), preprocess, Conv 7/2, 5/2, "
+                                 "3/2, 3/1 with ReLU between, Flatten, SimNorm(8)")
+    return [t for m in convs for t in (m.weight, m.bias)]
+
+
+def pixel_encode(seq, obs, shift, pass_images: int = PIXEL_PASS_IMAGES):
+    """`seq(obs)` for the `layers.conv` Sequential with ShiftAug's draw replaced by `shift` int32 [n, 2] (NativePlanner.draw_shift):
+    obs [n, cin, 64, 64], uint8 or floating pixel levels -> z [n, 16 C], differentiable in the four convolutions' parameters.  When
+    no gradient is needed (torch.no_grad, or no parameter requires one) nothing is saved and the call runs in passes of `pass_images`
+    images over one scratch buffer: rows are independent, so the bits are those of one pass.  There is no fallback: a CPU tensor is
+    an error."""
+    params = _pixel_params(seq)
+    if obs.device.type != "cuda":
+        raise native.NativeError(f"pixel_encode runs on an MI355X only (device {obs.device}); there is no CPU fallback")
+    if obs.dim() != 4 or tuple(obs.shape[2:]) != (64, 64):
+        raise native.NativeError(f"pixel_encode: obs [n, cin, 64, 64] (got {tuple(obs.shape)})")
+    if obs.dtype != torch.uint8:
+        obs = obs.to(torch.float32)
+    obs, shift = obs.contiguous(), shift.to(torch.int32).contiguous()
+    n = int(obs.shape[0])
+    if torch.is_grad_enabled() and any(t.requires_grad for t in params):
+        return PixelEncoderFn.apply(obs, shift, *params)
+    C, cin, step = int(params[0].shape[0]), int(obs.shape[1]), max(1, min(int(pass_images), n))
+    Ws, bs = [w.detach().contiguous() for w in params[0::2]], [b.detach().contiguous() for b in params[1::2]]
+    tab = native.pixgrad_shift_table(obs.device)
+    ab, fb, _ = native.pixgrad_workspace_bytes(native.pixgrad_desc(step, cin, C))
+    acts = torch.empty(ab // 4, dtype=torch.float32, device=obs.device)
+    fwd_ws = torch.empty(fb // 4, dtype=torch.float32, device=obs.device)
+    z = torch.empty((n, 16 * C), dtype=torch.float32, device=obs.device)
+    for e0 in range(0, n, step):
+        m = min(step, n - e0)
+        desc = native.pixgrad_desc(m, cin, C, 0 if obs.dtype == torch.uint8 else 1)
+        native.pixgrad_forward(desc, obs[e0:e0 + m], shift[e0:e0 + m], tab, Ws, bs, fwd_ws, acts)
+        z[e0:e0 + m] = acts[native.pixgrad_workspace_bytes(desc)[0] // 4 - m * 16 * C:][:m * 16 * C].view(m, 16 * C)
+    return z

@@ -21,8 +21,9 @@
 #   k_dropout.hip              dropout masks: Philox multipliers for the Q ensemble's first layer, its own C ABI and header (tdmpc2_dropout_*, include/tdmpc2_dropout.h)
 #   k_draw.hip                 draws of a training step: Philox normals and a pair of Q heads, its own C ABI and header (tdmpc2_draw_*, include/tdmpc2_draw.h)
 #   k_task.hip                 task conditioning: embedding renorm, [x | emb | a] gather and their backward, its own C ABI and header (tdmpc2_task_*, include/tdmpc2_task.h); no fp contraction
+#   k_pixel_grad.hip           pixel encoder in training: a forward that keeps its activations and the convolutions' backward, its own C ABI and header (tdmpc2_pixgrad_*, include/tdmpc2_pixel_grad.h)
 # Objects are cached under build/ and rebuilt when a source they include is newer (make-style), so an experiment on one
-# family recompiles one file.  TDMPC2_EXTRA_FLAGS (all units), TDMPC2_FLAGS_<unit> (one unit: main, fused, cluster, layered, policy, model, ploss, refresh, pixbatch, buffer, lgrad, optim, lossgrad, pigrad, dropout, draw, task),
+# family recompiles one file.  TDMPC2_EXTRA_FLAGS (all units), TDMPC2_FLAGS_<unit> (one unit: main, fused, cluster, layered, policy, model, ploss, refresh, pixbatch, buffer, lgrad, optim, lossgrad, pigrad, dropout, draw, task, pixgrad),
 # TDMPC2_ONLY_APAD=48 (experiment builds: the fused / cluster units of one padding only), TDMPC2_OUT, TDMPC2_BUILD_DIR, JOBS.
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
@@ -58,6 +59,7 @@ UNITS+=("pigrad|k_pi_grad.hip|${TDMPC2_FLAGS_pigrad:-}")  # policy loss seeds: u
 UNITS+=("dropout|k_dropout.hip|${TDMPC2_FLAGS_dropout:-}")  # dropout masks: Philox multipliers drawn on the device, its own C ABI (tdmpc2_dropout_*)
 UNITS+=("draw|k_draw.hip|${TDMPC2_FLAGS_draw:-}")  # draws of a training step: normals and a pair of Q heads drawn on the device, its own C ABI (tdmpc2_draw_*)
 UNITS+=("task|k_task.hip|-ffp-contract=off ${TDMPC2_FLAGS_task:-}")  # task conditioning: renorm, gather and backward, its own C ABI (tdmpc2_task_*); the renorm is separately rounded fp32 operations
+UNITS+=("pixgrad|k_pixel_grad.hip|${TDMPC2_FLAGS_pixgrad:-}")  # pixel encoder in training: stateless forward and backward, its own C ABI (tdmpc2_pixgrad_*)
 for ap in ${APADS}; do
     UNITS+=("fused${ap}|k_fused.hip|-DTU_APAD=${ap} ${TDMPC2_FLAGS_fused:-}")
     UNITS+=("cluster${ap}|k_cluster.hip|-DTU_APAD=${ap} ${TDMPC2_FLAGS_cluster:-}")
@@ -72,7 +74,7 @@ compile_unit() {  # name src flags
     [ -f "${obj}" ] || need=1
     [ -f "${stamp}" ] && [ "$(cat "${stamp}")" == "${want}" ] || need=1
     if [ "${need}" == 0 ]; then
-        for dep in "${HERE}"/*.hip "${HERE}"/*.cuh "${HERE}"/*.h "${HERE}/../../include/tdmpc2_plan.h" "${HERE}/../../include/tdmpc2_pi_grad.h" "${HERE}/../../include/tdmpc2_dropout.h" "${HERE}/../../include/tdmpc2_draw.h" "${HERE}/../../include/tdmpc2_task.h"; do
+        for dep in "${HERE}"/*.hip "${HERE}"/*.cuh "${HERE}"/*.h "${HERE}/../../include/tdmpc2_plan.h" "${HERE}/../../include/tdmpc2_pi_grad.h" "${HERE}/../../include/tdmpc2_dropout.h" "${HERE}/../../include/tdmpc2_draw.h" "${HERE}/../../include/tdmpc2_task.h" "${HERE}/../../include/tdmpc2_pixel_grad.h"; do
             if [ "${dep}" -nt "${obj}" ] && grep -q "$(basename "${dep}")" <(unit_deps "${src}"); then need=1; break; fi
         done
     fi

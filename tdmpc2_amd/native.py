@@ -164,6 +164,10 @@ class TaskDesc(C.Structure):  # struct tdmpc2_task_desc (include/tdmpc2_task.h)
                [("max_norm", C.c_float), ("reserved", C.c_uint32)]
 
 
+class PixGradDesc(C.Structure):  # struct tdmpc2_pixgrad_desc (include/tdmpc2_pixel_grad.h)
+    _fields_ = [(n, C.c_int32) for n in ("n", "cin", "C", "obs_dtype", "seed_is_preact")] + [("reserved", C.c_uint32)]
+
+
 class Debug(C.Structure):
     _fields_ = [("value", C.c_void_p), ("elite_idx", C.c_void_p), ("score", C.c_void_p), ("mean", C.c_void_p),
                 ("std", C.c_void_p), ("actions", C.c_void_p)]
@@ -259,13 +263,18 @@ _DRAW_H = {"tdmpc2_draw_noise": [_P(DrawDesc), _vp, _vp, _vp, _vp]}
 # include/tdmpc2_task.h: the task unit (embedding renorm, the [x | emb | a] gather and their backward), a header of its own too
 _TASK_H = {"tdmpc2_task_forward": [_P(TaskDesc)] + [_vp] * 6, "tdmpc2_task_backward": [_P(TaskDesc)] + [_vp] * 6,
            "tdmpc2_task_renorm": [_P(TaskDesc)] + [_vp] * 3}
+# include/tdmpc2_pixel_grad.h: the pixel encoder in training (a forward that keeps its activations, the convolutions' backward)
+_PIXEL_GRAD_H = {"tdmpc2_pixgrad_workspace_bytes": [_P(PixGradDesc), _P(_sz), _P(_sz), _P(_sz)],
+                 "tdmpc2_pixgrad_shift_table": [_vp],
+                 "tdmpc2_pixgrad_forward": [_P(PixGradDesc)] + [_vp] * 8, "tdmpc2_pixgrad_backward": [_P(PixGradDesc)] + [_vp] * 10}
 PROTOTYPES = {"tdmpc2_plan.h": _PLAN_H, "tdmpc2_pi_grad.h": _PI_GRAD_H, "tdmpc2_dropout.h": _DROPOUT_H,
-              "tdmpc2_draw.h": _DRAW_H, "tdmpc2_task.h": _TASK_H}  # by header under include/
+              "tdmpc2_draw.h": _DRAW_H, "tdmpc2_task.h": _TASK_H, "tdmpc2_pixel_grad.h": _PIXEL_GRAD_H}  # by header under include/
 ABI_SYMBOLS = list(_PLAN_H)  # every symbol include/tdmpc2_plan.h declares (tests check the .so exports all of them)
 PI_GRAD_SYMBOLS = tuple(_PI_GRAD_H)
 DROPOUT_SYMBOLS = tuple(_DROPOUT_H)
 DRAW_SYMBOLS = tuple(_DRAW_H)
 TASK_SYMBOLS = tuple(_TASK_H)
+PIXEL_GRAD_SYMBOLS = tuple(_PIXEL_GRAD_H)
 
 
 def signature(sig):
@@ -1400,7 +1409,7 @@ def layer_desc(kind: int, groups: int, rows: int, in_dim: int, out_dim: int, sha
 
 
 _UNIT_COUNTER = dict(layer="LAYER_CALLS", loss="LOSS_CALLS", pigrad="PI_GRAD_CALLS", dropout="DROPOUT_CALLS",
-                     draw="DRAW_CALLS", task="TASK_CALLS")
+                     draw="DRAW_CALLS", task="TASK_CALLS", pixgrad="PIXEL_GRAD_CALLS")
 
 
 def _unit_check(tag: str, rc: int):
@@ -1409,7 +1418,7 @@ def _unit_check(tag: str, rc: int):
 
 
 def _unit_call(tag: str, symbol: str, desc, first, want, tail, **ts):
-    """The one call path of the stateless units (layer, loss, pigrad, dropout, draw, task): `first` names the device; every tensor of `ts` (the
+    """The one call path of the stateless units (layer, loss, pigrad, dropout, draw, task, pixgrad): `first` names the device; every tensor of `ts` (the
     C order after the descriptor; None = absent, a c_void_p = a pointer its caller has checked) is contiguous fp32 on it and holds
     what `want` (name -> element count, or None: the library sees pointers only) asks for; then the unit's counter, the call on the
     current stream with `tail` between the tensors and the stream, and the library's error."""
@@ -1746,3 +1755,98 @@ def task_renorm(desc: TaskDesc, table, ids):
     """tdmpc2_task_renorm on the current stream: the forward's renorm alone."""
     _unit_call("task", "tdmpc2_task_renorm", desc, table, _task_want(desc), (), table=table,
                ids=_task_ids("task_renorm", desc, ids, table.device))
+
+
+# ---------------------------------------------------------------- pixel encoder in training (tdmpc2_pixgrad_*, include/tdmpc2_pixel_grad.h)
+PIXEL_GRAD_CALLS = 0  # library calls made through the wrappers below (forward + backward), kept like TASK_CALLS
+PIX_HW = (841, 169, 36, 16)      # output pixels of layers 0..3
+PIX_KERNEL = (7, 5, 3, 3)
+_PIX_TABLES = {}                 # device -> the uploaded ShiftAug tap table
+
+
+def pixgrad_desc(n: int, cin: int, channels: int, obs_dtype: int = 0, seed_is_preact: bool = False) -> PixGradDesc:
+    """n images [cin, 64, 64] (obs_dtype 0 uint8, 1 fp32) through the encoder of `channels` channels; seed_is_preact: the backward
+    takes dz as the gradient of layer 3's pre-activation and skips the SimNorm backward."""
+    return PixGradDesc(n=int(n), cin=int(cin), C=int(channels), obs_dtype=int(obs_dtype), seed_is_preact=int(bool(seed_is_preact)),
+                       reserved=0)
+
+
+def pixgrad_workspace_bytes(desc: PixGradDesc):
+    """-> (acts_bytes, fwd_ws_bytes, bwd_ws_bytes) of tdmpc2_pixgrad_workspace_bytes."""
+    a, f, b = C.c_size_t(), C.c_size_t(), C.c_size_t()
+    _unit_check("pixgrad", load_library().tdmpc2_pixgrad_workspace_bytes(C.byref(desc), C.byref(a), C.byref(f), C.byref(b)))
+    return int(a.value), int(f.value), int(b.value)
+
+
+def pixgrad_shift_table(device) -> torch.Tensor:
+    """ShiftAug's 7 x 64 tap table (tdmpc2_pixgrad_shift_table) on `device` as int32 [7, 64, 4] (two indices and the bit patterns of
+    two fp32 weights per entry): filled on the host, uploaded once per device and cached."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise NativeError(f"pixgrad_shift_table: the table lives on an MI355X (device {device}); there is no CPU fallback")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if device not in _PIX_TABLES:
+        host = torch.empty((7, 64, 4), dtype=torch.int32)
+        _unit_check("pixgrad", load_library().tdmpc2_pixgrad_shift_table(C.c_void_p(host.data_ptr())))
+        _PIX_TABLES[device] = host.to(device)
+    return _PIX_TABLES[device]
+
+
+def _pixgrad_obs(what: str, desc: PixGradDesc, obs, shift, tab):
+    dev = obs.device
+    want = torch.uint8 if desc.obs_dtype == 0 else torch.float32
+    if obs.dtype != want or tuple(obs.shape) != (desc.n, desc.cin, 64, 64) or not obs.is_contiguous():
+        raise NativeError(f"{what}: obs must be a contiguous {want} [{desc.n}, {desc.cin}, 64, 64] tensor (got {obs.dtype}, "
+                          f"{tuple(obs.shape)})")
+    if shift.dtype != torch.int32 or tuple(shift.shape) != (desc.n, 2) or not shift.is_contiguous() or shift.device != dev:
+        raise NativeError(f"{what}: shift must be a contiguous int32 [{desc.n}, 2] tensor on {dev}")
+    if tab.dtype != torch.int32 or tab.numel() != 7 * 64 * 4 or not tab.is_contiguous() or tab.device != dev:
+        raise NativeError(f"{what}: tab must be pixgrad_shift_table({dev})")
+    return _ptr(obs), _ptr(shift), _ptr(tab)
+
+
+def _pixgrad_four(what: str, desc: PixGradDesc, ts, weights: bool, device, optional: bool = False):
+    """Four per-layer tensors as a host array of device pointers -> (c_void_p of the array, the array to keep alive)."""
+    arr = (C.c_void_p * 4)()
+    for l, t in enumerate(ts):
+        if t is None and optional:
+            continue
+        cin_l = desc.cin if l == 0 else desc.C
+        count = desc.C * cin_l * PIX_KERNEL[l] ** 2 if weights else desc.C
+        if t is None or t.device != device or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != count:
+            raise NativeError(f"{what}: layer {l} needs a contiguous fp32 tensor of {count} floats on {device}")
+        arr[l] = t.data_ptr()
+    return C.cast(arr, C.c_void_p), arr
+
+
+def pixgrad_forward(desc: PixGradDesc, obs, shift, tab, W, b, fwd_ws, acts):
+    """tdmpc2_pixgrad_forward on the current stream: W / b the four Conv2d weights and biases, fwd_ws and acts fp32 tensors of at least
+    the sizes of pixgrad_workspace_bytes; acts is written (the outputs of layers 0..2 per image, then z [n, 16 C])."""
+    what, dev = "pixgrad_forward", acts.device
+    ab, fb, _ = pixgrad_workspace_bytes(desc)
+    if _nbytes(acts) < ab or _nbytes(fwd_ws) < fb:
+        raise NativeError(f"{what}: acts / fwd_ws hold {_nbytes(acts)} / {_nbytes(fwd_ws)} bytes, {ab} / {fb} needed")
+    po, ps, pt = _pixgrad_obs(what, desc, obs, shift, tab) if dev.type == "cuda" else (None, None, None)
+    Wp, keep_w = _pixgrad_four(what, desc, W, True, dev)
+    bp, keep_b = _pixgrad_four(what, desc, b, False, dev)
+    _unit_call("pixgrad", "tdmpc2_pixgrad_forward", desc, acts, None, (), obs=po, shift=ps, tab=pt, W=Wp, b=bp, fwd_ws=fwd_ws, acts=acts)
+    del keep_w, keep_b
+
+
+def pixgrad_backward(desc: PixGradDesc, obs, shift, tab, W, acts, dz, bwd_ws, dW, db):
+    """tdmpc2_pixgrad_backward on the current stream: dW / db are lists of four tensors or None (a layer's pair is given or None
+    together); bwd_ws an fp32 tensor of at least pixgrad_workspace_bytes(desc)[2] bytes."""
+    what, dev = "pixgrad_backward", acts.device
+    ab, _, bb = pixgrad_workspace_bytes(desc)
+    if _nbytes(acts) < ab or _nbytes(bwd_ws) < bb:
+        raise NativeError(f"{what}: acts / bwd_ws hold {_nbytes(acts)} / {_nbytes(bwd_ws)} bytes, {ab} / {bb} needed")
+    if dz.numel() != desc.n * 16 * desc.C:
+        raise NativeError(f"{what}: dz holds {dz.numel()} floats, the descriptor asks for {desc.n * 16 * desc.C}")
+    po, ps, pt = _pixgrad_obs(what, desc, obs, shift, tab) if dev.type == "cuda" else (None, None, None)
+    Wp, keep_w = _pixgrad_four(what, desc, W, True, dev)
+    dWp, keep_dw = _pixgrad_four(what, desc, dW, True, dev, optional=True)
+    dbp, keep_db = _pixgrad_four(what, desc, db, False, dev, optional=True)
+    _unit_call("pixgrad", "tdmpc2_pixgrad_backward", desc, acts, None, (), obs=po, shift=ps, tab=pt, W=Wp, acts=acts, dz=dz,
+               bwd_ws=bwd_ws, dW=dWp, db=dbp)
+    del keep_w, keep_dw, keep_db

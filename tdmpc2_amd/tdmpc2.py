@@ -115,6 +115,16 @@ class TDMPC2(torch.nn.Module):
         self.model.native_task_emb = bool(on)
 
     @property
+    def native_pixel_grad(self) -> bool:
+        """True: on a single-task rgb model `model.encode` runs the convolutional encoder through the library's pixel unit, forward
+        and backward (WorldModel.native_pixel_grad).  `native_pixel_encoder` and its handle routes do not read the flag."""
+        return self.model.native_pixel_grad
+
+    @native_pixel_grad.setter
+    def native_pixel_grad(self, on: bool):
+        self.model.native_pixel_grad = bool(on)
+
+    @property
     def draws(self):
         """The draw stream of the training step (autograd.Draws keyed by cfg.seed), made on this device at first use."""
         if self._draws is None:

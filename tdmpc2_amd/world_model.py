@@ -105,6 +105,11 @@ class WorldModel(nn.Module):
         # input [x | task_emb | a] with one library call each (autograd.task_concat, tdmpc2_task_forward: the max_norm renorm, the
         # lookup and the concatenations; its backward in tdmpc2_task_backward); off by default -- nn.Embedding and torch.cat
         self.native_task_emb = False
+        # True (cfg.obs == "rgb", single-task, the input on the GPU): encode runs the convolutional encoder through the library's
+        # pixel unit (autograd.pixel_encode, tdmpc2_pixgrad_forward / tdmpc2_pixgrad_backward), so loss.backward() computes the
+        # encoder's gradients in HIP; ShiftAug's shifts are drawn with the module's own torch.randint call, one draw per time step;
+        # off by default -- the nn.Sequential (MIOpen convolutions, grid_sample)
+        self.native_pixel_grad = False
         self._log_std_host = None  # host copies of log_std_min / log_std_dif for the library's policy head (made at first use)
         self.apply(self._weight_init)
         self._register_state_dict_hook(self._add_meta_keys)
@@ -183,11 +188,24 @@ class WorldModel(nn.Module):
         """reference world_model.py:103-112, including the [T, B, C, H, W] pixel-sequence branch."""
         if self.cfg.multitask:  # (rgb observations keep the module's lookup)
             obs = self._net_in(obs, task) if self.cfg.obs == "state" else self.task_emb(obs, task)
+        if self.native_pixel_grad and self.cfg.obs == "rgb" and not self.cfg.multitask and obs.is_cuda:
+            return self._encode_pixels(obs)
         if self.cfg.obs == "rgb" and obs.ndim == 5:
             return torch.stack([self._encoder[self.cfg.obs](o) for o in obs])
         if self.cfg.obs == "state":
             return self._mlp(self._encoder[self.cfg.obs], obs)
         return self._encoder[self.cfg.obs](obs)
+
+    def _encode_pixels(self, obs):
+        """encode of rgb observations in the library: [n, C, H, W], or the [T, B, C, H, W] sequence branch as ONE call over T B
+        images; the shifts are the module's draws in the module's order (one torch.randint call per time step)."""
+        from .native import NativePlanner
+        seq = self._encoder[self.cfg.obs]
+        if obs.ndim == 5:
+            T, B = int(obs.shape[0]), int(obs.shape[1])
+            shift = torch.cat([NativePlanner.draw_shift(B, obs.device) for _ in range(T)])
+            return autograd.pixel_encode(seq, obs.reshape(T * B, *obs.shape[2:]), shift).view(T, B, -1)
+        return autograd.pixel_encode(seq, obs, NativePlanner.draw_shift(int(obs.shape[0]), obs.device))
 
     def next(self, z, a, task):
         return self._mlp(self._dynamics, self._net_in(z, task, a))

@@ -16,12 +16,16 @@ its device activities (kernels, copies and fills, the library's launches include
 `--multitask` is the multitask arm, a file of its own: the `mt5` model (30 tasks, task_dim 64), H 3, B 256, the same flags and
 `native_draws` on, `native_task_emb` off and on toggled between rounds by the same protocol; with `--count-launches` the device
 activities of one step with the flag off and of one with it on.
+`--rgb` is the rgb arm, a file of its own: the 5M model on 9 x 64 x 64 uint8 frame stacks (C 32), H 3, B 256, the same flags and
+`native_draws` on, `native_pixel_grad` off (MIOpen convolutions and grid_sample under autograd) and on (the pixel unit, forward and
+backward) toggled between rounds by the same protocol.
 Measured, not gated: the script always exits 0.  MI355X box:
 
     python tools/probes/update_latency.py                    # writes profiles/update_latency.json
     python tools/probes/update_latency.py --count-launches   # adds the launches per step to it
     python tools/probes/update_latency.py --multitask                    # writes profiles/update_latency_mt.json
     python tools/probes/update_latency.py --multitask --count-launches   # adds both launch counts to it
+    python tools/probes/update_latency.py --rgb                          # writes profiles/update_latency_rgb.json
 """
 import argparse
 import json
@@ -222,6 +226,62 @@ def count_launches_mt():
     return out
 
 
+def measure_update_rgb():
+    """The rgb step (5M model, 9 x 64 x 64 uint8 frames, H 3, B 256) with `native_pixel_grad` off and on, interleaved on one agent."""
+    from tdmpc2_amd import TDMPC2, Buffer, native
+    from tdmpc2_amd.config import named_config
+
+    dev = torch.device("cuda", 0)
+    cfg = named_config("c2", dropout=P, batch_size=B, buffer_size=2_000)
+    cfg.obs, cfg.obs_shape, cfg.num_channels, cfg.latent_dim = "rgb", {"rgb": (9, 64, 64)}, 32, 512
+    torch.manual_seed(5)
+    agent = TDMPC2(cfg, device=dev)
+    agent.native_autograd = agent.native_refresh = agent.native_dropout = agent.native_draws = True
+    agent.planner()
+    rng = np.random.default_rng(17)
+    buf = Buffer(cfg, device=dev, seed=5)
+    for _ in range(8):
+        T = 101
+        buf.add({"obs": torch.as_tensor(rng.integers(0, 256, (T, 9, 64, 64), dtype=np.uint8)),
+                 "action": torch.as_tensor(rng.uniform(-1, 1, (T, cfg.action_dim)).astype(np.float32)),
+                 "reward": torch.as_tensor(rng.standard_normal(T).astype(np.float32))})
+
+    def run(on):
+        def fn():
+            agent.native_pixel_grad = on
+            agent.update(buf)
+        return fn
+
+    ways = {"pixel_grad_off": run(False), "pixel_grad_on": run(True)}
+    res = _interleaved(ways, CALLS)
+    counters = UNIT_COUNTERS + ("PIXEL_GRAD_CALLS",)
+    for k, fn in ways.items():
+        before = {n: getattr(native, n) for n in counters}
+        fn()
+        torch.cuda.synchronize()
+        res["unit_calls_per_step_" + k] = {n: getattr(native, n) - before[n] for n in counters}
+    res["pixel_grad_on_over_off"] = round(res["pixel_grad_on"]["median_us"] / res["pixel_grad_off"]["median_us"], 4)
+    res["shape"] = {"H": cfg.horizon, "B": B, "A": cfg.action_dim, "C": 32, "cin": 9, "frames_per_step": (cfg.horizon + 1) * B}
+    return res
+
+
+def main_rgb(a):
+    path = a.out or os.path.join(ROOT, "profiles", "update_latency_rgb.json")
+    out = {"device": torch.cuda.get_device_name(0), "rounds": ROUNDS, "gated": False,
+           "per_round": f"{CALLS} back-to-back repetitions between two device events after {WARM} warm-ups, per repetition",
+           "graph_replay": "not measured: capturing the whole step is not part of the package"}
+    try:
+        out["update"] = measure_update_rgb()
+    except Exception as e:  # measured, not gated
+        out["update"] = {"not_measured": f"{type(e).__name__}: {str(e)[:300]}"}
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+    return 0
+
+
 def main_mt(a):
     path = a.out or os.path.join(ROOT, "profiles", "update_latency_mt.json")
     out = {}
@@ -250,8 +310,11 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--count-launches", action="store_true")
     ap.add_argument("--multitask", action="store_true")
+    ap.add_argument("--rgb", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "the probe measures on the GPU: there is nothing to report without one"
+    if a.rgb:
+        return main_rgb(a)
     if a.multitask:
         return main_mt(a)
     a.out = a.out or os.path.join(ROOT, "profiles", "update_latency.json")
