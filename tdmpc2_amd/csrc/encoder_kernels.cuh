@@ -114,6 +114,10 @@ __global__ __launch_bounds__(ENC_THREADS) void k_encode(EncodeParams p) {
 // 256 contiguous bytes of the transposed weights per wave and k) and k_enc_norm (grid E: LayerNorm + Mish / SimNorm of
 // the row).
 constexpr int ENC_WIDE = 1024;
+// k_enc_gemv holds the whole input row plus its partials in dynamic LDS, (in + 256) floats, and a launch may ask for 64 KiB of
+// it: the widest input a layer may have.  Only an observation can be wider than a layer (4096), so this is a limit on obs_dim.
+constexpr size_t ENC_GEMV_LDS_MAX = 64 * 1024;
+constexpr int ENC_MAX_IN = (int)(ENC_GEMV_LDS_MAX / 4) - 256;
 
 struct EncGemvParams {
     const float *wt, *bias;  // [in][out], [out]

@@ -941,6 +941,9 @@ int ensure_layer_alloc(tdmpc2_plan *h, int net, int layer, const LayerShape &sh)
 int ensure_enc_alloc(tdmpc2_plan *h, int layer, int in_features, int out_features) {
     const tdmpc2_plan_cfg &c = h->cfg;
     tdmpc2_plan::Enc &L = h->enc[layer];
+    if (in_features > ENC_MAX_IN)  // binds and packed blobs both come through here, before anything is allocated or enqueued
+        return fail(TDMPC2_ERR_UNSUPPORTED, "encoder layer %d: %d inputs, at most %d (a layer's input row is held in %zu bytes of LDS)",
+                    layer, in_features, ENC_MAX_IN, ENC_GEMV_LDS_MAX);
     if (L.wt && (L.in != in_features || L.out != out_features))
         return fail(TDMPC2_ERR_STATE, "encoder layer %d re-bound with a different shape", layer);
     int rc;
@@ -1109,6 +1112,9 @@ int launch_encode(tdmpc2_plan *h, int E, const float *obs, int obs_dim, const fl
         if (!L.bound) return fail(TDMPC2_ERR_STATE, "encoder layer %d of %d is not bound", l, h->enc_layers);
         const int exp_in = l == 0 ? obs_dim + c.task_dim : h->enc[l - 1].out;
         if (L.in != exp_in) return fail(TDMPC2_ERR_INVALID, "encoder layer %d takes %d inputs, the data brings %d", l, L.in, exp_in);
+        if (L.in > ENC_MAX_IN)  // checked for every layer before the first launch
+            return fail(TDMPC2_ERR_UNSUPPORTED, "encoder layer %d: %d inputs, at most %d (a layer's input row is held in %zu bytes of LDS)",
+                        l, L.in, ENC_MAX_IN, ENC_GEMV_LDS_MAX);
         p.l[l] = EncLayerDev{L.wt, L.bias, L.g, L.b, L.in, L.out};
         maxw = std::max(maxw, std::max(L.in, L.out));
     }
