@@ -1,8 +1,14 @@
 #!/bin/bash
 # Build the planner's C-ABI shared library for gfx950 (cross-compiles without a GPU).
-# One translation unit per kernel family (and, for the fused 512-wide family, per action padding), compiled in parallel and
-# linked into ONE libtdmpc2_plan.so:
-#   tdmpc2_plan.hip            C ABI, handle (its sizes: plan_layout.h), job tables of the weight packer, refit, encoder, host side of the fused family
+# Five host units (the C ABI of include/tdmpc2_plan.h) and one translation unit per kernel family (for the fused 512-wide family,
+# per action padding), compiled in parallel and linked into ONE libtdmpc2_plan.so:
+#   plan_core.hip              host: error reporting, handle create / destroy (sizes: plan_layout.h), guards, allocations, fault recovery, tuning, profiling
+#   plan_weights.hip           host: binds, job tables of the weight packer, refresh / soft update, packed blob
+#   plan_run.hip               host: planning -- host side of the fused family, run / estimate_value / refit, sharded plans, noise export
+#   plan_obs.hip               host: state and pixel encoders, policy prior (encode, run_obs, run_pix, pix_batch, pi, act_pi)
+#   plan_train.hip             host: policy_value / td_target, model rollout and losses, policy loss (what they share: plan_host.h)
+#   k_plan.hip                 kernels outside the families: k_refit (elite selection + refit), ks_task_bias, state encoder (k_encode / k_enc_gemv / k_enc_norm),
+#                              pixel encoder's planning routes (k_pix_image / k_pix_spread / k_pix_pack), k_export_noise
 #   k_fused.hip   x {16,32,48,64}   ks_setup / ks_pitraj / ks_rollout / ks_value
 #   k_cluster.hip x {16,32,48,64}   ks_rollout_cl
 #   k_layered.hip              layered GEMMs + row kernels + their host orchestration
@@ -23,8 +29,8 @@
 #   k_task.hip                 task conditioning: embedding renorm, [x | emb | a] gather and their backward, its own C ABI and header (tdmpc2_task_*, include/tdmpc2_task.h); no fp contraction
 #   k_pixel_grad.hip           pixel encoder in training: a forward that keeps its activations and the convolutions' backward, its own C ABI and header (tdmpc2_pixgrad_*, include/tdmpc2_pixel_grad.h)
 # Objects are cached under build/ and rebuilt when a source they include is newer (make-style), so an experiment on one
-# family recompiles one file.  TDMPC2_EXTRA_FLAGS (all units), TDMPC2_FLAGS_<unit> (one unit: main, fused, cluster, layered, policy, model, ploss, refresh, pixbatch, buffer, lgrad, optim, lossgrad, pigrad, dropout, draw, task, pixgrad),
-# TDMPC2_ONLY_APAD=48 (experiment builds: the fused / cluster units of one padding only), TDMPC2_OUT, TDMPC2_BUILD_DIR, JOBS.
+# family recompiles one file.  TDMPC2_EXTRA_FLAGS (all units), TDMPC2_FLAGS_<unit> (one unit: main = the five host units plan_*.hip, plank, fused, cluster, layered, policy, model, ploss, refresh, pixbatch, buffer, lgrad, optim, lossgrad, pigrad, dropout, draw, task, pixgrad),
+# TDMPC2_ONLY_APAD=48 (experiment builds: the fused / cluster / model / policy-loss units of one padding only; reaches plan_core.hip, whose *_ops(apad) accessors then name that padding alone), TDMPC2_OUT, TDMPC2_BUILD_DIR, JOBS.
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 OUT="${TDMPC2_OUT:-${HERE}/../libtdmpc2_plan.so}"
@@ -39,10 +45,17 @@ ONLY=""
 
 # unit name | source | extra flags
 UNITS=()
-UNITS+=("main|tdmpc2_plan.hip|${ONLY} ${TDMPC2_FLAGS_main:-}")
-# the C-ABI unit once more with the test hooks compiled in (TDMPC2_CLUSTER_FAULT, TDMPC2_DEBUG_NO_TURN, TDMPC2_POISON): linked with the
-# SAME kernel objects into libtdmpc2_plan_hooks.so, which only the GPU tests of the fault paths load (tdmpc2_amd/native.py)
-[ -z "${TDMPC2_NO_HOOKS_LIB:-}" ] && UNITS+=("main_hooks|tdmpc2_plan.hip|${ONLY} -DTDMPC2_TEST_HOOKS ${TDMPC2_FLAGS_main:-}")
+# the host units (no kernels, no launches: everything goes through launch.h)
+UNITS+=("core|plan_core.hip|${ONLY} ${TDMPC2_FLAGS_main:-}")
+# plan_core.hip once more with the test hooks compiled in (TDMPC2_CLUSTER_FAULT, TDMPC2_DEBUG_NO_TURN, TDMPC2_POISON; every use of the
+# macro is in that unit): libtdmpc2_plan_hooks.so is the product's objects with this one in place of core.o, and only the GPU tests
+# of the fault paths load it (tdmpc2_amd/native.py)
+[ -z "${TDMPC2_NO_HOOKS_LIB:-}" ] && UNITS+=("core_hooks|plan_core.hip|${ONLY} -DTDMPC2_TEST_HOOKS ${TDMPC2_FLAGS_main:-}")
+UNITS+=("weights|plan_weights.hip|${TDMPC2_FLAGS_main:-}")
+UNITS+=("run|plan_run.hip|${TDMPC2_FLAGS_main:-}")
+UNITS+=("obs|plan_obs.hip|${TDMPC2_FLAGS_main:-}")
+UNITS+=("train|plan_train.hip|${TDMPC2_FLAGS_main:-}")
+UNITS+=("plank|k_plan.hip|${TDMPC2_FLAGS_plank:-}")
 UNITS+=("layered|k_layered.hip|${TDMPC2_FLAGS_layered:-}")
 UNITS+=("policy|k_policy.hip|${TDMPC2_FLAGS_policy:-}")
 UNITS+=("model|k_model.hip|${TDMPC2_FLAGS_model:-}")
@@ -101,9 +114,9 @@ printf '%s\n' "${UNITS[@]}" | xargs -P "${JOBS}" -I{} bash -c 'IFS="|" read -r n
 OBJS=(); HOBJS=()
 for u in "${UNITS[@]}"; do
     n="${u%%|*}"
-    [ "$n" == "main_hooks" ] && { HOBJS+=("${BUILD}/$n.o"); continue; }
+    [ "$n" == "core_hooks" ] && { HOBJS+=("${BUILD}/$n.o"); continue; }
     OBJS+=("${BUILD}/$n.o")
-    [ "$n" != "main" ] && HOBJS+=("${BUILD}/$n.o")
+    [ "$n" != "core" ] && HOBJS+=("${BUILD}/$n.o")
 done
 "${HIPCC}" --offload-arch=gfx950 -shared -fPIC -o "${OUT}" "${OBJS[@]}"
 echo "built ${OUT}"

@@ -2,7 +2,7 @@
 // helpers (math, Philox, the elite refit) that more than one kernel family uses.  Types live in namespace tdk so that
 // launcher functions defined in one translation unit can be called from another; the kernels themselves stay in the
 // anonymous namespace of the ONE translation unit that instantiates them (k_fused.hip, k_cluster.hip, k_layered.hip,
-// tdmpc2_plan.hip), which is what lets build.sh compile the families in parallel and an experiment rebuild one of them.
+// k_plan.hip ...), which is what lets build.sh compile the families in parallel and an experiment rebuild one of them.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -4,27 +4,13 @@
 // FLOPs; it is here so that a planning step is obs -> action inside the library (no framework launches in between),
 // not for its arithmetic: plain fp32 FMAs, thread = output feature, weights stored transposed ([in][out]) at bind
 // time so that a wave reads 256 contiguous bytes per k.
-// Included by tdmpc2_plan.hip inside its anonymous namespace.
+// Included by k_plan.hip inside its anonymous namespace; the limits and parameter blocks are encoder_params.h's (via launch.h).
 #pragma once
 
-constexpr int ENC_MAX_LAYERS = 6;    // num_enc_layers is 2..5 in the reference's model table (common/__init__.py:1-24)
-constexpr int ENC_THREADS = 512;
-constexpr int ENC_MAX_PER_THREAD = 8;  // output features per thread: widths up to 4096 (the 317M model's enc_dim)
-
-struct EncLayerDev {
-    const float *wt;    // [in][out], transposed nn.Linear weight
-    const float *bias;  // [out]
-    const float *g, *b; // LayerNorm affine [out]
-    int in, out;
-};
-struct EncodeParams {
-    EncLayerDev l[ENC_MAX_LAYERS];
-    int nl;
-    int obs_dim, T, maxw, simnorm_dim;
-    const float *obs;       // [E, obs_dim]
-    const float *task_emb;  // [E, T] or null
-    float *z;               // [E, latent_dim]
-};
+// The kernels' own names for the blocks of encoder_params.h (launch.h: "kernel parameter types").
+struct EncodeParams : EncodeArgs {};
+struct EncGemvParams : EncGemvArgs {};
+struct EncNormParams : EncNormArgs {};
 
 __device__ __forceinline__ float enc_block_sum(float v, float *red) {
     // all threads get the sum over the workgroup
@@ -112,22 +98,7 @@ __global__ __launch_bounds__(ENC_THREADS) void k_encode(EncodeParams p) {
 // stream up to 225 MB of weights through a single CU (measured 9.9 ms for the 317M encoder), so each layer becomes two
 // launches: k_enc_gemv (grid: out / 64 x E; the four waves of a workgroup split the contraction, lane = output feature,
 // 256 contiguous bytes of the transposed weights per wave and k) and k_enc_norm (grid E: LayerNorm + Mish / SimNorm of
-// the row).
-constexpr int ENC_WIDE = 1024;
-// k_enc_gemv holds the whole input row plus its partials in dynamic LDS, (in + 256) floats, and a launch may ask for 64 KiB of
-// it: the widest input a layer may have.  Only an observation can be wider than a layer (4096), so this is a limit on obs_dim.
-constexpr size_t ENC_GEMV_LDS_MAX = 64 * 1024;
-constexpr int ENC_MAX_IN = (int)(ENC_GEMV_LDS_MAX / 4) - 256;
-
-struct EncGemvParams {
-    const float *wt, *bias;  // [in][out], [out]
-    const float *x;          // [E, ldx] activations (layer 0: obs | task_emb assembled by the caller kernel)
-    const float *obs, *emb;  // layer 0 only: obs [E, obs_dim], emb [E, T] (x = null)
-    int obs_dim, T;
-    int in, out, ldx;
-    float *y;                // [E, out] pre-activations
-};
-
+// the row).  (ENC_WIDE, ENC_GEMV_LDS_MAX, ENC_MAX_IN: encoder_params.h)
 __global__ __launch_bounds__(256) void k_enc_gemv(EncGemvParams p) {
     extern __shared__ float enc_lds[];  // x row [in] + partials [4][64]
     float *xs = enc_lds, *part = enc_lds + p.in;
@@ -158,13 +129,6 @@ __global__ __launch_bounds__(256) void k_enc_gemv(EncGemvParams p) {
     if (wave == 0 && f < p.out)
         p.y[(size_t)e * p.out + f] = ((part[lane] + part[64 + lane]) + (part[128 + lane] + part[192 + lane])) + p.bias[f];
 }
-
-struct EncNormParams {
-    const float *y;      // [E, width] pre-activations
-    const float *g, *b;  // [width]
-    float *out;          // [E, width]: Mish(LN(y)) (hidden layers) or SimNorm(LN(y)) (last layer = z)
-    int width, last, simnorm_dim;
-};
 
 __global__ __launch_bounds__(ENC_THREADS) void k_enc_norm(EncNormParams p) {
     __shared__ float red[ENC_THREADS / 64];

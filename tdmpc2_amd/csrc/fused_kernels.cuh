@@ -19,7 +19,8 @@
 // rows, which makes the LayerNorm / activation / hi-lo-split epilogue register resident (no fp32 staging pass, two
 // barriers per layer); weight fragments are prefetched through a register ring whose issue order is pinned with
 // sched_barrier; 32- or 64-row workgroups (ST).  DESIGN.md section 3.2 has the measured breakdown.
-// Included by tdmpc2_plan.hip inside its anonymous namespace.
+// Included by k_fused.hip (and the units that build on the family: k_cluster.hip, k_model.hip, k_policy_loss.hip), each inside its
+// anonymous namespace.
 #pragma once
 
 #include "kloop_schedule.h"  // kloop_asm's schedule arithmetic (shared with tests/test_ring_schedule.py)

@@ -2,7 +2,7 @@
 // tdmpc2.py:122-136): which rollout kernel a call takes (one workgroup per row tile, a cluster of 8 per 32-row tile, two clusters
 // per tile), 32- or 64-row workgroups, whether ks_pitraj runs or the first rollout launch folds it in, grid and dynamic LDS of every
 // launch, whether the refit rides in the rollout launch, and what ks_setup arms.  Pure functions of the handle's scalars;
-// tdmpc2_plan.hip launches what they say, tests/test_fused_route.py compiles this header with g++ and checks them on the CPU
+// plan_run.hip launches what they say, tests/test_fused_route.py compiles this header with g++ and checks them on the CPU
 // (tests/fused_route_model.py) against the launches a GPU recorded (profiles/fused_route_launches.txt).
 #pragma once
 #include <cstddef>

@@ -1,6 +1,6 @@
 // Host-side declarations shared by the translation units of libtdmpc2_plan.so: the handle, the packed-weight records, and
-// the launcher interfaces through which tdmpc2_plan.hip (C ABI, bind, fused-family host code) reaches kernels that are
-// instantiated in other translation units (k_fused.hip / k_cluster.hip per action padding, k_layered.hip).
+// the error reporting every unit uses.  The launcher interfaces through which the host units (plan_*.hip: the C ABI) reach the
+// kernels, each family instantiated in a k_*.hip unit of its own, are launch.h's; what the host units share, plan_host.h's.
 #pragma once
 #include <atomic>
 #include <chrono>
@@ -12,7 +12,7 @@
 
 namespace tdk {
 
-// error reporting (tdmpc2_last_error): defined in tdmpc2_plan.hip
+// error reporting (tdmpc2_last_error): defined in plan_core.hip
 int fail(int code, const char *fmt, ...);
 #define HIP_TRY(expr)                                                                          \
     do {                                                                                       \
@@ -105,7 +105,7 @@ struct tdmpc2_plan {
     // per-task tables of policy_value / td_target on multitask batches (grown on demand)
     float *beff_tab = nullptr, *mask_tab = nullptr, *disc_tab = nullptr;
     int *task_rows = nullptr;  // [rows] copy of the row -> task map, padded to whole GEMM tiles (layered family)
-    int tab_tasks = 0;
+    size_t tab_tasks = 0;      // tasks the three tables hold (they grow together)
     size_t task_rows_cap = 0;
     // model rollout / losses (tdmpc2_plan_model_rollout / model_losses): zs [H + 1, B, L] when the caller does not ask for it, and
     // the per-row loss terms [3 + num_q][H B]; grown at first use
@@ -127,7 +127,7 @@ struct tdmpc2_plan {
     int cl2_mode = 1;                // TDMPC2_CLUSTER2=0: off
     int cl_fault = 0;                // TDMPC2_CLUSTER_FAULT=1 at create: test hook of the bounded waits
     int faults = 0;                  // cluster plans that gave up since the last tdmpc2_plan_take_fault
-    // Recovery from a reported wait (fault_note / fault_clean, tdmpc2_plan.hip): the paths with inter-workgroup waits are switched
+    // Recovery from a reported wait (fault_note / fault_clean, plan_core.hip): the paths with inter-workgroup waits are switched
     // off when a wait gives up and switched back on after `rearm_after` consecutive clean calls (doubling, up to 4096, every time
     // a fault follows a re-arm: a box that keeps faulting -- co-tenancy -- settles on the paths without waits)
     bool degraded = false;
@@ -138,7 +138,7 @@ struct tdmpc2_plan {
     int clean_calls = 0;             // consecutive calls without a fault since the downgrade
     int faults_total = 0, rearms = 0;
     std::chrono::steady_clock::time_point last_fault{};
-    // stream hand-over (StreamTurn, tdmpc2_plan.hip): the event every call leaves on its stream; a call on another stream waits for it
+    // stream hand-over (StreamTurn: plan_host.h, plan_core.hip): the event every call leaves on its stream; a call on another stream waits for it
     hipEvent_t turn_ev = nullptr;
     hipStream_t turn_stream = nullptr;
     bool turn_valid = false;

@@ -1,31 +1,14 @@
 // Translation unit of the replay buffer (tdmpc2_buffer_*): the kernels of buffer_kernels.cuh and the whole host side of the
-// handle -- it shares nothing with a planner handle, so its C ABI lives here and not in tdmpc2_plan.hip.  Every decision
+// handle -- it shares nothing with a planner handle, so its C ABI lives here and not in the planner's host units (plan_*.hip).  Every decision
 // (ring / table arithmetic, draws, access widths, grids, offsets) is buffer_route.h's; this file checks arguments, walks what the
 // header returns and launches.
 #include "handle.h"
+#include "dev_guard.h"
 #include "buffer_route.h"
 
 namespace {
 using namespace tdk;
 #include "buffer_kernels.cuh"
-
-struct BufDevGuard {  // run on the handle's device, restore the caller's
-    int prev = -1;
-    bool ok = true;
-    explicit BufDevGuard(int dev) {
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess) cur = -1;
-        if (cur != dev) {
-            ok = hipSetDevice(dev) == hipSuccess;
-            if (ok) prev = cur;
-        }
-    }
-    ~BufDevGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-    BufDevGuard(const BufDevGuard &) = delete;
-    BufDevGuard &operator=(const BufDevGuard &) = delete;
-};
 }  // namespace
 
 struct tdmpc2_buffer {
@@ -90,7 +73,7 @@ int buf_write_episodes(tdmpc2_buffer *b, uint64_t n_eps, uint32_t steps, const v
         if (!fields[f]) return fail(TDMPC2_ERR_INVALID, "%s: null pointer for field %d", what, f);
     BusyGuard bg(b);
     if (!bg.ok) return fail(TDMPC2_ERR_STATE, "%s: the handle is in use by another thread", what);
-    BufDevGuard dg(b->cfg.device);
+    DevGuard dg(b->cfg.device);
     if (!dg.ok) return fail(TDMPC2_ERR_HIP, "%s: cannot select device %d", what, b->cfg.device);
     if (int rc = buf_reserve(b)) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -164,7 +147,7 @@ int tdmpc2_buffer_create(const tdmpc2_buffer_cfg *cfg, tdmpc2_buffer_t **out) {
 void tdmpc2_buffer_destroy(tdmpc2_buffer_t *b) {
     if (!b) return;
     {
-        BufDevGuard dg(b->cfg.device);
+        DevGuard dg(b->cfg.device);
         if (b->dev) (void)hipFree(b->dev);
     }
     delete b;
@@ -187,7 +170,7 @@ int tdmpc2_buffer_sample(tdmpc2_buffer_t *b, int32_t batch, void *const *outs, i
     if (b->ring.count == 0)
         return fail(TDMPC2_ERR_STATE, "buffer_sample: no episode with at least %d live steps (%llu episodes written)", b->cfg.slice_len,
                     (unsigned long long)b->ring.num_eps);
-    BufDevGuard dg(b->cfg.device);
+    DevGuard dg(b->cfg.device);
     if (!dg.ok) return fail(TDMPC2_ERR_HIP, "buffer_sample: cannot select device %d", b->cfg.device);
     hipStream_t st = (hipStream_t)stream;
 
@@ -234,7 +217,7 @@ int tdmpc2_buffer_stats(tdmpc2_buffer_t *b, tdmpc2_buffer_info *info, void *stre
     if (!b || !info) return fail(TDMPC2_ERR_INVALID, "buffer_stats: null argument");
     uint32_t words[BST_WORDS] = {0, 0, b->pending_call, 0};
     if (b->dev) {
-    BufDevGuard dg(b->cfg.device);
+    DevGuard dg(b->cfg.device);
     if (!dg.ok) return fail(TDMPC2_ERR_HIP, "buffer_stats: cannot select device %d", b->cfg.device);
     HIP_TRY(hipMemcpyAsync(words, b->d_state, sizeof words, hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
@@ -253,7 +236,7 @@ int tdmpc2_buffer_set_call_counter(tdmpc2_buffer_t *b, uint32_t next_call, void 
         b->pending_call = next_call;
         return 0;
     }
-    BufDevGuard dg(b->cfg.device);
+    DevGuard dg(b->cfg.device);
     if (!dg.ok) return fail(TDMPC2_ERR_HIP, "buffer_set_call_counter: cannot select device %d", b->cfg.device);
     hipLaunchKernelGGL(k_buf_set_call, dim3(1), dim3(64), 0, (hipStream_t)stream, b->d_state, next_call);
     LAUNCH_CHECK();

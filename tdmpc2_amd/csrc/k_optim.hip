@@ -3,6 +3,7 @@
 // the step.  Every decision (layout, chunks, the order of the norm, grids, the device block) is optim_route.h's; this file checks
 // arguments, then launches.  A step allocates nothing, copies nothing from the host and never synchronises: it can be captured.
 #include "launch.h"  // handle.h + grid_fits
+#include "dev_guard.h"
 #include "optim_route.h"
 
 namespace {
@@ -10,24 +11,6 @@ using namespace tdk;
 #include "optim_kernels.cuh"
 
 static_assert(sizeof(OptSeg) == 32 && sizeof(OptState) == 40, "device records of optim_route.h");
-
-struct OptDevGuard {  // run on the handle's device, restore the caller's
-    int prev = -1;
-    bool ok = true;
-    explicit OptDevGuard(int dev) {
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess) cur = -1;
-        if (cur != dev) {
-            ok = hipSetDevice(dev) == hipSuccess;
-            if (ok) prev = cur;
-        }
-    }
-    ~OptDevGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-    OptDevGuard(const OptDevGuard &) = delete;
-    OptDevGuard &operator=(const OptDevGuard &) = delete;
-};
 
 // the refusals of layout and create, in one place: nothing here touches a device
 int opt_validate(const tdmpc2_optim_cfg *cfg, const char *what) {
@@ -117,7 +100,7 @@ int tdmpc2_optim_create(const tdmpc2_optim_cfg *cfg, tdmpc2_optim_t **out) {
     st.b1p = st.b2p = 1.0;
     memcpy(img.data() + o->lay.state_off, &st, sizeof st);
 
-    OptDevGuard dg(o->device);
+    DevGuard dg(o->device);
     if (!dg.ok) {
         delete o;
         return fail(TDMPC2_ERR_HIP, "optim_create: cannot select device %d", cfg->device);
@@ -137,7 +120,7 @@ int tdmpc2_optim_create(const tdmpc2_optim_cfg *cfg, tdmpc2_optim_t **out) {
 void tdmpc2_optim_destroy(tdmpc2_optim_t *o) {
     if (!o) return;
     {
-        OptDevGuard dg(o->device);
+        DevGuard dg(o->device);
         if (o->dev) (void)hipFree(o->dev);
     }
     delete o;
@@ -146,7 +129,7 @@ void tdmpc2_optim_destroy(tdmpc2_optim_t *o) {
 int tdmpc2_optim_step(tdmpc2_optim_t *o, float *grad, float *exp_avg, float *exp_avg_sq, int zero_grad, float *norm_out, void *stream) {
     if (!o) return fail(TDMPC2_ERR_INVALID, "optim_step: null handle");
     if (!grad || !exp_avg || !exp_avg_sq) return fail(TDMPC2_ERR_INVALID, "optim_step: null arena (grad, exp_avg, exp_avg_sq)");
-    OptDevGuard dg(o->device);
+    DevGuard dg(o->device);
     if (!dg.ok) return fail(TDMPC2_ERR_HIP, "optim_step: cannot select device %d", o->device);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((uint32_t)o->chunks), block(OPT_THREADS);
@@ -175,7 +158,7 @@ int tdmpc2_optim_step(tdmpc2_optim_t *o, float *grad, float *exp_avg, float *exp
 
 int tdmpc2_optim_get_step(tdmpc2_optim_t *o, int64_t *step, void *stream) {
     if (!o || !step) return fail(TDMPC2_ERR_INVALID, "optim_get_step: null argument");
-    OptDevGuard dg(o->device);
+    DevGuard dg(o->device);
     if (!dg.ok) return fail(TDMPC2_ERR_HIP, "optim_get_step: cannot select device %d", o->device);
     OptState s{};
     HIP_TRY(hipMemcpyAsync(&s, o->dev + o->lay.state_off, sizeof s, hipMemcpyDeviceToHost, (hipStream_t)stream));
@@ -187,7 +170,7 @@ int tdmpc2_optim_get_step(tdmpc2_optim_t *o, int64_t *step, void *stream) {
 int tdmpc2_optim_set_step(tdmpc2_optim_t *o, int64_t step, void *stream) {
     if (!o) return fail(TDMPC2_ERR_INVALID, "optim_set_step: null handle");
     if (step < 0) return fail(TDMPC2_ERR_INVALID, "optim_set_step: step %lld < 0", (long long)step);
-    OptDevGuard dg(o->device);
+    DevGuard dg(o->device);
     if (!dg.ok) return fail(TDMPC2_ERR_HIP, "optim_set_step: cannot select device %d", o->device);
     // the products a run of `step` steps would have made on the device: IEEE fp64 multiplications in the same order
     OptState &s = o->staged;

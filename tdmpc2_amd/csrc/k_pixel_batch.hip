@@ -1,5 +1,5 @@
 // Translation unit of the pixel encoder's batch route (tdmpc2_plan_encode_pix_batch): the MFMA kernels of
-// pixel_batch_kernels.cuh behind pixb_launch of launch.h.  The host side (checks, passes, the C ABI) is in tdmpc2_plan.hip.
+// pixel_batch_kernels.cuh behind pixb_launch of launch.h.  The host side (checks, passes, the C ABI) is in plan_obs.hip.
 #include "launch.h"
 
 namespace {

@@ -1,5 +1,6 @@
 // Translation unit of the policy prior (WorldModel.pi and act() with mpc = False): the row-route, GEMV and head kernels of
-// policy_kernels.cuh behind the pol_* launchers of launch.h.  The host side (bind, routes, the C ABI) is in tdmpc2_plan.hip.
+// policy_kernels.cuh behind the pol_* launchers of launch.h.  The host side is in plan_obs.hip (routes, the C ABI) and
+// plan_weights.hip (bind).
 #include "launch.h"
 
 namespace {

@@ -1,6 +1,6 @@
 // Translation unit of the weight packer (tdmpc2_plan_bind_weights / bind_encoder / bind_policy / refresh_weights /
 // soft_update_target): the kernels of refresh_kernels.cuh behind refresh_launch of launch.h.  The host side (job checks, job
-// table, the C ABI) is in tdmpc2_plan.hip.
+// table, the C ABI) is in plan_weights.hip.
 #include "launch.h"
 
 namespace {

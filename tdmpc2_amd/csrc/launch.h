@@ -2,6 +2,7 @@
 // in exactly one translation unit; everything else reaches it through these functions / tables.
 #pragma once
 #include "handle.h"
+#include "encoder_params.h"  // state encoder (k_plan.hip: encoder_kernels.cuh)
 #include "pixel_batch_route.h"
 #include "policy_route.h"
 #include "seed_route.h"  // at file scope before refresh_route.h (below, inside tdk) includes it for its __host__ / __device__ shim
@@ -39,6 +40,31 @@ struct PolGemvParams {
 struct PolHeadParams {
     const float *y;  // [n, 2A] output-layer pre-activations
     PolHeadArgs head;
+};
+
+// Kernel parameter types.  The state encoder's, the pixel planning routes' and the noise export's kernels were written with their
+// parameter blocks beside them, inside their unit's anonymous namespace, and a kernel's symbol carries its parameter type's
+// namespace.  The blocks the host fills are the *Args below (and encoder_params.h's); a kernel unit derives its own empty
+// `struct XParams : XArgs {}` from them, so those kernels keep their symbols -- what tools/isa_digest.py and recorded profiles
+// key on -- and their code.
+// ---- pixel encoder, planning routes (k_plan.hip: pixel_kernels.cuh, routes in pixel_route.h)
+struct PixArgs {
+    const float *wp[PIX_LAYERS];    // [cin][k][k][C] re-packed Conv2d weights
+    const float *bias[PIX_LAYERS];  // [C]
+    const void *obs;                // [E, cin, 64, 64] uint8 (obs_u8) or fp32
+    int obs_u8, cin, C;
+    const int32_t *shift;           // [E, 2] (dx, dy), clamped to [0, 6] in the kernels
+    const PixTap *tab;              // [PIX_SHIFTS][PIX_IN]
+    float *ws;                      // spread route: [E][pix_ws_floats(C)] outputs of layers 0..2
+    float *z;                       // [E, 16 C]
+};
+
+// ---- the in-kernel generator as a noise tape (k_export_noise, k_plan.hip; tdmpc2_plan_export_noise): environments [e0, e0 + n)
+struct NoiseExportArgs {
+    int e0, n, H, N, P, A, K, I, nq, hp;
+    unsigned long long seed;
+    unsigned int call;
+    tdmpc2_noise_out o;
 };
 
 // ---- pixel encoder, batch route (k_pixel_batch.hip: pixel_batch_kernels.cuh, decisions in pixel_batch_route.h)
@@ -89,7 +115,19 @@ inline int set_lds(K kernel, size_t bytes) {
     return 0;
 }
 
-// ---- elite selection + refit, one workgroup per plan (k_refit, tdmpc2_plan.hip)
+// ---- state encoder (k_plan.hip): the host computes grid, block and LDS and checks hipGetLastError after a call's launches
+void enc_launch_encode(const EncodeArgs &p, int grid, int threads, size_t lds, hipStream_t st);
+void enc_launch_gemv(const EncGemvArgs &p, int gx, int gy, int threads, size_t lds, hipStream_t st);
+void enc_launch_norm(const EncNormArgs &p, int grid, int threads, hipStream_t st);  // (the policy prior's spread route as well)
+// ---- pixel encoder, planning routes (k_plan.hip); checked by the host like the state encoder's
+void pix_launch_image(const PixArgs &p, const PixGrid &g, hipStream_t st);
+void pix_launch_spread(int layer, const PixArgs &p, const PixGrid &g, hipStream_t st);  // (static LDS only)
+void pix_launch_pack(const float *w, float *wp, int C, int cin, int kk, int grid, int threads, hipStream_t st);
+// ---- per-task first-layer biases of the fused family's value calls, and the noise export (k_plan.hip); checked by the host
+void launch_task_bias(const TaskBiasParams &p, int n_tasks, hipStream_t st);
+void launch_export_noise(const NoiseExportArgs &p, int grid, int threads, hipStream_t st);
+
+// ---- elite selection + refit, one workgroup per plan (k_refit, k_plan.hip)
 int launch_refit(const RefitParams &fp, int E, int N, size_t lds, hipStream_t st);
 // The refit of CEM iteration `it` of a plan (both families, whole and sharded plans).  err: the handle's error word where the
 // plan ran kernels with bounded waits (the final pick then returns NaN and keeps prev_mean), else null.

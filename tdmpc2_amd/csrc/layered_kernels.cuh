@@ -6,8 +6,8 @@
 // nn.Linear of the reference becomes one LDS-tiled fp32-MFMA GEMM launch over all E*N sample rows of all
 // plans, followed by one row-wise kernel for the LayerNorm / Mish / SimNorm / two-hot / policy-head math
 // (reference: tdmpc2/common/layers.py:94-133, tdmpc2/common/math.py:12-83, tdmpc2/common/world_model.py:114-216).
-// Included by tdmpc2_plan.hip inside its anonymous namespace (device helpers mish_f, symexp_f, group_*, rng_* are
-// defined there).
+// Included by k_layered.hip inside its anonymous namespace (device helpers mish_f, symexp_f, group_*, rng_* are
+// common.cuh's).
 #pragma once
 
 

@@ -12,7 +12,7 @@
 // g_gemm_s<NCT>: 128 x (128 NCT) output tile per 256-thread workgroup; wave w owns 32 NCT output columns for all 128 rows
 // (4 row tiles x NCT column tiles): every weight fragment (2 KB per k16-block, from L2) feeds 12 MFMAs and the row
 // fragments come from LDS (8 ds_read_b128 per block, shared by the NCT column tiles).
-// Included by tdmpc2_plan.hip inside its anonymous namespace, after fused_kernels.cuh and layered_kernels.cuh.
+// Included by k_layered.hip inside its anonymous namespace, after fused_kernels.cuh and layered_kernels.cuh.
 #pragma once
 
 // byte offset of the hi half of element (row, col) in a fragment-packed operand buffer with KB k16-blocks per row (lo: + 1024)

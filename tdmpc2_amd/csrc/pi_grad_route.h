@@ -71,7 +71,7 @@ __host__ __device__ inline void pg_decode(const PgGrid &g, uint64_t block, int &
 // the step of a row of PG_K_Q or an element of PG_K_SE
 __host__ __device__ inline int pg_step_of(const PgDesc &d, uint64_t unit) { return seed_step_of(d, unit); }
 
-// ---- bin k of torch.linspace(vmin, vmax, num_bins) in fp32, as the planner's handle forms its table (tdmpc2_plan.hip): the float
+// ---- bin k of torch.linspace(vmin, vmax, num_bins) in fp32, as the planner's handle forms its table (plan_core.hip): the float
 // step, the product and the sum in fp64, rounded once; the upper half counted down from vmax
 __host__ __device__ inline float pg_bin(const PgDesc &d, int k) {
     const float step = (d.vmax - d.vmin) / (float)(d.num_bins - 1);

@@ -3,7 +3,7 @@
 // the GEMM view of a layer (which output element a row / column is, which tap a k-index is, which input element a (row, k)
 // reads), the work decomposition (tiles, grid, LDS, the item of a wave, the element of an accumulator register), layer 0's
 // staging of the resampled patch, and the passes of a call over the reserved workspace.  Geometry, workspace layout and the
-// ShiftAug table are pixel_route.h's.  Pure functions; pixel_batch_kernels.cuh and tdmpc2_plan.hip call them,
+// ShiftAug table are pixel_route.h's.  Pure functions; pixel_batch_kernels.cuh and plan_obs.hip call them,
 // tests/test_pixel_batch_route.py compiles this header with g++ and checks them on the CPU (tests/pixel_batch_route_model.py).
 #pragma once
 #include "pixel_route.h"

@@ -4,20 +4,11 @@
 // the weights are re-packed at bind to [cin][k][k][C] so that a tap's PIX_CO weights are one float4 (the same address across a
 // wave).  ShiftAug and the preprocessing run inside the first convolution: every tap samples the uint8 / fp32 frames through the
 // resampling table of pixel_route.h (source indices + bilinear weights), so the resampled stack is never stored.
-// Routes, grids and work items: pixel_route.h.  Included by tdmpc2_plan.hip inside its anonymous namespace.
+// Routes, grids and work items: pixel_route.h.  Included by k_plan.hip inside its anonymous namespace.
 #pragma once
 #include "pixel_route.h"
 
-struct PixParams {
-    const float *wp[PIX_LAYERS];    // [cin][k][k][C] re-packed Conv2d weights
-    const float *bias[PIX_LAYERS];  // [C]
-    const void *obs;                // [E, cin, 64, 64] uint8 (obs_u8) or fp32
-    int obs_u8, cin, C;
-    const int32_t *shift;           // [E, 2] (dx, dy), clamped to [0, 6] here
-    const PixTap *tab;              // [PIX_SHIFTS][PIX_IN]
-    float *ws;                      // spread route: [E][pix_ws_floats(C)] outputs of layers 0..2
-    float *z;                       // [E, 16 C]
-};
+struct PixParams : PixArgs {};  // the kernels' own name for the block of launch.h ("kernel parameter types" there)
 
 template <bool U8>
 __device__ __forceinline__ float pix_px(const void *plane, int off) {

@@ -1,6 +1,6 @@
 // The pixel encoder's geometry (tdmpc2/common/layers.py:36-71, 136-150: ShiftAug, PixelPreprocess, four Conv2d, Flatten,
 // SimNorm) and its launch routes: which route encodes a call, the grids, the work item of every thread, the LDS of a workgroup,
-// the workspace bind allocates, and ShiftAug's resampling table.  Pure functions; pixel_kernels.cuh and tdmpc2_plan.hip call
+// the workspace bind allocates, and ShiftAug's resampling table.  Pure functions; pixel_kernels.cuh, plan_obs.hip and plan_weights.hip call
 // them, tests/test_pixel_route.py compiles this header with g++ and checks them on the CPU (tests/pixel_route_model.py).
 #pragma once
 #include <cmath>

@@ -1,7 +1,7 @@
 // What tdmpc2_plan_create decides for a configuration before it touches the device: whether the configuration is accepted, which
 // kernel family and arithmetic it gets, every derived scalar the handle stores, and the device buffers the handle owns from the
 // start -- which exist, how large each is, which start zeroed.  Pure functions of (configuration, compute units, creation-time
-// switches); tdmpc2_plan.hip allocates what they return.  Plain C++ (no HIP types, no allocation, no environment), like
+// switches); plan_core.hip allocates what they return.  Plain C++ (no HIP types, no allocation, no environment), like
 // layer_route.h: tests/test_plan_layout.py compiles it with g++, and tests/layer_route_model.py takes the capacities the routes
 // are tested with from here.  (The lazily grown sets -- weights, encoders, task tables, model / policy-loss rows -- are not here.)
 #pragma once
@@ -46,7 +46,7 @@ inline int plan_maxct(const tdmpc2_plan_cfg &c) { return (std::max(c.mlp_dim, c.
 inline long plan_cus(int num_cus) { return num_cus > 0 ? num_cus : DEFAULT_CUS; }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// The creation-time switches (tdmpc2_plan.hip fills them from the environment once, at the top of create)
+// The creation-time switches (plan_core.hip fills them from the environment once, at the top of create)
 struct CreateEnv {
     bool one_stream = false;  // TDMPC2_ONE_STREAM (set): layered family without its second chain
     bool fuse_ln = true;      // TDMPC2_FUSE_LN: NormedLinear epilogue inside the GEMM (layered, split arithmetic)

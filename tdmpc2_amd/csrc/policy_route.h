@@ -1,7 +1,7 @@
 // The policy prior's launch routes (WorldModel.pi, tdmpc2/common/world_model.py:144-184: _pi = NormedLinear(Mish) ->
 // NormedLinear(Mish) -> Linear(2A), then the Gaussian head of common/math.py:12-29): which route a call takes, the rows per
 // GEMV workgroup, the grid, threads and LDS of every launch, the work item of every thread, and the workspace binding
-// allocates.  Pure functions; policy_kernels.cuh and tdmpc2_plan.hip call them, tests/test_policy_route.py compiles this
+// allocates.  Pure functions; policy_kernels.cuh and plan_obs.hip call them, tests/test_policy_route.py compiles this
 // header with g++ and checks them on the CPU (tests/policy_route_model.py).
 #pragma once
 #include <cstddef>

@@ -1,7 +1,7 @@
 // Which operations a call that stores weights enqueues (tdmpc2_plan_refresh_weights / soft_update_target with a table,
 // tdmpc2_plan_bind_weights / bind_encoder / bind_policy with one layer), as a pure function of what the jobs name and of the
 // handle's arithmetic.  Compilable on the host, no HIP types: tests/test_refresh_route.py builds it with the host compiler.
-// The host side (tdmpc2_plan.hip) walks the list; the kernels are in refresh_kernels.cuh.
+// The host side (plan_weights.hip) walks the list; the kernels are in refresh_kernels.cuh.
 //
 // A call is at most REFRESH_MAX_OPS = 4 launches, whatever the model: every launch is GROUPED over a job table (one job per
 // (net, layer), all ensemble members inside it), so the count depends on neither num_q nor the number of nets or layers.

@@ -78,7 +78,7 @@ def expected(family, B, H, nq, nb, episodic, want, cap):
 
 
 def expected_launches(family, B, H, nq, episodic, want, cap, ln_after):
-    """Kernel launches of an accepted call, counted from the launch sequences of tdmpc2_plan.hip / model_layered_host.cuh."""
+    """Kernel launches of an accepted call, counted from the launch sequences of plan_train.hip / model_layered_host.cuh."""
     e = expected(family, B, H, nq, 101, episodic, want, cap)
     n = 2 if e["losses"] else 0                       # consistency rows, tail
     if family == FUSED:

@@ -34,7 +34,7 @@ EXPF_ULP = 0.84
 LOGF_ULP = 3.0
 
 
-# ------------------------------------------------------------------ the kernel's branch decisions (common.cuh, tdmpc2_plan.hip)
+# ------------------------------------------------------------------ the kernel's branch decisions (common.cuh, plan_run.hip)
 def sort_width(N):
     M = 64
     while M < N:

@@ -41,6 +41,23 @@ def test_library_exports_every_declared_symbol(lib):
     assert lib.tdmpc2_plan_abi_version() == native.ABI_VERSION
 
 
+def test_hooks_library_exports_what_the_product_exports(lib):
+    """libtdmpc2_plan_hooks.so is the product's objects with one host unit built -DTDMPC2_TEST_HOOKS in place of the plain one: the
+    dynamic symbols the two define under the library's prefix are the same list."""
+    from tdmpc2_amd import native
+
+    if not os.path.exists(native.hooks_lib_path()):
+        pytest.skip("hooks library not built")
+
+    def exports(path):
+        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+        return sorted(line.split()[-1] for line in out.splitlines() if "tdmpc2_" in line)
+
+    product = exports(native.lib_path())
+    assert set(_declared_symbols()) <= set(product)
+    assert exports(native.hooks_lib_path()) == product
+
+
 def test_cfg_struct_matches_header_layout():
     from tdmpc2_amd import native
 

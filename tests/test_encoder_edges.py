@@ -31,7 +31,7 @@ def _stages64(c):
 
 
 def test_limits_are_the_librarys():
-    src = open(os.path.join(CSRC, "encoder_kernels.cuh")).read()
+    src = open(os.path.join(CSRC, "encoder_params.h")).read()
 
     def const(name):
         return eval(re.search(rf"constexpr \w+ {name} = ([0-9 *]+);", src).group(1))
@@ -42,8 +42,8 @@ def test_limits_are_the_librarys():
     assert "ENC_MAX_IN = (int)(ENC_GEMV_LDS_MAX / 4) - 256" in src and ec.ENC_MAX_IN == 16128
     # the request k_enc_gemv's launch makes for the widest input is the limit itself; one more column is over it
     assert (ec.ENC_MAX_IN + 256) * 4 == ec.ENC_GEMV_LDS_MAX < (ec.ENC_MAX_IN + 1 + 256) * 4
-    host = open(os.path.join(CSRC, "tdmpc2_plan.hip")).read()
-    assert "((size_t)L.in + 256) * 4" in host and host.count("> ENC_MAX_IN") == 2   # ensure_enc_alloc (bind, import) and launch_encode
+    host = "".join(open(os.path.join(CSRC, f)).read() for f in ("plan_weights.hip", "plan_obs.hip"))
+    assert "((size_t)L.in + 256) * 4" in host and host.count("> ENC_MAX_IN") == 2   # ensure_enc_alloc (bind, import: plan_weights.hip) and launch_encode (plan_obs.hip)
 
 
 def test_cases_reach_their_edges():

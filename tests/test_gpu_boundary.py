@@ -125,7 +125,7 @@ def test_a_handle_moved_to_another_stream_orders_its_own_calls():
     """One handle = one workspace: a plan on the NULL stream followed AT ONCE by a plan of the same handle on a non-blocking
     stream (no wait_stream in between -- what test_plan_is_hip_graph_capturable did, and what made it fail whenever a second
     hardware queue already existed: profiles/README.md 'r03k, root cause') must not overlap.  The handle leaves an event
-    behind every call and makes the first call on a different stream wait for it (StreamTurn, tdmpc2_plan.hip)."""
+    behind every call and makes the first call on a different stream wait for it (StreamTurn: plan_host.h, plan_core.hip)."""
     from tests.gpu_common import case_on_gpu, plan_inputs
 
     c, model, planner = case_on_gpu("c1")

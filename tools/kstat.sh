@@ -1,6 +1,6 @@
 #!/bin/bash
 # device-side assembly of one build variant -> VGPRs / scratch bytes of every kernel matching a pattern
-# usage: tools/kstat.sh "<extra flags>" [kernel-name regex] [translation unit: k_fused.hip (default, -DTU_APAD=48) | k_cluster.hip | k_layered.hip | tdmpc2_plan.hip]
+# usage: tools/kstat.sh "<extra flags>" [kernel-name regex] [translation unit: k_fused.hip (default, -DTU_APAD=48) | k_cluster.hip | k_layered.hip | k_plan.hip | any other k_*.hip]
 R="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
 out="${KSTAT_OUT:-/tmp/kstat.s}"
 TU="${3:-k_fused.hip}"

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build a VARIANT of the library for a same-call A/B (tools/gpu_ab.sh): the objects of the in-tree build are reused, only the
 # translation unit(s) whose flags differ are recompiled (seconds for the layered unit, about a minute for a fused one).
-# usage: tools/variant.sh <name> <unit>:"<flags>" [<unit>:"<flags>" ...]      units: main layered fused cluster
+# usage: tools/variant.sh <name> <unit>:"<flags>" [<unit>:"<flags>" ...]      units: main (the host units plan_*.hip) plank layered fused cluster ... (build.sh)
 #   e.g. tools/variant.sh wr4 fused:"-DKLOOP_RING=4"   ->  build/ablate/lib_wr4.so
 set -euo pipefail
 R="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
