@@ -48,9 +48,10 @@ def fp64_encode(cfg, sd, obs, tasks):
     return x.numpy()
 
 
-def fp64_pi(cfg, sd, z, tasks, eps):
-    """The reference's pi in float64 on z (fp32 inputs promoted): {mean, log_std, action, entropy, scaled_entropy}."""
-    d = lambda a: torch.as_tensor(np.asarray(a)).double()  # noqa: E731
+def fp64_pi(cfg, sd, z, tasks, eps, dtype=torch.float64):
+    """The reference's pi in float64 on z (fp32 inputs promoted): {mean, log_std, action, entropy, scaled_entropy}.  `dtype`
+    torch.float32: the same formula in the reference's own arithmetic on the CPU (tests/policy_edges_common.py's ref32)."""
+    d = lambda a: torch.as_tensor(np.asarray(a)).to(dtype)  # noqa: E731
     x = d(z)
     mask = None
     if tasks is not None:
